@@ -1,6 +1,6 @@
 """Headline benchmark: stylized 256x256 stroke patches / second at batch 32 on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 256] [--batch 32] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 256] [--batch 32] [--no-cpu] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started without a torchrun environment and --gpus N > 1, it launches the N ranks itself (one process per GPU through
@@ -23,6 +23,10 @@ multiplies; never "f32" for a split mode).  At N=1 the same process then measure
 each with value / ms_per_step / roofline / live parity against the fp32 CPU oracle; `value_fp32_parity` = the `h3`
 number (SURVEY 8d's "fp32 parity mode": products to ~2^-22).  `cpu_baseline` = the CPU oracle (port of the reference
 path) timed on this box's host cores on a bounded sample.
+
+--dump-outputs DIR writes what the headline leg's last timed step returned to its caller -- the uint8 RGBA tiles of the
+primary mode, rank 0's batch -- as DIR/rgba_u8.npy in float32 (see dump_outputs).  Weights and inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -212,9 +216,10 @@ def traffic_lookup(table, kname):
     return None
 
 
-def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, sampler=None, calib=None):
+def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, sampler=None, calib=None, outputs=None):
     """W warm-up steps, then exactly K timed steps of the hot path in one arithmetic mode, bracketed by barrier +
-    synchronize; returns this mode's figures (value, ms_per_step, roofline of its dominant kernel)."""
+    synchronize; returns this mode's figures (value, ms_per_step, roofline of its dominant kernel).  ``outputs`` (a dict):
+    receives the uint8 RGBA tiles of the last timed step of the leg `value` is measured on, as a host array."""
     from brushstroke_engine_amd.sharding import TileGatherer
     z, geom, pos = inputs
     B = args.batch
@@ -256,7 +261,7 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
                 with torch.cuda.stream(getattr(pipe, "tail_stream", None) or pipe.main_stream):
                     gatherer.finish()
                     gatherer.start(u8)
-            return
+            return u8
         # without a gather the step is enqueued without joining the generator's sub-batch streams, so consecutive
         # steps overlap across them (the timed region ends with a device-wide synchronize)
         res = G.render_triad(z=z, geom_feature=geom, positions=pos, render_mode="clear", join=False)
@@ -269,6 +274,7 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
             else:
                 gatherer.finish()
                 gatherer.start(res[0])
+        return res
 
     # The library's throughput schedule (pipeline.ConcurrentTriadSteps; the headline since round 6): independent steps dealt round-robin
     # to k HIP streams with a workspace slot each -- the other chains' kernels fill the CUs one chain leaves idle in its kernel tails
@@ -290,6 +296,7 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
             with torch.cuda.stream(conc.last_stream):
                 g_.finish()
                 g_.start(u8)
+        return u8
 
     def finish_conc():
         for g_ in conc_gatherers:
@@ -377,7 +384,7 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
     t0 = time.perf_counter()
     for i_ in range(args.steps):
         G.synthesis.event_filter = dom_layers if i_ % args.event_every == 0 else none_
-        step()
+        last = step()
     finish_gathers()
     torch.cuda.synchronize()
     elapsed_local = time.perf_counter() - t0
@@ -387,6 +394,10 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
     elapsed = time.perf_counter() - t0
     if sampler is not None:
         sampler.unmark(mode)                    # (moved on below when the concurrent leg follows)
+    if outputs is not None and conc is None:    # (a pipeline returns the tiles; render_triad a tuple, or a joining callable)
+        last = last() if callable(last) else last
+        outputs["rgba_u8"] = (last if torch.is_tensor(last) else last[0]).cpu().numpy()
+    last = None
     events = G.synthesis.layer_events
     G.synthesis.layer_events, G.synthesis.event_filter, G.synthesis.event_pool = None, None, None
 
@@ -440,7 +451,7 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step_conc()
+            last = step_conc()
         finish_conc()
         torch.cuda.synchronize()
         elapsed_local = time.perf_counter() - t0
@@ -450,6 +461,9 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
         elapsed = time.perf_counter() - t0
         if sampler is not None:
             sampler.unmark(mode)
+        if outputs is not None:
+            outputs["rgba_u8"] = last.cpu().numpy()
+        last = None
         elapsed, per_rank_ms = reduce_times(elapsed, elapsed_local)
         gather_wait = gather_wait_of(conc_gatherers)
         schedule = (f"{conc.streams} independent steps in flight, dealt round-robin to {conc.streams} HIP streams with a workspace slot each "
@@ -599,6 +613,32 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
 
 
 MAX_LINE_BYTES = 4096               # the final stdout line: the driver keeps the last 8 KB of stdout
+DUMP_LIMIT_BYTES = 64 * 2**20       # --dump-outputs: all files together
+NPY_HEADER_BYTES = 4096             # (an upper bound of one .npy file's header)
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes every array of ``arrays`` ({name: array}) as ``dirname/<name>.npy`` in float32.  If they do not fit ``limit`` bytes,
+    each keeps the same fixed, seeded sample of its leading axis (patches), in ascending order, and the indices taken go to
+    ``dirname/<name>_index.npy`` (float64).  Returns {file name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    full = sum(a.size * 4 + NPY_HEADER_BYTES for a in arrays.values())
+    idx = None
+    if full > limit:
+        n = min(a.shape[0] for a in arrays.values())
+        per_item = sum(a[0].size * 4 + 8 for a in arrays.values())
+        k = (limit - 2 * NPY_HEADER_BYTES * len(arrays)) // per_item
+        if k < 1:
+            raise ValueError(f"--dump-outputs: one patch of the outputs is larger than {limit} bytes")
+        idx = np.sort(np.random.RandomState(0).choice(n, min(k, n), replace=False))
+    written = {}
+    for name, a in arrays.items():
+        parts = {name: a.astype(np.float32)} if idx is None else {name: a[idx].astype(np.float32), f"{name}_index": idx.astype(np.float64)}
+        for fn, arr in parts.items():
+            np.save(os.path.join(dirname, f"{fn}.npy"), arr)
+            written[f"{fn}.npy"] = list(arr.shape)
+    return written
 
 
 def _pick(d, keys):
@@ -722,6 +762,10 @@ def main():
     ap.add_argument("--full-line", action="store_true", help="print the FULL record on stdout instead of the compact line (the A/B scripts under "
                                                              "tools/ read its calibration tables); never what the driver runs")
     ap.add_argument("--detail", default=None, help="where the full record goes (default: bench_detail.json next to this file)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline leg's last timed step returned (the primary mode's uint8 RGBA "
+                         "tiles of rank 0's batch) as DIR/rgba_u8.npy in float32; a fixed, seeded sample of the patches if the whole "
+                         f"would exceed {DUMP_LIMIT_BYTES >> 20} MB")
     ap.add_argument("--event-every", type=int, default=4,
                     help="bracket the dominant kernel's launches with HIP events in every K-th timed step (an event pair costs ~10 us "
                          "of stream time, which a single chain of launches cannot hide)")
@@ -734,6 +778,8 @@ def main():
         args.schedule = "pipeline" if args.pipeline else "prefetch"
     if args.streams < 0 or args.streams > 8:
         ap.error("--streams must lie in 0..8")
+    if args.dump_outputs and args.res * args.res * 4 * 4 + 8 > DUMP_LIMIT_BYTES - 2 * NPY_HEADER_BYTES:
+        ap.error(f"--dump-outputs: one {args.res}x{args.res} patch exceeds {DUMP_LIMIT_BYTES >> 20} MB")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # self-launch: N ranks as a child torchrun.  Nothing in this process has touched the GPU (importing torch does
@@ -869,9 +915,11 @@ def main():
     sampler = _tele.PowerClockSampler(_tele.find_hwmon(_tele.pci_bus_id_of(local_rank)) if os.environ.get("NB_TELEMETRY", "1") != "0" else None)
     sampler.__enter__()
     gens, results = {}, {}
+    dumped = {} if (args.dump_outputs and rank == 0) else None
     for m in modes:
         gens[m] = Generator(cfg, sd, conv_mode=m).to(dev)
-        results[m] = measure_mode(gens[m], m, args, cfg, (z, geom, pos), world, rank, dev, backend, gather, sampler=sampler, calib=calib)
+        results[m] = measure_mode(gens[m], m, args, cfg, (z, geom, pos), world, rank, dev, backend, gather, sampler=sampler, calib=calib,
+                                  outputs=dumped if m == args.conv_mode else None)
     G = gens[args.conv_mode]
     prim = results[args.conv_mode]
     if rank == 0:
@@ -930,6 +978,9 @@ def main():
         except OSError as e:
             out["detail_file"] = f"(not written: {e})"
         final_line = json.dumps(out) if args.full_line else fit_line(compact_line(out))
+        if dumped is not None:
+            files = dump_outputs(args.dump_outputs, dumped)
+            print(f"[bench] outputs of the last timed step ({args.conv_mode}) written to {args.dump_outputs}: {files}", file=sys.stderr, flush=True)
     sampler.__exit__(None, None, None)
     if use_pg:
         dist.barrier()

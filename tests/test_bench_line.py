@@ -98,3 +98,22 @@ def test_debug_env_names_map_onto_declared_setters():
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".h")):
             assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """--dump-outputs: the whole output in float32 while it fits, else the same seeded sample of patches on every run, with the indices
+    taken; all files together within the limit."""
+    import numpy as np
+    b = _bench()
+    tiles = np.random.RandomState(3).randint(0, 256, (6, 16, 16, 4)).astype(np.uint8)
+    assert b.dump_outputs(str(tmp_path / "all"), {"rgba_u8": tiles}) == {"rgba_u8.npy": [6, 16, 16, 4]}
+    got = np.load(tmp_path / "all" / "rgba_u8.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, tiles)
+    limit = 2 * b.NPY_HEADER_BYTES + 3 * (16 * 16 * 4 * 4 + 8)              # room for three of the six patches
+    for run in ("a", "b"):
+        files = b.dump_outputs(str(tmp_path / run), {"rgba_u8": tiles}, limit=limit)
+        assert files == {"rgba_u8.npy": [3, 16, 16, 4], "rgba_u8_index.npy": [3]}
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= limit
+    idx = np.load(tmp_path / "a" / "rgba_u8_index.npy")
+    assert idx.dtype == np.float64 and list(idx) == sorted(set(idx)) and np.array_equal(idx, np.load(tmp_path / "b" / "rgba_u8_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "rgba_u8.npy"), tiles[idx.astype(int)])

@@ -1,20 +1,18 @@
 """Formats row: websocket binary protocol, brush libraries, engine snapshot container.  The cross-checks
-against the reference's own functions run only where /root/reference exists (the build container)."""
+against the reference read what its own functions and generator produced (tests/golden/formats_ref.npz, made by
+tests/golden/make_golden_formats.py); no test here needs the reference tree."""
+import argparse
 import os
 import pickle
 import subprocess
 import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO
+from conftest import REPO, load_golden
 from brushstroke_engine_amd import config as cfgmod, encoder as encmod, formats, painting, weights as wmod
-
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 
 
 def _request(w, h, x, y, m, rs):
@@ -41,36 +39,16 @@ def test_protocol_roundtrip():
         formats.binary_to_image_patches(msg[:40])
 
 
-@needs_ref
 def test_protocol_matches_reference():
-    sys.path.insert(0, REF)
-    # import stubs for packages the container lacks (nothing of them is exercised by the three functions compared)
-    for name in ("tornado", "tornado.websocket", "tornado.web", "tornado.gen", "skimage", "skimage.io", "skimage.filters",
-                 "torchvision"):
-        if name not in sys.modules:
-            m = types.ModuleType(name)
-            m.__path__ = []
-            sys.modules[name] = m
-    sys.modules["tornado.websocket"].WebSocketHandler = object
-    sys.modules["tornado"].gen = sys.modules["tornado.gen"]
-    sys.modules["tornado.gen"].coroutine = lambda f: f
-    sys.modules["skimage.io"].imread = sys.modules["skimage.io"].imsave = None
-    sys.modules["skimage.filters"].threshold_otsu = sys.modules["skimage.filters"].threshold_local = None
-    import matplotlib
-    matplotlib.use("Agg")
-    import thirdparty.stylegan2_ada_pytorch  # noqa: F401
-    try:
-        import forger.ui.util as ref
-    except Exception as e:                                    # other optional dependencies of the UI module
-        pytest.skip(f"reference ui module not importable here: {e}")
-    rs = np.random.RandomState(1)
-    msg, stroke = _request(16, 16, 3, 4, 2, rs)
-    a, b = ref.binary_to_image_patches(msg), formats.binary_to_image_patches(msg)
-    assert {k: int(v) for k, v in a[0].items()} == b[0] and np.array_equal(a[1], b[1])
-    assert ref.image_patch_to_binary(stroke, 7, 8) == formats.image_patch_to_binary(stroke, 7, 8)
-    head = bytes([0, 1, 3, 2, 9, 8, 7])
-    ra, rb = ref.decode_render_request_metadata(head), formats.decode_render_request_metadata(head)
-    assert ra[1] == rb[1] and list(ra[0]["colors"][0]) == list(rb[0]["colors"][0])
+    """The three protocol functions against the reference's (forger/ui/util.py) on the same messages."""
+    g = load_golden("formats_ref.npz")
+    msg, stroke = _request(16, 16, 3, 4, 2, np.random.RandomState(1))
+    assert msg == g["proto_msg"].tobytes()                    # the message the reference decoded
+    meta, img = formats.binary_to_image_patches(msg)[:2]
+    assert meta == dict(zip(g["proto_meta_keys"].tolist(), g["proto_meta_values"].tolist())) and np.array_equal(img, g["proto_img"])
+    assert formats.image_patch_to_binary(stroke, 7, 8) == g["proto_patch_binary"].tobytes()
+    meta, off = formats.decode_render_request_metadata(g["proto_head"].tobytes())
+    assert off == int(g["proto_head_offset"]) and list(meta["colors"][0]) == g["proto_head_color0"].tolist()
 
 
 def test_seed_and_w_libraries(tmp_path):
@@ -124,37 +102,56 @@ def test_engine_snapshot_roundtrip(tmp_path):
     wmod.validate_state_dict(cfg2, sd2)
 
 
-@needs_ref
+# A stand-in for the two reference modules tools/convert_snapshot.py opens a snapshot with: the network pickle becomes the object
+# graph the converter reads (generator attributes, blocks' conv1, state_dict(), encoder, args), built from plain data.
+STUB_FILES = {
+    "thirdparty/__init__.py": "",
+    "thirdparty/stylegan2_ada_pytorch/__init__.py": "",
+    "thirdparty/stylegan2_ada_pytorch/dnnlib/__init__.py": "from . import util\n",
+    "thirdparty/stylegan2_ada_pytorch/dnnlib/util.py": "def open_url(url):\n    return open(url, 'rb')\n",
+    "thirdparty/stylegan2_ada_pytorch/legacy.py": '''
+import pickle
+from types import SimpleNamespace as NS
+
+
+def load_network_pkl(f):
+    d = pickle.load(f)
+    g, sd = d["G_ema"], d["G_ema"]["state_dict"]
+    blocks = {f"b{r}": NS(conv1=NS(weight=sd[f"synthesis.b{r}.conv1.weight"], conv_clamp=g["conv_clamp"])) for r in g["block_resolutions"]}
+    syn = NS(block_resolutions=g["block_resolutions"], geom_feature_channels=g["geom_feature_channels"],
+             geom_feature_resolutions=g["geom_feature_resolutions"], **blocks)
+    return dict(d, G_ema=NS(z_dim=g["z_dim"], w_dim=g["w_dim"], img_resolution=g["img_resolution"], synthesis=syn, state_dict=lambda: dict(sd)))
+''',
+}
+
+
 def test_convert_reference_snapshot(tmp_path):
-    """tools/convert_snapshot.py on a snapshot pickled from the reference's own classes."""
-    mk = tmp_path / "mk.py"
-    mk.write_text(f'''
-import sys, types, argparse, pickle, numpy as np, torch
-sys.dont_write_bytecode = True
-sys.path.insert(0, {REPO!r}); sys.path.insert(0, {REF!r})
-import thirdparty.stylegan2_ada_pytorch
-import thirdparty.stylegan2_ada_pytorch.dnnlib as dnnlib
-from thirdparty.stylegan2_ada_pytorch.training.networks_modified import Generator
-from thirdparty.stylegan2_ada_pytorch.training.networks import Discriminator
-import forger.experimental.autoenc.simple_autoencoder as sa
-from brushstroke_engine_amd import config as cfgmod, weights as wmod, encoder as encmod
-cfg = cfgmod.style1_config(128); sd = wmod.random_state_dict(cfg, seed=0)
-G = Generator(z_dim=64, c_dim=0, w_dim=64, img_resolution=128, img_channels=3, mapping_kwargs=dnnlib.EasyDict(num_layers=4),
-              synthesis_kwargs=dnnlib.EasyDict(channel_base=16384, channel_max=128, num_fp16_res=0, conv_clamp=256, architecture="orig",
-                                               color_format="triad", color_w_channels=0, enable_geom_linear=False,
-                                               geom_feature_channels=[16, 256], geom_feature_resolutions=[16, 32])).eval().requires_grad_(False)
-G.load_state_dict({{k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}}, strict=True)
-ap = argparse.ArgumentParser(); sa.add_model_flags(ap); ea = ap.parse_args([]); ea.preproc_type = "inverse"
-esd = {{k: torch.from_numpy(v) for k, v in encmod.random_encoder_state_dict(5).items()}}
-D = Discriminator(c_dim=0, img_resolution=128, img_channels=3, architecture="orig", channel_base=16384, channel_max=128)
-snap = dict(G=G, D=D, G_ema=G, training_set_kwargs=None, augment_pipe=None,
-            args=argparse.Namespace(color_format="triad", geom_inject_resolutions=[0, 1]), encoder={{"args": ea, "model_state": esd}})
-pickle.dump(snap, open({str(tmp_path / "snap.pkl")!r}, "wb"))
-''')
+    """tools/convert_snapshot.py on a snapshot of a reference generator: its key names, shapes and attributes are those of the
+    reference's Generator (style1 shapes, R=128) that loaded this build's state dict strictly (tests/golden/formats_ref.npz)."""
+    g = load_golden("formats_ref.npz")
+    cfg = cfgmod.style1_config(128)
+    sd = wmod.random_state_dict(cfg, seed=0)
+    keys = g["snap_keys"].tolist()
+    assert sorted(keys) == sorted(sd.keys())
+    for k, shape in zip(keys, g["snap_shapes"].tolist()):
+        assert list(np.shape(sd[k])) == [d for d in shape if d >= 0], k
+    ref = tmp_path / "reference"
+    for name, text in STUB_FILES.items():
+        (ref / name).parent.mkdir(parents=True, exist_ok=True)
+        (ref / name).write_text(text)
+    z_dim, w_dim, res = g["snap_dims"].tolist()
+    snap = {"G_ema": dict(z_dim=z_dim, w_dim=w_dim, img_resolution=res, block_resolutions=g["snap_block_resolutions"].tolist(),
+                          conv_clamp=int(g["snap_conv_clamp"]), geom_feature_channels=g["snap_geom_feature_channels"].tolist(),
+                          geom_feature_resolutions=g["snap_geom_feature_resolutions"].tolist(),
+                          state_dict={k: torch.from_numpy(np.asarray(sd[k])) for k in keys}),
+            "args": argparse.Namespace(color_format="triad", geom_inject_resolutions=[0, 1]),
+            "encoder": {"args": argparse.Namespace(preproc_type="inverse"),
+                        "model_state": {k: torch.from_numpy(v) for k, v in encmod.random_encoder_state_dict(5).items()}}}
+    with open(tmp_path / "snap.pkl", "wb") as f:
+        pickle.dump(snap, f)
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    subprocess.check_call([sys.executable, str(mk)], env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     out = str(tmp_path / "engine.npz")
-    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "convert_snapshot.py"), "--reference", REF,
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "convert_snapshot.py"), "--reference", str(ref),
                            "--pkl", str(tmp_path / "snap.pkl"), "--out", out], env=env, stdout=subprocess.DEVNULL)
     cfg, sd, esd, pre, extra = formats.load_engine_snapshot(out)
     assert cfg == cfgmod.style1_config(128) and pre == "inverse" and extra["geom_inject_resolutions"] == [0, 1]

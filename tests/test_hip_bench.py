@@ -136,3 +136,26 @@ def test_train_bench_two_ranks_gradient_all_reduce():
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["value"] > 0 and "all-reduce" in out["config"]["parallelism"]
+
+
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes what the headline leg's last timed step returned -- the primary mode's uint8 RGBA tiles, in float32 --
+    and `--steps` sets the timed steps.  The tiles are the ones Generator.render_triad gives for the seeded weights and inputs of
+    bench.py (rank 0), bit for bit."""
+    import numpy as np
+    import torch
+    from brushstroke_engine_amd import config as cfgmod, synthetic, weights as wmod
+    from brushstroke_engine_amd.networks import Generator
+    r = _run(["--steps", "3", "--warmup", "1", "--res", "128", "--batch", "8", "--no-latency", "--no-cpu", "--modes", "primary",
+              "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _last_line(r.stdout)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    got = np.load(tmp_path / "rgba_u8.npy")
+    assert got.dtype == np.float32 and got.shape == (8, 128, 128, 4) and os.listdir(tmp_path) == ["rgba_u8.npy"]
+    cfg, dev = cfgmod.style1_config(128), torch.device("cuda:0")
+    G = Generator(cfg, wmod.random_state_dict(cfg, seed=0), conv_mode=out["conv_mode"]).to(dev)
+    u8 = G.render_triad(z=torch.from_numpy(synthetic.batch_z(cfg, 8, first_seed=0)).to(dev).to(torch.float32),
+                        geom_feature=[torch.from_numpy(g).to(dev) for g in synthetic.geom_features(cfg, 8, seed=0)],
+                        positions=torch.from_numpy(synthetic.positions(cfg, 8, seed=0)).to(dev), render_mode="clear")[0]
+    assert np.array_equal(got, u8.cpu().numpy().astype(np.float32))

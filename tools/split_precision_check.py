@@ -1,5 +1,5 @@
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 torch.set_num_threads(8)
 from brushstroke_engine_amd import config as cfgmod, weights as wmod, synthetic
 from oracle import neube_oracle as orc

@@ -6,8 +6,8 @@
        K values = [16 channels x {xl, x}] of one pixel and tap).
 End-to-end pixel error of the R=128 generator against the fp32 oracle on the three weight sets the GPU tests use (random,
 trained-like, hdr).  CPU simulation of the arithmetic only (the convolution itself runs in float64)."""
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 torch.set_num_threads(8)
 from brushstroke_engine_amd import config as cfgmod, weights as wmod, synthetic
 from oracle import neube_oracle as orc

@@ -1,8 +1,8 @@
 """Would fp8 (e4m3, fixed scales) be enough for the two CORRECTION products of the split-f16 scheme?
 x*w ~= xh*wh [f16 x f16]  +  fp8(xl*2^9)*fp8(wh) * 2^-9  +  fp8(xh/4)*fp8(wl*2^11) * 2^-9     (mode 'f8')
 End-to-end pixel error of the R=128 generator against the fp32 oracle (CPU simulation; the GPU kernel does not exist)."""
-import sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 torch.set_num_threads(8)
 from brushstroke_engine_amd import config as cfgmod, weights as wmod, synthetic
 from oracle import neube_oracle as orc
