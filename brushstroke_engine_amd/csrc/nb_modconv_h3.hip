@@ -2147,7 +2147,7 @@ static int g_force_tqh = -1;
 extern "C" void nb_debug_set_up2_tile(int tqh) { g_force_tqh = tqh; }
 // the 8-wave form with the software-pipelined K loop (nb_modconv_up2v.hip)
 bool nb_up2v_eligible(int in_fmt, int c_in, int h, int w);
-int nb_up2v_launch(H3Up2Params p, int n, int in_fmt, void* stream, unsigned long long* tstamps, int tstamps_cap);
+int nb_up2v_launch(H3Up2Params p, int n, int in_fmt, void* stream, unsigned long long* tstamps, int tstamps_cap, bool auto_rows);
 #ifndef NB_UP2V_AUTO
 #define NB_UP2V_AUTO 1          // 1: f8 launches on the 12-row throughput tiles run on the software-pipelined kernel
 #endif
@@ -2260,7 +2260,7 @@ static int nb_up2_h3_impl(const void* x_h2, int c_in, const void* w_h3, const fl
         case UP2_W16: return nb_up2_h3_launch<8, 16>(p, n, in_fmt, stream);
         case UP2_W8: return nb_up2_h3_launch<8, 8>(p, n, in_fmt, stream);
         case UP2_PAIR: return nb_up2_h3_launch<NB_H3_TQH, 16, 4, 2>(p, n, in_fmt, stream);
-        case UP2_V2: return nb_up2v_launch(p, n, in_fmt, stream, g_tstamps, g_tstamps_cap);
+        case UP2_V2: return nb_up2v_launch(p, n, in_fmt, stream, g_tstamps, g_tstamps_cap, g_force_v2 < 0);      // (forced: 12-row tiles)
         case UP2_MID: return nb_up2_h3_launch<NB_H3_TQH_MID>(p, n, in_fmt, stream);
         case UP2_SMALL: return nb_up2_h3_launch<NB_H3_TQH_SMALL>(p, n, in_fmt, stream);
         default: return nb_up2_h3_launch<NB_H3_TQH>(p, n, in_fmt, stream);

@@ -12,6 +12,7 @@
 //   * fragment reads and DMA pieces are dealt out between the MFMAs (one or two reads per gap, a piece behind an fp8 MFMA)
 //     instead of in bursts between the groups, a scheduling fence after every statement: program order is issue order;
 //   * the two 16-byte halves of a block-scaled fp8 operand are read straight into one 8-register tuple (no v_mov assembling).
+// Round 7: 13-row tiles as well (Up2vTile below: 16 full position blocks, two per wave), chosen per launch shape (nb_up2v_rows).
 #include "nb_h3_common.h"
 
 #ifdef NB_ABL6_NOMFMA
@@ -28,17 +29,37 @@
 #define NB_ABL_NODMA 1
 #endif
 namespace {
-constexpr int TQH = 12, TQW = 32, NW = 8, NT = NW * 64;
-constexpr int PH = TQH + 2, PW = TQW + 2, NPOS = PH * PW;            // 14 x 34 = 476 halo'd quad positions
-constexpr int NBLK = (NPOS + 31) / 32, NBJ = 2;                      // 15 position blocks of 32: wave w takes w and w + 8
-constexpr int XR = TQH + 3, XS = TQW + 3, XPL = XR * XS;             // 15 x 35 input pixels = 525 slots per (cg, hi/lo) plane
-constexpr int PP = (XPL + 63) / 64, NXP = 4 * PP;                    // 9 pieces per plane, 36 per chunk
+constexpr int TQW = 32, NW = 8, NT = NW * 64;
+constexpr int PW = TQW + 2, XS = TQW + 3, NBJ = 2;
 constexpr int CO_WG = 32, WROWS = 36, WSLOTS = WROWS * CO_WG, NWP = WSLOTS / 64;     // 18 weight pieces per chunk
-constexpr int NPC = (NXP + NWP + NW - 1) / NW;                       // 7 pieces per wave and chunk (54 dealt as one list, 2 re-copies)
-constexpr int STAGE = 4 * XPL + WSLOTS, NST = 3;                     // 3 x 52 032 B
+constexpr int NST = 3;
 constexpr int N4 = 2;                                                // pieces of chunk c + 3 issued under the last group of chunk c
-constexpr int KMIX = NXP / NW;                                       // the round of the list where the kind changes (4: waves 0-3 activations)
-static_assert(NBLK <= NBJ * NW && KMIX * NW <= NXP && (KMIX + 1) * NW > NXP && NPC == 7, "piece list layout");
+// The tile's geometry by its height (quad rows): 12 or 13.
+//   12: 14 x 34 = 476 halo'd quad positions = 15 blocks of 32 (wave w takes w and w + 8: SIMD 3 runs 3 blocks, the others 4, so the
+//       K loop lasts 16 block-times for 384 quads); 15 x 35 = 525 input slots per (cg, hi/lo) plane; stages of 52 032 B.
+//   13: 15 x 34 = 510 positions = 16 blocks (every wave two: the same 16 block-times for 416 quads); 16 x 35 = 560 slots per plane;
+//       stages of 54 272 B, the ring 162 816 B.  With the 400 B of static tables that leaves 624 B of the 160 KiB: no room for the
+//       12-row form's static noise tile (6 656 B here) nor for the next tile's activation planes (35 840 B) beside the epilogue's
+//       phase slots (131 072 B).  So the noise tile is written behind the K loop, into the ring behind the phase slots (which start
+//       at 0), and no next tile is prefetched under the epilogue: 131 072 + 6 656 = 137 728 B of the ring.
+// Both: 9 pieces per plane, 36 activation + 18 weight pieces per chunk dealt as one list of 7 per wave (2 re-copies).
+template <int TQH_>
+struct Up2vTile {
+    static constexpr int TQH = TQH_, PH = TQH + 2, NPOS = PH * PW, NBLK = (NPOS + 31) / 32;
+    static constexpr int XR = TQH + 3, XPL = XR * XS, PP = (XPL + 63) / 64, NXP = 4 * PP;
+    static constexpr int NPC = (NXP + NWP + NW - 1) / NW, STAGE = 4 * XPL + WSLOTS;
+    static constexpr int KMIX = NXP / NW;                            // the round of the list where the kind changes (4: waves 0-3 activations)
+    static constexpr int Y1P = NBLK * 32;                            // epilogue phase slots: positions per (group, half, phase) plane
+    static constexpr bool PREFETCH = TQH == 12;                      // the next tile's chunk 0 under the epilogue, the noise tile in static LDS
+    static constexpr size_t Y4_OFF = PREFETCH ? (size_t)4 * XPL * 16 : 0;           // bytes: the phase slots (behind stage 0's activation planes)
+    static constexpr size_t NZ_OFF = Y4_OFF + (size_t)16 * Y1P * 16;                // bytes: the noise tile of the 13-row form
+    static constexpr size_t LDS_RING = (size_t)NST * STAGE * 16;
+    static constexpr size_t LDS_EPI = NZ_OFF + (PREFETCH ? 0 : (size_t)2 * TQH * 2 * TQW * 4);
+    static constexpr size_t LDS = LDS_RING > LDS_EPI ? LDS_RING : LDS_EPI;
+    static_assert(NBLK <= NBJ * NW && KMIX * NW <= NXP && (KMIX + 1) * NW > NXP && NPC == 7, "piece list layout");
+    static_assert(PREFETCH || NBLK == NBJ * NW, "13-row tiles: two full position blocks per wave");
+    static_assert(LDS + 400 + (PREFETCH ? (size_t)2 * TQH * 2 * TQW * 4 : 16) <= 160 * 1024, "LDS budget (dynamic + static)");
+};
 }
 
 // F8: "f8" operands (hi f16 + fp8 correction operands: 14 matrix instructions per tap-chunk and block) or H2 operands (hi / lo f16:
@@ -55,10 +76,15 @@ static_assert(NBLK <= NBJ * NW && KMIX * NW <= NXP && (KMIX + 1) * NW > NXP && N
 // consumer and are dropped by the compiler.
 // PERSIST = false: the same body WITHOUT the tile loop (item_next is the list's end at compile time: no next tile, no prefetch, nothing carried) -- one
 // workgroup per tile, as until round 5 (see modconv3x3_up1_h3_kernel's PERSIST and profiles/r06_ab_variants.txt for why both exist).
-template <bool F8, int OUTM, bool F6 = false, bool HO = false, bool PERSIST = true>
+// TQH_ = 12 or 13 quad rows per tile (Up2vTile): the same per-output arithmetic on both, bit-identical results.
+template <bool F8, int OUTM, bool F6 = false, bool HO = false, bool PERSIST = true, int TQH_ = 12>
 __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Params p) {
     static_assert(!F6 || F8, "the f6 form is a variant of the f8 loop");
     static_assert(!HO || (F8 && !F6), "the hi-only form is a variant of the f8 loop");
+    using TG = Up2vTile<TQH_>;
+    constexpr int TQH = TG::TQH, PH = TG::PH, NPOS = TG::NPOS, NBLK = TG::NBLK, XPL = TG::XPL, PP = TG::PP, NXP = TG::NXP;
+    constexpr int NPC = TG::NPC, STAGE = TG::STAGE, KMIX = TG::KMIX;
+    static_assert(PH * PW == NPOS, "");
     NB_TSTAMP(0);
     if constexpr (OUTM == 2) nb_set_fp16_ovfl();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_v[];
@@ -107,10 +133,13 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
     };
     unsigned item = __builtin_amdgcn_readfirstlane(blockIdx.x);
     tile_coords(item);
-    const int nblk = wv < NBLK - (NBJ - 1) * NW ? NBJ : NBJ - 1;      // blocks wv, wv + 8 (< 15)
+    const int nblk = wv < NBLK - (NBJ - 1) * NW ? NBJ : NBJ - 1;      // blocks wv, wv + 8 (< NBLK)
 
     __shared__ __attribute__((aligned(16))) float s_dco[CO_WG], s_bias[CO_WG], s_nst[CO_WG];
-    __shared__ __attribute__((aligned(16))) float s_noise[2 * TQH * 2 * TQW];
+    // the tile's noise values x gain: static LDS written in the prologue (12 rows), or the ring behind the phase slots written
+    // behind the K loop (13 rows: Up2vTile)
+    __shared__ __attribute__((aligned(16))) float s_noise_st[TG::PREFETCH ? 2 * TQH * 2 * TQW : 4];
+    float* const s_noise = TG::PREFETCH ? s_noise_st : reinterpret_cast<float*>(smem_v + TG::NZ_OFF);
     // per-tile epilogue operands (written at the top of a tile's iteration: the previous tile's epilogue has passed its closing barrier)
     auto load_channel_tables = [&]() {
         kparams_t q_ = fresh_params();
@@ -623,7 +652,8 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
     //      the previous tile's epilogue, its weights behind it); now chunk 1 and the two pieces of chunk 2 that the steady state
     //      issues under the previous chunk's last group.  The tile's epilogue operands and noise values are written meanwhile. ----
     load_channel_tables();
-    {
+    // the noise values x gain of the tile at (tn, tI0, tJ0) into s_noise: here for 12-row tiles; behind the K loop for 13-row tiles
+    auto write_noise = [&](const int tn, const int tI0, const int tJ0) {
         kparams_t q_ = fresh_params();
         const float* noise = q_->noise;
         const long long nstride = q_->noise_stride_n;
@@ -631,19 +661,20 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
         const NbNoiseSrcDev nsrc{q_->nsrc.const_t, q_->nsrc.lin, q_->nsrc.strength, q_->nsrc.norm_pos, q_->nsrc.positions, q_->nsrc.res, q_->nsrc.img_res};
         for (int e = tid; e < 2 * TQH * 2 * TQW; e += NT) {
             const int r = e / (2 * TQW), c = e - r * (2 * TQW);
-            const int oy = 2 * I0 + r, ox = 2 * J0 + c;
-            float v = (noise && oy < 2 * H) ? noise[(size_t)n * nstride + (size_t)oy * (2 * W) + ox] : 0.f;
+            const int oy = 2 * tI0 + r, ox = 2 * tJ0 + c;
+            float v = (noise && oy < 2 * H) ? noise[(size_t)tn * nstride + (size_t)oy * (2 * W) + ox] : 0.f;
             if (nsrc.const_t && oy < 2 * H) {
                 float np0, np1, wx0, wx1, wy0, wy1;
                 int sx0, sy0;
-                nb_noise_np(nsrc, n, np0, np1);
+                nb_noise_np(nsrc, tn, np0, np1);
                 nb_noise_axis(nsrc, oy, np0, sx0, wx0, wx1);
                 nb_noise_axis(nsrc, ox, np1, sy0, wy0, wy1);
                 v = nb_noise_value(nsrc, nsrc.strength[0], sx0, wx0, wx1, sy0, wy0, wy1);
             }
             s_noise[e] = v * gain;
         }
-    }
+    };
+    if constexpr (TG::PREFETCH) write_noise(n, I0, J0);
     if (NC > 1) nb_static_for<0, NPC>([&](auto k) { issue_piece(k, 1, STAGE); });
     if (NC > 2) nb_static_for<0, N4>([&](auto k) { issue_piece(k, 2, 2 * STAGE); });
     // (vmcnt counts the previous tile's epilogue stores too -- older than every piece of this tile: "all but the youngest N" covers them)
@@ -689,10 +720,11 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
     if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) p.y[0] = 0.f; return; }      // ablation: main loop only
     // ---- the NEXT tile's chunk 0, activations: into stage 0's activation planes (the first 33 600 bytes of the ring), which the
     //      epilogue below leaves alone (its phase slots start behind them) -- they travel while the epilogue computes and stores.
-    //      The epilogue keeps THIS tile's coordinates (e_*); the coordinates and piece sources move on to the next tile. ----
+    //      The epilogue keeps THIS tile's coordinates (e_*); the coordinates and piece sources move on to the next tile.
+    //      (13-row tiles: no room beside the phase slots -- the whole chunk 0 goes out behind the epilogue, as with dbg & 64.) ----
     const int e_n = n, e_I0 = I0, e_J0 = J0, e_co0 = co0;
     const unsigned item_next = PERSIST ? __builtin_amdgcn_readfirstlane(item + gridDim.x) : total;
-    const bool has_next = item_next < total && !(p.dbg & 64);          // (dbg & 64: no prefetch -- the next tile's chunk 0 goes out after the epilogue)
+    const bool has_next = TG::PREFETCH && item_next < total && !(p.dbg & 64);      // (dbg & 64: no prefetch -- the next tile's chunk 0 goes out after the epilogue)
     if (item_next < total) {
         tile_coords(item_next);
         piece_sources();
@@ -709,9 +741,9 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
     asm volatile("" : "+v"(l31e), "+v"(lhe), "+s"(wve));
     const int Wo = 2 * W, Ho = 2 * H;
     constexpr int nquads = TQH * TQW;
-    constexpr int Y1P = NBLK * 32;
-    // (the phase slots start behind stage 0's activation planes, where the next tile's first chunk is landing)
-    f32x4* y4 = reinterpret_cast<f32x4*>(smem_v + (size_t)4 * XPL * 16);
+    constexpr int Y1P = TG::Y1P;
+    // (12 rows: the phase slots start behind stage 0's activation planes, where the next tile's first chunk is landing)
+    f32x4* y4 = reinterpret_cast<f32x4*>(smem_v + TG::Y4_OFF);
     const float clampv = p.clamp >= 0.f ? p.clamp : __builtin_inff();
     unsigned long long te_w = 0, te_f = 0, te0 = 0;
 #pragma unroll
@@ -732,6 +764,7 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
                 }
             }
         }
+        if constexpr (!TG::PREFETCH) { if (R == 0) write_noise(e_n, e_I0, e_J0); }     // (13 rows: behind the phase slots; read from round 0 on)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if (p.tstamps) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); te_w += t_ - te0; te0 = t_; }
         auto quad_item = [&](const int wi) {
@@ -840,10 +873,13 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
                 }
             }
         };
-        constexpr int NWI = nquads * 2 / 32;          // 24 wave-iterations of 32 quads x both channel halves per round
-        static_assert(nquads * 2 % 32 == 0 && NWI % NW == 0, "tile quads must fill whole waves");
+        // wave-iterations of 32 quads x both channel halves per round: 12 rows 24 = 3 per wave; 13 rows 26 = 3 per wave + a fourth on
+        // waves 0 and 1 (waves w and w + 4 share a SIMD: 7, 7, 6, 6 per SIMD)
+        constexpr int NWI = nquads * 2 / 32;
+        static_assert(nquads * 2 % 32 == 0 && NWI % NW <= NW / 2, "tile quads must fill whole waves");
 #pragma unroll
         for (int k = 0; k < NWI / NW; ++k) quad_item(wve + k * NW);
+        if constexpr (NWI % NW != 0) { if (wve < NWI % NW) quad_item(NWI / NW * NW + wve); }
         if (p.tstamps) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); te_f += t_ - te0; }
     }
     NB_TSTAMP(4);
@@ -880,51 +916,95 @@ static int g_up2v_persist = -1;
 // developer / test hook: -1 / 1 = persistent workgroups (one per CU, next tile's first chunk prefetched under the epilogue), 0 = one workgroup per tile
 extern "C" void nb_debug_set_up2v_persistent(int mode) { g_up2v_persist = mode; }
 
-template <bool F8, int OUTM, bool F6 = false, bool HO = false, bool PERSIST = true>
-static int nb_up2v_launch1(const H3Up2Params& p, int n, void* stream) {
-    // (epilogue phase slots behind stage 0's activation planes: 33 600 + 122 880 = 156 480 B, 384 more than the ring)
-    constexpr size_t lds_ring = (size_t)NST * STAGE * 16, lds_epi = (size_t)4 * XPL * 16 + (size_t)16 * NBLK * 32 * 16;
-    constexpr size_t lds = lds_ring > lds_epi ? lds_ring : lds_epi;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)modconv3x3_up2v_kernel<F8, OUTM, F6, HO, PERSIST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    // persistent workgroups: one per CU (fewer items than CUs: one each), each walking its items with the next tile's first chunk
-    // prefetched under the current tile's epilogue; g_up2v_persist == 0 (test hook): one workgroup per item, as until round 5
-    static int ncu = 0;
+static long up2v_ncu() {
+    static long ncu = 0;
     if (!ncu) {
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         ncu = v;
     }
+    return ncu;
+}
+
+template <bool F8, int OUTM, bool F6 = false, bool HO = false, bool PERSIST = true, int TQH = 12>
+static int nb_up2v_launch1(const H3Up2Params& p, int n, void* stream) {
+    // (12 rows: epilogue phase slots behind stage 0's activation planes, 33 600 + 122 880 = 156 480 B, 384 more than the ring;
+    //  13 rows: the ring, 162 816 B -- Up2vTile)
+    constexpr size_t lds = Up2vTile<TQH>::LDS;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)modconv3x3_up2v_kernel<F8, OUTM, F6, HO, PERSIST, TQH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+    }
+    // persistent workgroups: one per CU (fewer items than CUs: one each), each walking its items with the next tile's first chunk
+    // prefetched under the current tile's epilogue; g_up2v_persist == 0 (test hook): one workgroup per item, as until round 5
     const int items = p.items;
-    const long want = (long)ncu * g_persist_wgs_per_cu;                  // (workgroups per CU: NB_PERSIST_WGS_PER_CU in nb_modconv_h3.hip)
+    const long want = up2v_ncu() * g_persist_wgs_per_cu;                  // (workgroups per CU: NB_PERSIST_WGS_PER_CU in nb_modconv_h3.hip)
     dim3 grid(PERSIST && items > want ? (unsigned)want : (unsigned)items);
-    hipLaunchKernelGGL((modconv3x3_up2v_kernel<F8, OUTM, F6, HO, PERSIST>), grid, dim3(NT), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((modconv3x3_up2v_kernel<F8, OUTM, F6, HO, PERSIST, TQH>), grid, dim3(NT), lds, (hipStream_t)stream, p);
     NB_CHECK_LAUNCH("modconv3x3_up2v");
     return NB_OK;
 }
 
-// shapes this form takes: whole 16-channel chunks (f8 or H2 operands), 32-column tiles of 12 quad rows
+// shapes this form takes: whole 16-channel chunks (f8 or H2 operands), 32-column tiles of 12 or 13 quad rows
 bool nb_up2v_eligible(int in_fmt, int c_in, int h, int w) { return in_fmt >= 0 && in_fmt <= 3 && c_in % 16 == 0 && w % TQW == 0 && h >= 8; }
 
-// p as filled in by nb_up2_h3_impl (nb_modconv_h3.hip); tiles are set here
-int nb_up2v_launch(H3Up2Params p, int n, int in_fmt, void* stream, unsigned long long* tstamps, int tstamps_cap) {
+static int g_up2v_rows = 0;
+// developer / test hook: 0 = automatic tile height (12 or 13 quad rows by nb_up2v_rows), 12 / 13 = that height
+extern "C" void nb_debug_set_up2v_rows(int rows) { g_up2v_rows = rows; }
+
+// Tile height of a launch.  A full tile's K loop takes 16 block-times at both heights (4 position blocks per SIMD); 13 rows cover 8 %
+// more quads per tile, and a tile whose last rows lie below the image skips the blocks that only feed them (a SIMD's share of the
+// remaining blocks sets the loop's length).  What 13 rows cost per tile: 26 epilogue wave-iterations per round instead of 24, the
+// noise tile written behind the K loop, a cold prologue.  Estimate per launch = rounds of one workgroup per CU x mean tile time,
+// tile = 0.44 us per chunk and block-time of the critical SIMD + the rest of the tile (prologue, epilogue, store drain: 18.5 us at 12
+// rows, 19.7 at 13) -- both from the phase stamps (profiles/r07_phase_times.txt), rough: single launches of one shape differ by up
+// to ~7 % between visits, so the 2 % margin is a tie-breaker, not a noise bound; 13 rows where the estimate is >= 2 % lower.
+static int nb_up2v_rows(int nchunks, int n, int h, int w, int slices, long ncu) {
+    auto est = [&](int tqh, double rest) {
+        const int tiles_y = (h + tqh - 1) / tqh;
+        double sum = 0.0;
+        for (int ty = 0; ty < tiles_y; ++ty) {
+            const int rows = h - ty * tqh < tqh ? h - ty * tqh : tqh;
+            const int blocks = ((rows + 2) * PW + 31) / 32, crit = (blocks + 3) / 4;       // blocks s, s + 4, s + 8, s + 12 on SIMD s
+            sum += 0.44 * nchunks * crit + rest;
+        }
+        const long items = (long)n * (w / TQW) * tiles_y * slices;
+        return (double)((items + ncu - 1) / ncu) * (sum / tiles_y);
+    };
+    return est(13, 19.7) < 0.98 * est(12, 18.5) ? 13 : 12;
+}
+
+// developer / test hook: the tile height nb_up2v_rows picks for a launch shape (c_in in 16-channel chunks)
+extern "C" int nb_debug_up2v_auto_rows(int c_in, int c_out, int n, int h, int w) {
+    return nb_up2v_rows((c_in + 15) / 16, n, h, w, (c_out + CO_WG - 1) / CO_WG, up2v_ncu());
+}
+
+// p as filled in by nb_up2_h3_impl (nb_modconv_h3.hip); tiles are set here.  auto_rows: choose the tile height (else 12 rows, as the
+// test hook nb_debug_set_up2_v2(1) promises; nb_debug_set_up2v_rows overrides both)
+int nb_up2v_launch(H3Up2Params p, int n, int in_fmt, void* stream, unsigned long long* tstamps, int tstamps_cap, bool auto_rows) {
     NB_REQUIRE(nb_up2v_eligible(in_fmt, p.nchunks * 16, p.h, p.w) && p.co_ld % CO_WG == 0, "modconv3x3_up2v: shape not supported");
-    p.tiles_x = p.w / TQW;
-    p.tiles_y = (p.h + TQH - 1) / TQH;
     p.slices = (p.c_out + CO_WG - 1) / CO_WG;
+    const int rows = g_up2v_rows == 12 || g_up2v_rows == 13 ? g_up2v_rows : auto_rows ? nb_up2v_rows(p.nchunks, n, p.h, p.w, p.slices, up2v_ncu()) : 12;
+    p.tiles_x = p.w / TQW;
+    p.tiles_y = (p.h + rows - 1) / rows;
     p.items_x = p.tiles_x * p.tiles_y * p.slices;
     p.items = p.items_x * n;
     p.tstamps = (tstamps && (long long)p.items <= tstamps_cap) ? tstamps : nullptr;
     const int outm = p.yh2 ? (p.out_f8 ? 2 : 1) : 0;
-    // (persistent workgroups: NB_UP2V_PERSIST_DEFAULT; nb_debug_set_up2v_persistent(0 / 1) = never / always)
-    const bool persist = g_up2v_persist >= 0 ? g_up2v_persist != 0 : NB_UP2V_PERSIST_DEFAULT != 0;
-    auto go = [&](auto f8_, auto f6_, auto ho_) {
+    // (persistent workgroups: NB_UP2V_PERSIST_DEFAULT, nb_debug_set_up2v_persistent(0 / 1) = never / always -- at 12 rows.  13-row
+    //  tiles have no room to prefetch under the epilogue: one workgroup per tile, and no persistent instantiation)
+    const bool persist = rows == 12 && (g_up2v_persist >= 0 ? g_up2v_persist != 0 : NB_UP2V_PERSIST_DEFAULT != 0);
+    auto go1 = [&](auto f8_, auto f6_, auto ho_, auto rows_) {
         constexpr bool F8_ = decltype(f8_)::value, F6_ = decltype(f6_)::value, HO_ = decltype(ho_)::value;
-        if (persist) return outm == 2 ? nb_up2v_launch1<F8_, 2, F6_, HO_, true>(p, n, stream) : outm == 1 ? nb_up2v_launch1<F8_, 1, F6_, HO_, true>(p, n, stream) : nb_up2v_launch1<F8_, 0, F6_, HO_, true>(p, n, stream);
-        return outm == 2 ? nb_up2v_launch1<F8_, 2, F6_, HO_, false>(p, n, stream) : outm == 1 ? nb_up2v_launch1<F8_, 1, F6_, HO_, false>(p, n, stream) : nb_up2v_launch1<F8_, 0, F6_, HO_, false>(p, n, stream);
+        constexpr int R_ = decltype(rows_)::value;
+        if constexpr (R_ == 12) {
+            if (persist) return outm == 2 ? nb_up2v_launch1<F8_, 2, F6_, HO_, true, R_>(p, n, stream) : outm == 1 ? nb_up2v_launch1<F8_, 1, F6_, HO_, true, R_>(p, n, stream) : nb_up2v_launch1<F8_, 0, F6_, HO_, true, R_>(p, n, stream);
+        }
+        return outm == 2 ? nb_up2v_launch1<F8_, 2, F6_, HO_, false, R_>(p, n, stream) : outm == 1 ? nb_up2v_launch1<F8_, 1, F6_, HO_, false, R_>(p, n, stream) : nb_up2v_launch1<F8_, 0, F6_, HO_, false, R_>(p, n, stream);
+    };
+    auto go = [&](auto f8_, auto f6_, auto ho_) {
+        return rows == 13 ? go1(f8_, f6_, ho_, std::integral_constant<int, 13>{}) : go1(f8_, f6_, ho_, std::integral_constant<int, 12>{});
     };
     using T = std::true_type; using F = std::false_type;
     if (in_fmt == 3) return go(T{}, F{}, T{});

@@ -55,6 +55,14 @@ void nb_debug_set_up1_persistent(int mode);
  * loop-less instantiation (PERSIST = false).  tests/test_hip_f8.py asserts the two bit-identical. */
 void nb_debug_set_up2v_persistent(int mode);
 
+/* Tile height of the software-pipelined up=2 kernel: 0 (default) = chosen per launch shape (13 quad rows where the estimate of
+ * nb_modconv_up2v.hip says they win, else 12), 12 / 13 = that height wherever the kernel runs (13 rows: one workgroup per tile
+ * whatever nb_debug_set_up2v_persistent says).  Bit-identical outputs
+ * (tests/test_up2v_tile_rows.py). */
+void nb_debug_set_up2v_rows(int rows);
+/* The tile height the automatic choice takes for an up2v launch of this shape (12 or 13). */
+int nb_debug_up2v_auto_rows(int c_in, int c_out, int n, int h, int w);
+
 /* Workgroups per CU of the persistent launches (both kernels above): default 4 (<= 0 restores it) -- a workgroup walks 2-4 tiles of the
  * BASELINE launches and CUs come free four times per launch for other streams' kernels; 1 = every workgroup resident from the start
  * (`profiles/r06_ab_persistent_grid.txt`). */

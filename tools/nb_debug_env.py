@@ -20,6 +20,7 @@ SWITCHES = {
     "NB_UP2_PAIR": ("nb_debug_set_up2_pair", -1),
     "NB_UP2_V2": ("nb_debug_set_up2_v2", -1),
     "NB_UP2V_PERSIST": ("nb_debug_set_up2v_persistent", -1),
+    "NB_UP2V_ROWS": ("nb_debug_set_up2v_rows", 0),
     "NB_UP1_PERSIST": ("nb_debug_set_up1_persistent", -1),
     "NB_PERSIST_WGS": ("nb_debug_set_persistent_wgs_per_cu", 0),
     "NB_SMALL_WAVES": ("nb_debug_set_small_waves", 0),
