@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lock = threading.Lock()
 _lib = None
@@ -119,6 +119,18 @@ PROTOTYPES = {
     "nb_enc_upsample2x_h2_ex": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "nb_enc_stem_conv3x3_f8": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
     "nb_pack_conv_weight": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "nb_pack_conv_weight_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+    "nb_pack_conv_weight_h3f8_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "nb_pack_conv_weight_h3_up2_dev": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    # the whole generator behind one handle (argument structs below)
+    "nb_generator_param_count": (C.c_int, [vp]),
+    "nb_generator_param_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "nb_generator_layer_count": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "nb_generator_layer_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, vp]),
+    "nb_generator_create": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]),
+    "nb_generator_destroy": (C.c_int, [vp]),
+    "nb_generator_forward": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+    "nb_generator_describe": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
 }
 
 
@@ -142,6 +154,37 @@ class NbTorgbArgs(C.Structure):
     _fields_ = [("styles", vp), ("w", vp), ("bias", vp), ("color_bias", vp), ("logits", vp), ("uvs", vp), ("img", vp),
                 ("colors_out", vp), ("user_colors", vp), ("sfactor", vp), ("rgba_f32", vp), ("rgba_u8", vp),
                 ("styles_stride_n", C.c_int), ("render_mode", C.c_int), ("clamp", C.c_float)]
+
+
+class NbGeneratorConfig(C.Structure):
+    """``struct NbGeneratorConfig`` of include/neube_hip.h (config.GeneratorConfig)."""
+    _fields_ = [("z_dim", C.c_int32), ("c_dim", C.c_int32), ("w_dim", C.c_int32), ("img_resolution", C.c_int32),
+                ("mapping_layers", C.c_int32), ("mapping_lr_multiplier", C.c_float), ("channel_base", C.c_int32),
+                ("channel_max", C.c_int32), ("conv_clamp", C.c_float), ("num_geom", C.c_int32),
+                ("geom_channels", C.c_int32 * 4), ("geom_resolutions", C.c_int32 * 4)]
+
+
+class NbGeneratorLayerInfo(C.Structure):
+    """``struct NbGeneratorLayerInfo`` (config.LayerSpec)."""
+    _fields_ = [("block_res", C.c_int32), ("up", C.c_int32), ("in_channels", C.c_int32), ("out_channels", C.c_int32),
+                ("geom_channels", C.c_int32), ("w_index", C.c_int32)]
+
+
+class NbGeneratorInputs(C.Structure):
+    """``struct NbGeneratorInputs``."""
+    _fields_ = [("z", vp), ("ws", vp), ("truncation_psi", C.c_float), ("truncation_cutoff", C.c_int32), ("geom", vp * 4),
+                ("positions", vp), ("noise_mode", C.c_int32), ("render_mode", C.c_int32), ("user_colors", vp), ("sfactor", vp)]
+
+
+class NbGeneratorOutputs(C.Structure):
+    """``struct NbGeneratorOutputs``."""
+    _fields_ = [("rgba_u8", vp), ("rgba", vp), ("img", vp), ("uvs", vp), ("colors", vp)]
+
+
+NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3
+NB_CONV_MODES = {"f32": 0, "h3": 1, "f8": 2, "f6": 3, "f16": 4}
+NB_NOISE_MODES = {"const": 0, "none": 1, "random": 2}
+NB_RENDER_MODES = {"clear": 0, "full": 1}
 
 
 class NeubeHipError(RuntimeError):

@@ -1,0 +1,898 @@
+// The whole generator behind one C handle (include/neube_hip.h, "the whole generator"): device weight packers, the parameter and
+// layer tables of a GeneratorConfig, and the host orchestration of one forward pass -- the launches and per-batch kernel choices of
+// SynthesisNetwork._run_layers (networks.py) on one stream, without torch.
+//
+// The orchestration is a single walk (gen_walk) used three ways: to size the workspaces at creation (every batch up to n_max), to
+// name the kernels a batch will run (nb_generator_describe) and to enqueue a forward pass.  Its decisions are ported from
+// SynthesisNetwork (_h3_eligible and friends, the styles / noise path, positions_once, in-kernel noise, the operand hand-off and the
+// early geometry pack) with the constructor's defaults; what differs is only that the early geometry pack runs in-line on the one
+// stream instead of on a side stream (same kernel, same inputs: same bits).
+#include "nb_h3_common.h"
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+// ------------------------------------------------------------------------------------------------
+// device weight packers
+// ------------------------------------------------------------------------------------------------
+
+// wpk[ci][tap][co] (zero padded to ceil8(c_in) x 9 x ceil32(c_out)) = W[co][ci][tap]
+__global__ __launch_bounds__(256) void gen_pack_wpk_kernel(const float* __restrict__ w, int c_out, int c_in, int co_ld, int total,
+                                                           float* __restrict__ wpk) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int co = idx % co_ld, r = idx / co_ld, tap = r % 9, ci = r / 9;
+    wpk[idx] = (co < c_out && ci < c_in) ? w[((size_t)co * c_in + ci) * 9 + tap] : 0.f;
+}
+
+// wsq[ci][co] = sum_k W[co][ci][k]^2 in the order of torch's reduction kernel for `w.square().sum(dim=[2, 3])` on ROCm
+// (ATen/native/hip/Reduce.cuh: 9 inputs per output -> 8 lanes; lane 0 adds its two inputs 0 and 8, the lanes then combine with
+// shuffle offsets 1, 2, 4), so that the demodulation coefficients of the C path equal the Python path's
+__global__ __launch_bounds__(256) void gen_pack_wsq_kernel(const float* __restrict__ w, int c_out, int c_in, float* __restrict__ wsq) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= c_out * c_in) return;
+    const int co = idx % c_out, ci = idx / c_out;
+    const float* p = w + ((size_t)co * c_in + ci) * 9;
+    float s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = p[k] * p[k];
+    const float a = (s[0] + s[8]) + s[1], b = s[2] + s[3], c = s[4] + s[5], d = s[6] + s[7];
+    wsq[idx] = (a + b) + (c + d);
+}
+
+// "f8" weights: [chunk][tap][cg][hl][ceil64(c_out)][16 bytes]; hl 0 = the 8 f16 hi halves of channel group cg, hl 1 = 16 fp8 e4m3 bytes
+// over the chunk's 16 channels: w (cg 0) or (w - f16(w)) * 2^11 (cg 1), each clamped to +-448 (ops.pack_conv_weight_h3f8)
+__global__ __launch_bounds__(256) void gen_pack_h3f8_kernel(const float* __restrict__ w, int c_out, int c_in, int co_ld, int nch,
+                                                            uint4* __restrict__ out) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;             // ((chunk * 9 + tap) * 2 + cg) * co_ld + co
+    if (idx >= nch * 18 * co_ld) return;
+    const int co = idx % co_ld;
+    int r = idx / co_ld;
+    const int cg = r & 1; r >>= 1;
+    const int tap = r % 9, ch = r / 9;
+    auto wv = [&](int ci) -> float { return (co < c_out && ci < c_in) ? w[((size_t)co * c_in + ci) * 9 + tap] : 0.f; };
+    unsigned hi[4], f8[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const _Float16 h0 = (_Float16)wv(ch * 16 + cg * 8 + 2 * j), h1 = (_Float16)wv(ch * 16 + cg * 8 + 2 * j + 1);
+        hi[j] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float x = wv(ch * 16 + 4 * j + k);
+            v[k] = cg == 0 ? x : (x - (float)(_Float16)x) * 2048.f;
+        }
+        f8[j] = nb_pk2_fp8<true>(v[0], v[1]) | (nb_pk2_fp8<true>(v[2], v[3]) << 16);
+    }
+    const size_t base = ((((size_t)ch * 9 + tap) * 2 + cg) * 2) * co_ld;
+    out[base + co] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+    out[base + co_ld + co] = make_uint4(f8[0], f8[1], f8[2], f8[3]);
+}
+
+// Up=2 phase kernels folded with the FIR (ops.fold_up2_fir: Keff[2 py + px][co, ci, di + 1, dj + 1] = sum_{a, b} W[a, b] g[a - ty + 1,
+// b - tx + 1], ty = py - 2 di, tx = px - 2 dj, g = flip(4 f); float64, a-major, then rounded to fp32) and packed as
+// nb_pack_conv_weight_h3 per phase: out = 4 such images back to back
+__global__ __launch_bounds__(256) void gen_pack_h3_up2_kernel(const float* __restrict__ w, const float* __restrict__ f, int c_out, int c_in,
+                                                              int co_ld, int nch, h8* __restrict__ out) {
+    const int per_phase = nch * 18 * co_ld;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 4 * per_phase) return;
+    const int ph = idx / per_phase, rem = idx % per_phase;
+    const int co = rem % co_ld;
+    int r = rem / co_ld;
+    const int cg = r & 1; r >>= 1;
+    const int tap = r % 9, ch = r / 9;
+    const int py = ph >> 1, px = ph & 1, di = tap / 3 - 1, dj = tap % 3 - 1, ty = py - 2 * di, tx = px - 2 * dj;
+    h8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int ci = ch * 16 + cg * 8 + j;
+        float v = 0.f;
+        if (co < c_out && ci < c_in) {
+            const float* wp = w + ((size_t)co * c_in + ci) * 9;
+            double acc = 0.0;
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) {
+                    const int u = a - ty + 1, vv = b - tx + 1;
+                    if (u >= 0 && u < 4 && vv >= 0 && vv < 4) {
+                        const double g = (double)f[(3 - u) * 4 + (3 - vv)] * 4.0;
+                        const double prod = (double)wp[a * 3 + b] * g;
+                        acc = acc + prod;
+                    }
+                }
+            v = (float)acc;
+        }
+        const _Float16 hh = (_Float16)v;
+        hi[j] = hh;
+        lo[j] = (_Float16)(v - (float)hh);
+    }
+    h8* o = out + (size_t)ph * nch * 36 * co_ld;
+    const size_t base = ((((size_t)ch * 9 + tap) * 2 + cg) * 2) * co_ld;
+    o[base + co] = hi;
+    o[base + co_ld + co] = lo;
+}
+
+extern "C" int nb_pack_conv_weight_dev(const float* w, int c_out, int c_in, float* wpk, float* wsq, void* stream) {
+    NB_REQUIRE(w && c_out > 0 && c_in > 0, "pack_conv_weight_dev: bad arguments");
+    if (wpk) {
+        const int total = (c_in + 7) / 8 * 8 * 9 * ((c_out + 31) / 32 * 32);
+        hipLaunchKernelGGL(gen_pack_wpk_kernel, dim3(nb_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, c_out, c_in,
+                           (c_out + 31) / 32 * 32, total, wpk);
+        NB_CHECK_LAUNCH("pack_conv_weight_dev");
+    }
+    if (wsq) {
+        hipLaunchKernelGGL(gen_pack_wsq_kernel, dim3(nb_cdiv(c_out * c_in, 256)), dim3(256), 0, (hipStream_t)stream, w, c_out, c_in, wsq);
+        NB_CHECK_LAUNCH("pack_conv_weight_dev");
+    }
+    return NB_OK;
+}
+
+extern "C" int nb_pack_conv_weight_h3f8_dev(const float* w, int c_out, int c_in, void* out, void* stream) {
+    NB_REQUIRE(w && out && c_out > 0 && c_in > 0 && (uintptr_t)out % 16 == 0, "pack_conv_weight_h3f8_dev: bad arguments");
+    const int nch = (c_in + 15) / 16, co_ld = (c_out + 63) / 64 * 64;
+    hipLaunchKernelGGL(gen_pack_h3f8_kernel, dim3(nb_cdiv(nch * 18 * co_ld, 256)), dim3(256), 0, (hipStream_t)stream, w, c_out, c_in, co_ld,
+                       nch, (uint4*)out);
+    NB_CHECK_LAUNCH("pack_conv_weight_h3f8_dev");
+    return NB_OK;
+}
+
+extern "C" int nb_pack_conv_weight_h3_up2_dev(const float* w, const float* resample_filter, int c_out, int c_in, void* out, void* stream) {
+    NB_REQUIRE(w && resample_filter && out && c_out > 0 && c_in > 0 && (uintptr_t)out % 16 == 0, "pack_conv_weight_h3_up2_dev: bad arguments");
+    const int nch = (c_in + 15) / 16, co_ld = (c_out + 63) / 64 * 64;
+    hipLaunchKernelGGL(gen_pack_h3_up2_kernel, dim3(nb_cdiv(4 * nch * 18 * co_ld, 256)), dim3(256), 0, (hipStream_t)stream, w,
+                       resample_filter, c_out, c_in, co_ld, nch, (h8*)out);
+    NB_CHECK_LAUNCH("pack_conv_weight_h3_up2_dev");
+    return NB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// small helpers of the generator object
+// ------------------------------------------------------------------------------------------------
+
+// dst[i] = src[i * stride] (noise_lin = noise_grid[0, :, 0, 0])
+__global__ __launch_bounds__(256) void gen_gather_kernel(const float* __restrict__ src, int stride, int count, float* __restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count) dst[i] = src[(size_t)i * stride];
+}
+
+// dst[x * r + y] = src[y * r + x] (noise_const_t)
+__global__ __launch_bounds__(256) void gen_transpose_kernel(const float* __restrict__ src, int r, float* __restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < r * r) dst[i] = src[(i % r) * r + i / r];
+}
+
+// dst[k * count + i] = src[i] for k < reps (the learned constant repeated over the batch)
+__global__ __launch_bounds__(256) void gen_repeat_kernel(const float* __restrict__ src, int count, int reps, float* __restrict__ dst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count * reps) dst[i] = src[i % count];
+}
+
+// Truncation (networks.py:283-289): ws[:, :cutoff] = lerp(w_avg, ws, psi), in the form of torch's lerp (the small-weight branch
+// below 0.5); the summation in torch may differ in the last bit
+__global__ __launch_bounds__(256) void gen_truncate_kernel(float* __restrict__ ws, const float* __restrict__ w_avg, float psi, int n,
+                                                           int num_ws, int w_dim, int cutoff) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int per = cutoff * w_dim;
+    if (i >= n * per) return;
+    const int s = i / per, r = i % per;
+    float* p = ws + (size_t)s * num_ws * w_dim + r;
+    const float a = w_avg[r % w_dim], b = *p;
+    *p = fabsf(psi) < 0.5f ? a + psi * (b - a) : b - (b - a) * (1.f - psi);
+}
+
+// ------------------------------------------------------------------------------------------------
+// configuration: parameter and layer tables (config.GeneratorConfig, weights.random_state_dict)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct GenLayer {
+    std::string name;
+    int block_res, up, in_ch, out_ch, geom_ch, w_index;
+    int in_res() const { return block_res / up; }
+};
+
+struct GenParam {
+    std::string name;
+    int ndim;
+    int64_t shape[4];
+    int64_t numel() const { int64_t v = 1; for (int k = 0; k < ndim; ++k) v *= shape[k]; return v; }
+};
+
+struct GenCfg {
+    NbGeneratorConfig c;
+    int R = 0;
+    std::vector<int> blocks, geom_res, geom_ch;
+    std::vector<GenLayer> layers;
+    std::vector<GenParam> params;
+    int num_ws = 0;
+    int channels(int res) const { return std::min(c.channel_base / res, c.channel_max); }
+    int geom_index(int res) const {
+        for (size_t k = 0; k < geom_res.size(); ++k)
+            if (geom_res[k] == res) return (int)k;
+        return -1;
+    }
+    int layer_index(const std::string& name) const {
+        for (size_t k = 0; k < layers.size(); ++k)
+            if (layers[k].name == name) return (int)k;
+        return -1;
+    }
+};
+
+std::string fmt(const char* f, int a) {
+    char b[96];
+    snprintf(b, sizeof(b), f, a);
+    return b;
+}
+
+void add_param(GenCfg& g, const std::string& name, std::initializer_list<int64_t> shape) {
+    GenParam p;
+    p.name = name;
+    p.ndim = (int)shape.size();
+    int k = 0;
+    for (int64_t v : shape) p.shape[k++] = v;
+    for (; k < 4; ++k) p.shape[k] = 0;
+    g.params.push_back(p);
+}
+
+// validates and expands a configuration; NB_EINVAL (with nb_last_error) on anything GeneratorConfig would reject or this path
+// does not take
+int resolve_cfg(const NbGeneratorConfig* c, GenCfg& g) {
+    NB_REQUIRE(c, "generator: null config");
+    const int R = c->img_resolution;
+    NB_REQUIRE(c->c_dim == 0, "generator: c_dim must be 0 (conditioning labels are not part of this path)");
+    NB_REQUIRE(c->z_dim >= 1 && c->z_dim <= 512 && c->w_dim >= 1 && c->w_dim <= 512, "generator: z_dim and w_dim must be in [1, 512]");
+    NB_REQUIRE(R >= 4 && R <= 4096 && (R & (R - 1)) == 0, "generator: img_resolution must be a power of two >= 4");
+    NB_REQUIRE(c->mapping_layers >= 1 && c->mapping_layers <= 64, "generator: mapping_layers must be in [1, 64]");
+    NB_REQUIRE(c->mapping_lr_multiplier > 0.f, "generator: mapping_lr_multiplier must be positive");
+    NB_REQUIRE(c->channel_max >= 1 && c->channel_base / R >= 1, "generator: channel_base / img_resolution and channel_max must be >= 1");
+    NB_REQUIRE(c->num_geom >= 0 && c->num_geom <= 4, "generator: num_geom must be in [0, 4]");
+    g.c = *c;
+    g.R = R;
+    for (int r = 4; r <= R; r *= 2) g.blocks.push_back(r);
+    bool all_zero = true;
+    for (int k = 0; k < c->num_geom; ++k) all_zero = all_zero && c->geom_resolutions[k] == 0;
+    for (int k = 0; k < c->num_geom; ++k) {
+        NB_REQUIRE(c->geom_channels[k] >= 1 && c->geom_channels[k] <= 4096, "generator: geom_channels[%d] must be in [1, 4096]", k);
+        g.geom_ch.push_back(c->geom_channels[k]);
+        if (all_zero) {
+            NB_REQUIRE(c->num_geom == 2, "generator: the default geometry resolutions (R/8, R/4) need num_geom == 2");
+            g.geom_res.push_back(k == 0 ? R / 8 : R / 4);
+        } else {
+            g.geom_res.push_back(c->geom_resolutions[k]);
+        }
+        const int gr = g.geom_res.back();
+        NB_REQUIRE(gr >= 4 && gr < R && (gr & (gr - 1)) == 0, "generator: geometry resolution %d must be a power of two in [4, R/2]", gr);
+        for (int j = 0; j < k; ++j) NB_REQUIRE(g.geom_res[j] != gr, "generator: geometry resolution %d given twice", gr);
+    }
+    int w = 0;
+    for (int res : g.blocks) {
+        const int oc = g.channels(res);
+        if (res > 4) {
+            const int gi = g.geom_index(res / 2);
+            const int gc = gi < 0 ? 0 : g.geom_ch[gi];
+            g.layers.push_back({fmt("synthesis.b%d.conv0", res), res, 2, g.channels(res / 2) + gc, oc, gc, w++});
+        }
+        g.layers.push_back({fmt("synthesis.b%d.conv1", res), res, 1, oc, oc, 0, w++});
+    }
+    g.num_ws = (int)g.layers.size() + 1;
+    // the state dict, in the order of weights.random_state_dict
+    for (int i = 0; i < c->mapping_layers; ++i) {
+        add_param(g, fmt("mapping.fc%d.weight", i), {c->w_dim, i == 0 ? c->z_dim : c->w_dim});
+        add_param(g, fmt("mapping.fc%d.bias", i), {c->w_dim});
+    }
+    add_param(g, "mapping.w_avg", {c->w_dim});
+    add_param(g, "synthesis.b4.const", {g.channels(4), 4, 4});
+    for (int res : g.blocks) add_param(g, fmt("synthesis.b%d.resample_filter", res), {4, 4});
+    for (const GenLayer& l : g.layers) {
+        add_param(g, l.name + ".weight", {l.out_ch, l.in_ch, 3, 3});
+        add_param(g, l.name + ".noise_strength", {});
+        add_param(g, l.name + ".bias", {l.out_ch});
+        add_param(g, l.name + ".noise_grid", {1, l.block_res, l.block_res, 2});
+        add_param(g, l.name + ".resample_filter", {4, 4});
+        add_param(g, l.name + ".noise_const", {l.block_res, l.block_res});
+        add_param(g, l.name + ".affine.weight", {l.in_ch, c->w_dim});
+        add_param(g, l.name + ".affine.bias", {l.in_ch});
+    }
+    const std::string t = fmt("synthesis.b%d.torgb", R);
+    const int cl = g.channels(R);
+    add_param(g, t + ".weight", {3, cl, 1, 1});
+    add_param(g, t + ".bias", {3});
+    add_param(g, t + ".color_bias", {9});
+    add_param(g, t + ".affine.weight", {cl + 9, c->w_dim});
+    add_param(g, t + ".affine.bias", {cl + 9});
+    return NB_OK;
+}
+
+int copy_name(const std::string& s, char* buf, int len) {
+    if (!buf) return NB_OK;
+    NB_REQUIRE(len > (int)s.size(), "generator: name buffer too short (%d bytes for \"%s\")", len, s.c_str());
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return NB_OK;
+}
+
+}  // namespace
+
+extern "C" int nb_generator_param_count(const NbGeneratorConfig* cfg) {
+    GenCfg g;
+    const int rc = resolve_cfg(cfg, g);
+    return rc ? rc : (int)g.params.size();
+}
+
+extern "C" int nb_generator_param_info(const NbGeneratorConfig* cfg, int i, char* name, int len, int64_t shape[4], int* ndim) {
+    GenCfg g;
+    const int rc = resolve_cfg(cfg, g);
+    if (rc) return rc;
+    NB_REQUIRE(i >= 0 && i < (int)g.params.size(), "generator: parameter index %d out of range [0, %d)", i, (int)g.params.size());
+    const GenParam& p = g.params[i];
+    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
+    if (ndim) *ndim = p.ndim;
+    return copy_name(p.name, name, len);
+}
+
+extern "C" int nb_generator_layer_count(const NbGeneratorConfig* cfg, int* num_ws) {
+    GenCfg g;
+    const int rc = resolve_cfg(cfg, g);
+    if (rc) return rc;
+    if (num_ws) *num_ws = g.num_ws;
+    return (int)g.layers.size();
+}
+
+extern "C" int nb_generator_layer_info(const NbGeneratorConfig* cfg, int i, char* name, int len, NbGeneratorLayerInfo* info) {
+    GenCfg g;
+    const int rc = resolve_cfg(cfg, g);
+    if (rc) return rc;
+    NB_REQUIRE(i >= 0 && i < (int)g.layers.size(), "generator: layer index %d out of range [0, %d)", i, (int)g.layers.size());
+    const GenLayer& l = g.layers[i];
+    if (info) *info = NbGeneratorLayerInfo{l.block_res, l.up, l.in_ch, l.out_ch, l.geom_ch, l.w_index};
+    return copy_name(l.name, name, len);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the generator object
+// ------------------------------------------------------------------------------------------------
+
+struct GenLayerDev {
+    const float *weight = nullptr, *bias = nullptr, *noise_strength = nullptr, *noise_const = nullptr, *affine_w = nullptr,
+                *affine_b = nullptr, *filter = nullptr, *noise_grid = nullptr;
+    float *wpk = nullptr, *wsq = nullptr, *noise_lin = nullptr, *noise_const_t = nullptr;
+    void *w_h3 = nullptr, *w_f8 = nullptr, *w_h3_up2 = nullptr;
+    float *styles = nullptr, *dcoefs = nullptr, *noise = nullptr;
+};
+
+struct NbGenerator {
+    GenCfg cfg;
+    int mode = 0, n_max = 0, device = 0;
+    bool styles_fast = false;
+    float act_gain = 0.f;
+    std::vector<void*> allocs;
+    std::vector<GenLayerDev> L;
+    const float* map_w = nullptr;
+    const float* map_b = nullptr;
+    const float* w_avg = nullptr;
+    const float *trgb_w = nullptr, *trgb_b = nullptr, *trgb_cb = nullptr, *trgb_aw = nullptr, *trgb_ab = nullptr;
+    float* trgb_styles = nullptr;
+    float* const_rep = nullptr;
+    NbLayerDesc* tables = nullptr;   // (layers + 1) tables: table k has noise_const cleared for the conv layers >= k (k = layers: full)
+    float* ws_buf = nullptr;
+    float* npos = nullptr;
+    float* act[2] = {nullptr, nullptr};
+    void* h2[2] = {nullptr, nullptr};
+    std::vector<void*> pre_h2;       // per geometry feature: the consumer's operand tensor its early pack writes (or NULL)
+    float *uvs_ws = nullptr, *img_ws = nullptr, *colors_ws = nullptr;
+    // workspace sizes (bytes) found by the sizing walk
+    size_t need_act = 0, need_h2 = 0;
+    std::vector<size_t> need_pre;
+
+    bool split() const { return mode == NB_CONV_H3 || mode == NB_CONV_F8; }
+    bool clamp_ok() const { return cfg.c.conv_clamp >= 0.f && cfg.c.conv_clamp <= 1024.f; }
+    // SynthesisNetwork._h3_eligible / _h3_up2_eligible / _small_h3_eligible / _small_h3_up2_eligible / _operand_fmt with the
+    // constructor's thresholds (h3_min_pixels 128 * 128, h3_up2_w16_min_batch = h3_up2_w8_min_batch = 16, h3_min_batch 1)
+    bool h3(const GenLayer& s, int n) const {
+        return split() && s.up == 1 && s.block_res >= 32 && (long long)n * s.block_res * s.block_res >= 128 * 128 && s.block_res % 32 == 0 && clamp_ok();
+    }
+    bool h3_up2(const GenLayer& s, int n) const {
+        const int ir = s.in_res();
+        const bool w8 = ir == 8 && n >= 16;
+        return split() && s.up == 2 && ((ir >= 32 && ir % 32 == 0) || (ir == 16 && n >= 16) || w8)
+            && (w8 || (long long)n * s.block_res * s.block_res >= 128 * 128) && clamp_ok();
+    }
+    bool large(const GenLayer& s, int n) const { return s.up == 2 ? h3_up2(s, n) : h3(s, n); }
+    bool small_h3(const GenLayer& s) const {
+        return split() && s.up == 1 && s.block_res <= 64 && s.in_ch % 16 == 0 && s.in_ch <= 512 && clamp_ok();
+    }
+    bool small_h3_up2(const GenLayer& s, const GenLayerDev& d) const {
+        return split() && s.up == 2 && s.in_res() <= 32 && s.in_ch % 16 == 0 && s.in_ch <= 512 && d.w_h3_up2 && clamp_ok();
+    }
+    int operand_fmt(const GenLayer* s) const { return (!s || mode != NB_CONV_F8 || s->in_ch % 16) ? 0 : 1; }
+    const NbLayerDesc* table(int first) const { return tables + (size_t)first * (L.size() + 1); }
+};
+
+namespace {
+
+size_t h2_bytes(int n, int c, int hw) { return (size_t)n * ((c + 7) / 8) * 2 * hw * 8 * sizeof(_Float16); }
+
+struct WalkSink {
+    bool launch = false;                                 // enqueue (else: decisions only)
+    bool sizing = false;                                 // record workspace needs (NbGenerator::need_*)
+    std::string* describe = nullptr;                     // append "layer=kernel" lines
+};
+
+#define GEN_TRY(call)                      \
+    do {                                   \
+        if (sink.launch) {                 \
+            const int rc_ = (call);        \
+            if (rc_ != NB_OK) return rc_;  \
+        }                                  \
+    } while (0)
+
+// One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant or no noise, no taps / blending / resume).
+int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, hipStream_t st, const WalkSink& sink) {
+    const GenCfg& cfg = g->cfg;
+    const std::vector<GenLayer>& specs = cfg.layers;
+    const int nL = (int)specs.size(), R = cfg.R, w_dim = cfg.c.w_dim;
+    const float clamp = cfg.c.conv_clamp < 0.f ? -1.f : cfg.c.conv_clamp;
+    const float alpha = 0.2f, gain = g->act_gain;
+    char vbuf[128];
+
+    // ---- mapping (MappingNetwork.forward) ----
+    const float* ws = in->ws;
+    if (!ws) {
+        GEN_TRY(nb_mapping_ws_f32(in->z, g->map_w, g->map_b, g->ws_buf, n, cfg.c.z_dim, w_dim, cfg.c.mapping_layers,
+                                  cfg.c.mapping_lr_multiplier, cfg.num_ws, st));
+        if (in->truncation_psi != 1.f && sink.launch) {
+            const int cutoff = (in->truncation_cutoff < 0 || in->truncation_cutoff > cfg.num_ws) ? cfg.num_ws : in->truncation_cutoff;
+            if (cutoff > 0) {
+                hipLaunchKernelGGL(gen_truncate_kernel, dim3(nb_cdiv(n * cutoff * w_dim, 256)), dim3(256), 0, st, g->ws_buf, g->w_avg,
+                                   in->truncation_psi, n, cfg.num_ws, w_dim, cutoff);
+                NB_CHECK_LAUNCH("generator: truncation");
+            }
+        }
+        ws = g->ws_buf;
+    }
+
+    // ---- noise sources (_prepare_noise_sources) ----
+    const bool cnoise = in->noise_mode == NB_NOISE_CONST;
+    const int64_t* ipos = cnoise ? in->positions : nullptr;
+    const bool shared = ipos == nullptr;
+    const float* npos_k = nullptr;
+    if (cnoise && ipos && n > 8) {                      // positions_once
+        GEN_TRY(nb_norm_positions_f32(ipos, R, g->npos, n, st));
+        npos_k = g->npos;
+    }
+    int inkernel_from = -1;                            // first layer from which every layer computes its noise itself
+    if (cnoise && ipos) {
+        int k = nL;
+        while (k > 0 && g->large(specs[k - 1], n)) --k;
+        inkernel_from = k < nL ? k : -1;
+    }
+
+    // ---- styles and noise images (_launch_styles_and_noise) ----
+    const int n_tab = nL + 1;
+    if (g->styles_fast && cnoise && n <= 8 && ipos) {
+        GEN_TRY(nb_styles_noise_f32(g->table(inkernel_from < 0 ? nL : inkernel_from), n_tab, ws, cfg.num_ws, w_dim, nullptr, ipos, R, n, st));
+    } else {
+        GEN_TRY((g->styles_fast ? nb_styles_fast_f32 : nb_styles_f32)(g->table(nL), n_tab, ws, cfg.num_ws, w_dim, n, st));
+        if (cnoise) {
+            int hi = n_tab;
+            if (inkernel_from >= 0) hi = std::min(hi, inkernel_from);
+            if (hi > 0) {
+                int max_res = 0;
+                for (int i = 0; i < std::min(hi, nL); ++i) max_res = std::max(max_res, specs[i].block_res);
+                GEN_TRY(nb_noise_f32(g->table(nL), hi, max_res, npos_k, npos_k ? nullptr : ipos, R, n, st));
+            }
+        }
+    }
+
+    // ---- early geometry packs (_pack_geometry_early; in-line on the one stream) ----
+    const int ng = (int)cfg.geom_res.size();
+    std::vector<bool> pre(ng, false);
+    for (int gi = 0; gi < ng; ++gi) {
+        const int gres = cfg.geom_res[gi], gch = cfg.geom_ch[gi];
+        const int ip = cfg.layer_index(fmt("synthesis.b%d.conv1", gres)), ic = cfg.layer_index(fmt("synthesis.b%d.conv0", 2 * gres));
+        const GenLayer &sp = specs[ip], &sc = specs[ic];
+        const int ofmt = g->operand_fmt(&sc);
+        if (!(g->h3(sp, n) && g->h3_up2(sc, n) && sp.out_ch % 8 == 0 && (ofmt == 0 || (sp.out_ch % 16 == 0 && gch % 16 == 0))))
+            continue;
+        if (sink.sizing) g->need_pre[gi] = std::max(g->need_pre[gi], h2_bytes(n, sc.in_ch, gres * gres));
+        const int c_prod = sc.in_ch - gch;
+        GEN_TRY((ofmt ? nb_pack_h2f8_part_f32 : nb_pack_h2_part_f32)(in->geom[gi], gch, g->L[ic].styles + c_prod, sc.in_ch, g->pre_h2[gi],
+                                                                     (sc.in_ch + 7) / 8, c_prod / 8, n, gres * gres, st));
+        pre[gi] = true;
+    }
+
+    // ---- the layers (_run_layers / _run_layer / _finish_block) ----
+    const float* x = g->const_rep;                    // fp32 NCHW input of the next layer (NULL: handed over in operand format)
+    int xc = cfg.channels(4);
+    const float* x2 = nullptr;                        // geometry feature still to be concatenated
+    int x2c = 0;
+    void* xh2 = nullptr;                              // the next layer's complete operand-format input, when its producer wrote it
+    bool fused_rgb = false;
+    float* uvs = out->uvs ? out->uvs : g->uvs_ws;
+    float* img = out->img ? out->img : g->img_ws;
+    float* colors = out->colors ? out->colors : g->colors_ws;
+    const int c_last = cfg.channels(R);
+    int geo_idx = 0;
+    auto other_act = [&](const float* cur) { return cur == g->act[0] ? g->act[1] : g->act[0]; };
+    auto other_h2 = [&](const void* cur) { return cur == g->h2[0] ? g->h2[1] : g->h2[0]; };
+    for (int i = 0; i < nL; ++i) {
+        const GenLayer& s = specs[i];
+        const GenLayerDev& d = g->L[i];
+        const int res = s.block_res, ir = s.in_res();
+        const int c2 = x2c;                           // (not the pointer: the sizing and describe walks carry none)
+        const int c1 = x ? xc : s.in_ch - c2;
+        if (c1 + c2 != s.in_ch) {
+            nb_set_error("generator: %s got %d+%d input channels, expected %d", s.name.c_str(), c1, c2, s.in_ch);
+            return NB_EINVAL;
+        }
+        NbNoiseSrc nsrc{};
+        const float* noise = nullptr;
+        int64_t nstride = 0;
+        if (cnoise && inkernel_from >= 0 && i >= inkernel_from) {
+            nsrc = NbNoiseSrc{d.noise_const_t, d.noise_lin, d.noise_strength, npos_k, npos_k ? nullptr : ipos, res, R};
+            noise = (const float*)&nsrc;
+            nstride = NB_NOISE_IN_KERNEL;
+        } else if (cnoise) {
+            noise = d.noise;
+            nstride = shared ? 0 : (int64_t)res * res;
+        }
+        const GenLayer* nxt = i + 1 < nL ? &specs[i + 1] : nullptr;
+        const bool at_block_end = s.up == 1, is_last = res == R;
+        const bool tapped = at_block_end && is_last;
+        const bool me_h3 = g->large(s, n);
+        const bool nxt_h3 = nxt && g->large(*nxt, n);
+        const int in_fmt = g->operand_fmt(&s), out_fmt = nxt_h3 ? g->operand_fmt(nxt) : 0;
+        const int gi_after = at_block_end ? cfg.geom_index(res) : -1;
+        const int geo_after = gi_after < 0 ? 0 : cfg.geom_ch[gi_after];
+        const bool fuse_out = me_h3 && nxt_h3 && !tapped && s.out_ch % 8 == 0
+            && (out_fmt == 0 || (s.out_ch % 16 == 0 && geo_after % 16 == 0));
+        float* y = nullptr;
+        void* next_h2 = nullptr;
+        fused_rgb = false;
+        std::string kname;
+        if (me_h3) {
+            if (!xh2) {                                 // producer was not a split-f16 kernel: (x ++ geometry) * styles -> operands
+                xh2 = g->h2[0];
+                if (sink.sizing) g->need_h2 = std::max(g->need_h2, h2_bytes(n, s.in_ch, ir * ir));
+                GEN_TRY((in_fmt ? nb_pack_h2f8_f32 : nb_pack_h2_f32)(x, c1, x2, c2, d.styles, xh2, n, ir * ir, st));
+            }
+            const void* wts = in_fmt ? d.w_f8 : d.w_h3;
+            const bool fuse_rgb = is_last && s.up == 1 && s.out_ch <= 128;
+            NbTorgbArgs targs{};
+            if (fuse_rgb) {
+                targs = NbTorgbArgs{g->trgb_styles, g->trgb_w, g->trgb_b, g->trgb_cb, nullptr, uvs, img, colors, in->user_colors,
+                                    in->sfactor, out->rgba, out->rgba_u8, s.out_ch + 9, in->render_mode, clamp};
+            } else if (fuse_out) {
+                if (at_block_end && gi_after >= 0 && pre[gi_after]) {
+                    next_h2 = g->pre_h2[gi_after];
+                } else {
+                    next_h2 = other_h2(xh2);
+                    if (sink.sizing) g->need_h2 = std::max(g->need_h2, h2_bytes(n, nxt->in_ch, res * res));
+                }
+            } else {
+                y = other_act(x);
+                if (sink.sizing) g->need_act = std::max(g->need_act, (size_t)n * s.out_ch * res * res * sizeof(float));
+            }
+            const float* nst = next_h2 ? g->L[i + 1].styles : nullptr;
+            const int c_next = next_h2 ? nxt->in_ch : 0;
+            if (s.up == 1) {
+                GEN_TRY(nb_modconv3x3_up1_h3_ex(xh2, s.in_ch, wts, d.dcoefs, noise, nstride, d.bias, y, next_h2, nst, c_next, c_next,
+                                                fuse_rgb ? &targs : nullptr, in_fmt, next_h2 ? out_fmt : 0, n, ir, ir, s.out_ch, alpha,
+                                                gain, clamp, st));
+                kname = fmt("modconv3x3_up1_h3_kernel<%d>", s.out_ch > 64 ? 2 : 1);
+            } else {
+                GEN_TRY(nb_modconv3x3_up2_h3_ex(xh2, s.in_ch, wts, d.dcoefs, noise, nstride, d.bias, y, next_h2, nst, c_next, c_next,
+                                                in_fmt, next_h2 ? out_fmt : 0, n, ir, ir, s.out_ch, alpha, gain, clamp, st));
+                if (sink.describe) {
+                    const int rc = nb_modconv3x3_up2_h3_variant(in_fmt, s.in_ch, s.out_ch, n, ir, ir, vbuf, sizeof(vbuf));
+                    if (rc) return rc;
+                    kname = vbuf;
+                }
+            }
+            fused_rgb = fuse_rgb;
+        } else {
+            y = other_act(x);
+            if (sink.sizing) g->need_act = std::max(g->need_act, (size_t)n * s.out_ch * res * res * sizeof(float));
+            if (g->small_h3(s) && c2 == 0 && x) {
+                GEN_TRY(nb_modconv3x3_up1_small_h3(x, c1, d.w_h3, d.styles, d.dcoefs, noise, nstride, d.bias, y, n, ir, ir, s.out_ch,
+                                                   alpha, gain, clamp, st));
+                kname = "modconv3x3_up1_small_h3_kernel";
+            } else if (g->small_h3_up2(s, d) && c1 % 16 == 0 && c2 % 16 == 0 && x) {
+                GEN_TRY(nb_modconv3x3_up2_small_h3(x, c1, x2, c2, d.w_h3_up2, d.styles, d.dcoefs, noise, nstride, d.bias, y, n, ir, ir,
+                                                   s.out_ch, alpha, gain, clamp, st));
+                kname = "modconv3x3_up1_small_h3_kernel";
+            } else {
+                GEN_TRY(nb_modconv3x3_f32(x, c1, x2, c2, d.wpk, d.styles, d.dcoefs, noise, nstride, d.bias, y, n, ir, ir, s.out_ch, s.up,
+                                          alpha, gain, clamp, st));
+                if (sink.describe) {
+                    const int rc = nb_modconv3x3_variant(n, ir, ir, s.out_ch, s.up, vbuf, sizeof(vbuf));
+                    if (rc) return rc;
+                    kname = vbuf;
+                }
+            }
+        }
+        if (sink.describe) *sink.describe += s.name + "=" + kname + "\n";
+        xh2 = next_h2;
+        x = y;
+        xc = s.out_ch;
+        x2 = nullptr;
+        x2c = 0;
+        if (s.up == 2) continue;
+        // ---- what follows a block's last layer ----
+        if (is_last && !fused_rgb)
+            GEN_TRY(nb_torgb_triad_f32(x, g->trgb_styles, c_last + 9, g->trgb_w, g->trgb_b, g->trgb_cb, clamp, nullptr, uvs, img, colors,
+                                       in->user_colors, in->sfactor, in->render_mode, out->rgba, out->rgba_u8, n, c_last, R * R, st));
+        if (gi_after < 0) continue;
+        const float* gf = in->geom[geo_idx];
+        const int gch = cfg.geom_ch[geo_idx];
+        if (xh2 && pre[geo_idx] && xh2 == g->pre_h2[geo_idx]) {
+            // packed at the start of the pass
+        } else if (xh2) {
+            // the block's last layer wrote its channels into the consumer's operands: the geometry channels go behind them
+            const int inext = cfg.layer_index(fmt("synthesis.b%d.conv0", 2 * res));
+            const GenLayer& sn = specs[inext];
+            const int c_prod = sn.in_ch - gch;
+            GEN_TRY((g->operand_fmt(&sn) ? nb_pack_h2f8_part_f32 : nb_pack_h2_part_f32)(gf, gch, g->L[inext].styles + c_prod, sn.in_ch, xh2,
+                                                                                       (sn.in_ch + 7) / 8, c_prod / 8, n, res * res, st));
+        } else {
+            x2 = gf;
+            x2c = gch;
+        }
+        ++geo_idx;
+    }
+    return NB_OK;
+}
+
+#undef GEN_TRY
+
+void gen_free(NbGenerator* g) {
+    if (!g) return;
+    int prev = 0;
+    const bool have = hipGetDevice(&prev) == hipSuccess;
+    if (!g->allocs.empty() && hipSetDevice(g->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        for (void* p : g->allocs) (void)hipFree(p);
+    }
+    if (have) (void)hipSetDevice(prev);
+    delete g;
+}
+
+}  // namespace
+
+extern "C" int nb_generator_destroy(NbGenerator* gen) {
+    gen_free(gen);
+    return NB_OK;
+}
+
+extern "C" int nb_generator_create(const NbGeneratorConfig* cfg, const void* const* params_dev, int conv_mode, int n_max, void* stream,
+                                   NbGenerator** out) {
+    NB_REQUIRE(out, "generator_create: null output handle");
+    *out = nullptr;
+    GenCfg gc;
+    int rc = resolve_cfg(cfg, gc);
+    if (rc) return rc;
+    if (conv_mode == NB_CONV_F6 || conv_mode == NB_CONV_F16) {
+        nb_set_error("generator_create: conv_mode %d (f6 / f16) is not supported by the C entry (f32, h3, f8 are)", conv_mode);
+        return NB_EUNSUPPORTED;
+    }
+    if (conv_mode != NB_CONV_F32 && conv_mode != NB_CONV_H3 && conv_mode != NB_CONV_F8) {
+        nb_set_error("generator_create: unknown conv_mode %d", conv_mode);
+        return NB_EUNSUPPORTED;
+    }
+    NB_REQUIRE(n_max >= 1 && n_max <= 65535, "generator_create: n_max must be in [1, 65535]");
+    NB_REQUIRE(params_dev, "generator_create: null parameter array");
+    for (size_t i = 0; i < gc.params.size(); ++i)
+        NB_REQUIRE(params_dev[i], "generator_create: parameter %d (%s) is NULL", (int)i, gc.params[i].name.c_str());
+
+    NbGenerator* g = new NbGenerator();
+    g->cfg = gc;
+    g->mode = conv_mode;
+    g->n_max = n_max;
+    g->act_gain = (float)std::sqrt(2.0);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipGetDevice(&g->device) != hipSuccess) {
+        delete g;
+        nb_set_error("generator_create: no HIP device");
+        return NB_ELAUNCH;
+    }
+    const GenCfg& C = g->cfg;
+    const int nL = (int)C.layers.size(), w_dim = C.c.w_dim;
+    bool ok = true;
+    auto alloc = [&](size_t bytes) -> void* {
+        void* p = nullptr;
+        if (!ok || bytes == 0) return nullptr;
+        if (hipMalloc(&p, (bytes + 255) / 256 * 256) != hipSuccess) {
+            ok = false;
+            nb_set_error("generator_create: hipMalloc of %zu bytes failed", bytes);
+            return nullptr;
+        }
+        g->allocs.push_back(p);
+        return p;
+    };
+    auto launched = [&]() -> int {
+        NB_CHECK_LAUNCH("generator_create");
+        return NB_OK;
+    };
+    auto fail = [&](int code) {
+        gen_free(g);
+        return code;
+    };
+    // the caller's parameters, copied (they may be freed after this call)
+    std::vector<const float*> P(C.params.size());
+    for (size_t i = 0; i < C.params.size(); ++i) {
+        const size_t bytes = (size_t)C.params[i].numel() * sizeof(float);
+        float* p = (float*)alloc(bytes);
+        if (!ok) return fail(NB_ELAUNCH);
+        if (hipMemcpyAsync(p, params_dev[i], bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            nb_set_error("generator_create: copy of parameter %s failed", C.params[i].name.c_str());
+            return fail(NB_ELAUNCH);
+        }
+        P[i] = p;
+    }
+    int pi = 0;
+    // mapping: the FC weights / biases concatenated (MappingNetwork._pack)
+    {
+        size_t wn = 0;
+        for (int i = 0; i < C.c.mapping_layers; ++i) wn += (size_t)C.params[2 * i].numel();
+        float* mw = (float*)alloc(wn * sizeof(float));
+        float* mb = (float*)alloc((size_t)C.c.mapping_layers * w_dim * sizeof(float));
+        if (!ok) return fail(NB_ELAUNCH);
+        size_t off = 0;
+        for (int i = 0; i < C.c.mapping_layers; ++i) {
+            const size_t k = (size_t)C.params[2 * i].numel();
+            bool copied = hipMemcpyAsync(mw + off, P[2 * i], k * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
+            copied = copied && hipMemcpyAsync(mb + (size_t)i * w_dim, P[2 * i + 1], w_dim * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
+            if (!copied) {
+                nb_set_error("generator_create: copy of the mapping weights failed");
+                return fail(NB_ELAUNCH);
+            }
+            off += k;
+        }
+        g->map_w = mw;
+        g->map_b = mb;
+        pi = 2 * C.c.mapping_layers;
+    }
+    g->w_avg = P[pi++];
+    const float* b4_const = P[pi++];
+    pi += (int)C.blocks.size();                        // the blocks' resample filters (the layers carry their own)
+    const int c4 = C.channels(4);
+    g->const_rep = (float*)alloc((size_t)n_max * c4 * 16 * sizeof(float));
+    if (!ok) return fail(NB_ELAUNCH);
+    hipLaunchKernelGGL(gen_repeat_kernel, dim3(nb_cdiv(n_max * c4 * 16, 256)), dim3(256), 0, st, b4_const, c4 * 16, n_max, g->const_rep);
+    if ((rc = launched())) return fail(rc);
+    const bool split = conv_mode == NB_CONV_H3 || conv_mode == NB_CONV_F8;
+    const bool has_clamp = C.c.conv_clamp >= 0.f;
+    g->L.resize(nL);
+    g->styles_fast = w_dim % 16 == 0;
+    for (int i = 0; i < nL; ++i) {
+        const GenLayer& s = C.layers[i];
+        GenLayerDev& d = g->L[i];
+        g->styles_fast = g->styles_fast && s.out_ch % 4 == 0;
+        d.weight = P[pi++]; d.noise_strength = P[pi++]; d.bias = P[pi++]; d.noise_grid = P[pi++]; d.filter = P[pi++];
+        d.noise_const = P[pi++]; d.affine_w = P[pi++]; d.affine_b = P[pi++];
+        const int r = s.block_res;
+        d.wpk = (float*)alloc((size_t)(s.in_ch + 7) / 8 * 8 * 9 * ((s.out_ch + 31) / 32 * 32) * sizeof(float));
+        d.wsq = (float*)alloc((size_t)s.in_ch * s.out_ch * sizeof(float));
+        d.noise_lin = (float*)alloc((size_t)r * sizeof(float));
+        d.noise_const_t = (float*)alloc((size_t)r * r * sizeof(float));
+        d.styles = (float*)alloc((size_t)n_max * s.in_ch * sizeof(float));
+        d.dcoefs = (float*)alloc((size_t)n_max * s.out_ch * sizeof(float));
+        d.noise = (float*)alloc((size_t)n_max * r * r * sizeof(float));
+        const size_t h3_bytes = (size_t)(s.in_ch + 15) / 16 * 9 * 4 * ((s.out_ch + 63) / 64 * 64) * 8 * sizeof(_Float16);
+        if (split && has_clamp) {
+            d.w_h3 = alloc(h3_bytes);
+            if (conv_mode == NB_CONV_F8 && s.in_ch % 16 == 0) d.w_f8 = alloc(h3_bytes);
+            if (s.up == 2 && s.in_res() <= 32 && s.in_ch % 16 == 0) d.w_h3_up2 = alloc(4 * h3_bytes);
+        }
+        if (!ok) return fail(NB_ELAUNCH);
+        if ((rc = nb_pack_conv_weight_dev(d.weight, s.out_ch, s.in_ch, d.wpk, d.wsq, st))) return fail(rc);
+        if (d.w_h3 && (rc = nb_pack_conv_weight_h3_dev(d.weight, s.out_ch, s.in_ch, 64, 0, d.w_h3, st))) return fail(rc);
+        if (d.w_f8 && (rc = nb_pack_conv_weight_h3f8_dev(d.weight, s.out_ch, s.in_ch, d.w_f8, st))) return fail(rc);
+        if (d.w_h3_up2 && (rc = nb_pack_conv_weight_h3_up2_dev(d.weight, d.filter, s.out_ch, s.in_ch, d.w_h3_up2, st))) return fail(rc);
+        hipLaunchKernelGGL(gen_gather_kernel, dim3(nb_cdiv(r, 256)), dim3(256), 0, st, d.noise_grid, 2 * r, r, d.noise_lin);
+        hipLaunchKernelGGL(gen_transpose_kernel, dim3(nb_cdiv(r * r, 256)), dim3(256), 0, st, d.noise_const, r, d.noise_const_t);
+        if ((rc = launched())) return fail(rc);
+    }
+    g->trgb_w = P[pi++]; g->trgb_b = P[pi++]; g->trgb_cb = P[pi++]; g->trgb_aw = P[pi++]; g->trgb_ab = P[pi++];
+    const int c_last = C.channels(C.R);
+    g->trgb_styles = (float*)alloc((size_t)n_max * (c_last + 9) * sizeof(float));
+    // layer tables (_Plan): the full one and, for the fused styles + noise launch of small batches, one per first in-kernel-noise layer
+    std::vector<NbLayerDesc> descs((size_t)(nL + 1) * (nL + 1));
+    for (int first = 0; first <= nL; ++first) {
+        NbLayerDesc* t = descs.data() + (size_t)first * (nL + 1);
+        for (int i = 0; i < nL; ++i) {
+            const GenLayer& s = C.layers[i];
+            const GenLayerDev& d = g->L[i];
+            t[i] = NbLayerDesc{d.affine_w, d.affine_b, d.wsq, d.styles, d.dcoefs, i >= first ? nullptr : d.noise_const, d.noise_lin, d.noise,
+                               d.noise_strength, s.in_ch, 0, s.out_ch, s.w_index, s.block_res, 1.f, {0, 0}};
+        }
+        t[nL] = NbLayerDesc{g->trgb_aw, g->trgb_ab, nullptr, g->trgb_styles, nullptr, nullptr, nullptr, nullptr, nullptr, c_last + 9, 9, 3,
+                            nL, 0, (float)(1.0 / std::sqrt((double)c_last)), {0, 0}};
+    }
+    g->tables = (NbLayerDesc*)alloc(descs.size() * sizeof(NbLayerDesc));
+    g->ws_buf = (float*)alloc((size_t)n_max * C.num_ws * w_dim * sizeof(float));
+    g->npos = (float*)alloc((size_t)n_max * 2 * sizeof(float));
+    g->uvs_ws = (float*)alloc((size_t)n_max * 3 * C.R * C.R * sizeof(float));
+    g->img_ws = (float*)alloc((size_t)n_max * 3 * C.R * C.R * sizeof(float));
+    g->colors_ws = (float*)alloc((size_t)n_max * 9 * sizeof(float));
+    if (!ok) return fail(NB_ELAUNCH);
+    if (hipMemcpyAsync(g->tables, descs.data(), descs.size() * sizeof(NbLayerDesc), hipMemcpyHostToDevice, st) != hipSuccess) {
+        nb_set_error("generator_create: upload of the layer tables failed");
+        return fail(NB_ELAUNCH);
+    }
+    // workspaces: the largest each buffer gets at any batch size up to n_max (decisions change with the batch)
+    {
+        static char sentinel[8];
+        g->act[0] = (float*)&sentinel[0]; g->act[1] = (float*)&sentinel[2];
+        g->h2[0] = &sentinel[4]; g->h2[1] = &sentinel[6];
+        g->pre_h2.assign(C.geom_res.size(), nullptr);
+        g->need_pre.assign(C.geom_res.size(), 0);
+        for (size_t k = 0; k < C.geom_res.size(); ++k) g->pre_h2[k] = &sentinel[1];
+        NbGeneratorInputs din{};
+        din.z = (const float*)&sentinel[3];
+        din.positions = (const int64_t*)&sentinel[5];
+        din.truncation_psi = 1.f;
+        NbGeneratorOutputs dout{};
+        WalkSink sink;
+        sink.sizing = true;
+        for (int n = 1; n <= n_max; ++n)
+            if ((rc = gen_walk(g, &din, &dout, n, st, sink))) return fail(rc);
+        g->act[0] = (float*)alloc(g->need_act); g->act[1] = (float*)alloc(g->need_act);
+        g->h2[0] = alloc(g->need_h2); g->h2[1] = alloc(g->need_h2);
+        for (size_t k = 0; k < C.geom_res.size(); ++k) g->pre_h2[k] = alloc(g->need_pre[k]);
+        if (!ok) return fail(NB_ELAUNCH);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) {
+        nb_set_error("generator_create: %s", hipGetErrorString(hipGetLastError()));
+        return fail(NB_ELAUNCH);
+    }
+    *out = g;
+    return NB_OK;
+}
+
+extern "C" int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, void* stream) {
+    NB_REQUIRE(gen && in && out, "generator_forward: null pointer");
+    NB_REQUIRE(n >= 1 && n <= gen->n_max, "generator_forward: batch %d outside [1, n_max = %d]", n, gen->n_max);
+    NB_REQUIRE((in->z != nullptr) != (in->ws != nullptr), "generator_forward: pass exactly one of z / ws");
+    NB_REQUIRE(in->truncation_psi == 1.f || in->z, "generator_forward: truncation applies to z input only (ws input needs psi = 1)");
+    for (size_t k = 0; k < gen->cfg.geom_res.size(); ++k) NB_REQUIRE(in->geom[k], "generator_forward: geometry feature %d is NULL", (int)k);
+    if (in->noise_mode != NB_NOISE_CONST && in->noise_mode != NB_NOISE_NONE) {
+        nb_set_error("generator_forward: noise_mode %d not supported (const and none are)", in->noise_mode);
+        return in->noise_mode == NB_NOISE_RANDOM ? NB_EUNSUPPORTED : NB_EINVAL;
+    }
+    NB_REQUIRE(in->render_mode == NB_RENDER_CLEAR || in->render_mode == NB_RENDER_FULL, "generator_forward: unknown render_mode %d", in->render_mode);
+    int dev = -1;
+    NB_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev == gen->device, "generator_forward: current device %d is not the generator's (%d)", dev,
+               gen->device);
+    if (stream) {
+        hipDevice_t sdev = -1;
+        NB_REQUIRE(hipStreamGetDevice((hipStream_t)stream, &sdev) == hipSuccess && sdev == gen->device,
+                   "generator_forward: the stream belongs to device %d, the generator to %d", (int)sdev, gen->device);
+    }
+    WalkSink sink;
+    sink.launch = true;
+    return gen_walk(gen, in, out, n, (hipStream_t)stream, sink);
+}
+
+extern "C" int nb_generator_describe(NbGenerator* gen, int n, char* buf, int len) {
+    NB_REQUIRE(gen && buf && len > 0, "generator_describe: bad arguments");
+    NB_REQUIRE(n >= 1 && n <= gen->n_max, "generator_describe: batch %d outside [1, n_max = %d]", n, gen->n_max);
+    std::string s;
+    NbGeneratorInputs din{};
+    static const float dummy = 0.f;
+    static const int64_t dpos[2] = {0, 0};
+    din.z = &dummy;
+    din.positions = dpos;
+    din.truncation_psi = 1.f;
+    NbGeneratorOutputs dout{};
+    WalkSink sink;
+    sink.describe = &s;
+    const int rc = gen_walk(gen, &din, &dout, n, nullptr, sink);
+    if (rc) return rc;
+    NB_REQUIRE(len > (int)s.size(), "generator_describe: buffer of %d bytes, %d needed", len, (int)s.size() + 1);
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return NB_OK;
+}

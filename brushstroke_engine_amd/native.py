@@ -1,0 +1,226 @@
+"""The generator through its C entry (``nb_generator_*`` of include/neube_hip.h): the path a C or C++ host takes, from Python.
+
+``NativeGenerator`` owns one library-side generator handle: packed weights and workspaces for batches up to ``n_max`` on one
+device.  ``render_triad`` is a thin ctypes call on the current torch stream that enqueues the whole step (mapping, styles, noise,
+every layer, the fused ToRGB + compositing) as one chain of launches; its results equal ``Generator.render_triad``'s bit for bit
+when the Python path runs as one chain too.  The Python ``Generator`` is not involved.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .config import GeneratorConfig, LayerSpec
+
+_p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+
+
+def native_config(cfg: GeneratorConfig) -> "_lib.NbGeneratorConfig":
+    """config.GeneratorConfig -> struct NbGeneratorConfig."""
+    if cfg.c_dim != 0:
+        raise ValueError("c_dim must be 0")
+    if tuple(cfg.resample_filter) != (1, 3, 3, 1):
+        raise ValueError("the C entry takes the [1, 3, 3, 1] resample filter of the shipped configuration")
+    if len(cfg.geom_feature_channels) > 4:
+        raise ValueError("at most 4 geometry features")
+    c = _lib.NbGeneratorConfig()
+    c.z_dim, c.c_dim, c.w_dim, c.img_resolution = cfg.z_dim, cfg.c_dim, cfg.w_dim, cfg.img_resolution
+    c.mapping_layers, c.mapping_lr_multiplier = cfg.mapping_layers, cfg.mapping_lr_multiplier
+    c.channel_base, c.channel_max = cfg.channel_base, cfg.channel_max
+    c.conv_clamp = -1.0 if cfg.conv_clamp is None else float(cfg.conv_clamp)
+    c.num_geom = len(cfg.geom_feature_channels)
+    for k, (ch, res) in enumerate(zip(cfg.geom_feature_channels, cfg.geom_feature_resolutions)):
+        c.geom_channels[k], c.geom_resolutions[k] = ch, res
+    return c
+
+
+def param_table(cfg: GeneratorConfig) -> List[tuple]:
+    """[(state-dict key, shape)] in the order nb_generator_create takes the parameters (weights.random_state_dict's)."""
+    lib, c = _lib.lib(), native_config(cfg)
+    count = lib.nb_generator_param_count(ctypes.byref(c))
+    _lib.check(min(count, 0), "generator_param_count")
+    out, name = [], ctypes.create_string_buffer(256)
+    shape, ndim = (ctypes.c_int64 * 4)(), ctypes.c_int()
+    for i in range(count):
+        _lib.check(lib.nb_generator_param_info(ctypes.byref(c), i, name, 256, shape, ctypes.byref(ndim)), "generator_param_info")
+        out.append((name.value.decode(), tuple(int(shape[k]) for k in range(ndim.value))))
+    return out
+
+
+def layer_table(cfg: GeneratorConfig):
+    """([LayerSpec] in execution order, num_ws) as the library derives them from the configuration."""
+    lib, c = _lib.lib(), native_config(cfg)
+    num_ws = ctypes.c_int()
+    count = lib.nb_generator_layer_count(ctypes.byref(c), ctypes.byref(num_ws))
+    _lib.check(min(count, 0), "generator_layer_count")
+    out, name, info = [], ctypes.create_string_buffer(256), _lib.NbGeneratorLayerInfo()
+    for i in range(count):
+        _lib.check(lib.nb_generator_layer_info(ctypes.byref(c), i, name, 256, ctypes.byref(info)), "generator_layer_info")
+        out.append(LayerSpec(name.value.decode(), info.block_res, info.up, info.in_channels, info.out_channels, info.geom_channels,
+                             info.w_index))
+    return out, num_ws.value
+
+
+class NativeGenerator:
+    """One ``NbGenerator`` handle.  Build it with :meth:`from_state_dict` or :meth:`from_generator`."""
+
+    def __init__(self, cfg: GeneratorConfig, handle: int, conv_mode: str, n_max: int, device: torch.device):
+        self.cfg, self._h, self.conv_mode, self.n_max, self.device = cfg, handle, conv_mode, n_max, device
+        self.img_resolution, self.num_ws = cfg.img_resolution, cfg.num_ws
+
+    @staticmethod
+    def from_state_dict(cfg: GeneratorConfig, sd, conv_mode: str = "f8", n_max: int = 32, device="cuda") -> "NativeGenerator":
+        """sd: state dict (numpy arrays or tensors, the reference's key names).  The parameters are uploaded, handed to
+        nb_generator_create (which copies and packs them) and released."""
+        if conv_mode not in _lib.NB_CONV_MODES:
+            raise ValueError(f"unknown conv_mode {conv_mode!r}")
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        table = param_table(cfg)
+        tensors = []
+        for name, shape in table:
+            v = sd[name]
+            t = v if torch.is_tensor(v) else torch.from_numpy(np.array(v, dtype=np.float32))     # (0-dim stays 0-dim)
+            t = t.detach().to(device=device, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+            tensors.append(t)
+        ptrs = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        c = native_config(cfg)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(_lib.lib().nb_generator_create(ctypes.byref(c), ptrs, _lib.NB_CONV_MODES[conv_mode], n_max, stream,
+                                                      ctypes.byref(h)), "generator_create")
+        return NativeGenerator(cfg, h.value, conv_mode, n_max, device)
+
+    @staticmethod
+    def from_generator(G, n_max: int = 32) -> "NativeGenerator":
+        """The weights and arithmetic mode of a networks.Generator."""
+        dev = G.synthesis.get_last_block().conv1.weight.device
+        return NativeGenerator.from_state_dict(G.cfg, G.state_dict(), G.synthesis.conv_mode, n_max, dev)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().nb_generator_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                    # noqa: BLE001  (interpreter shutdown)
+            pass
+
+    def describe(self, n: int) -> dict:
+        """{layer name: kernel} the forward at batch n launches (the strings SynthesisNetwork.layer_kernels records)."""
+        buf = ctypes.create_string_buffer(8192)
+        _lib.check(_lib.lib().nb_generator_describe(self._h, n, buf, len(buf)), "generator_describe")
+        return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+    # ---- forward ----
+    def _f32(self, t, shape, name):
+        t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
+        if list(t.shape) != list(shape):
+            raise ValueError(f"{name}: expected shape {list(shape)}, got {list(t.shape)}")
+        return t
+
+    def forward_into(self, outputs: dict, n: int, z=None, ws=None, geom_feature: Sequence = (), positions=None, noise_mode="const",
+                     render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0, truncation_cutoff=None):
+        """Enqueue one forward on the current stream into caller-allocated ``outputs`` (keys rgba_u8 / rgba / img / uvs / colors;
+        missing = not wanted).  Inputs must already be device tensors of the right dtype and shape (nothing is converted here):
+        the form for graph capture."""
+        ins = _lib.NbGeneratorInputs()
+        ins.z, ins.ws = _p(z), _p(ws)
+        ins.truncation_psi = float(truncation_psi)
+        ins.truncation_cutoff = -1 if truncation_cutoff is None else int(truncation_cutoff)
+        for k, g in enumerate(geom_feature):
+            ins.geom[k] = _p(g)
+        ins.positions = _p(positions)
+        ins.noise_mode = _lib.NB_NOISE_MODES[noise_mode] if isinstance(noise_mode, str) else int(noise_mode)
+        if render_mode not in _lib.NB_RENDER_MODES:
+            raise RuntimeError(f"Unknown render mode for TriadGanPaintEngine: {render_mode}")
+        ins.render_mode = _lib.NB_RENDER_MODES[render_mode]
+        ins.user_colors, ins.sfactor = _p(user_colors), _p(sfactor)
+        outs = _lib.NbGeneratorOutputs()
+        for k in ("rgba_u8", "rgba", "img", "uvs", "colors"):
+            setattr(outs, k, _p(outputs.get(k)))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(_lib.lib().nb_generator_forward(self._h, ctypes.byref(ins), ctypes.byref(outs), n, stream), "generator_forward")
+
+    def render_triad(self, z=None, ws=None, geom_feature=None, positions=None, render_mode="clear", user_colors=None, want_u8=True,
+                     want_f32=False, sfactor=None, noise_mode="const", truncation_psi=1.0, truncation_cutoff=None):
+        """Generator.render_triad through the C entry: (rgba_u8 [N,R,R,4] | None, rgba [N,4,R,R] | None, {uvs, colors, img})."""
+        cfg, dev = self.cfg, self.device
+        if (z is None) == (ws is None):
+            raise ValueError("pass exactly one of z / ws")
+        n = (z if z is not None else ws).shape[0]
+        z = None if z is None else self._f32(z, [n, cfg.z_dim], "z")
+        ws = None if ws is None else self._f32(ws, [n, cfg.num_ws, cfg.w_dim], "ws")
+        geom_feature = list(geom_feature) if isinstance(geom_feature, (list, tuple)) else [geom_feature]
+        if len(geom_feature) != len(cfg.geom_feature_channels):
+            raise ValueError(f"expected {len(cfg.geom_feature_channels)} geometry features, got {len(geom_feature)}")
+        geom = [self._f32(g, [n, c, r, r], f"geom_feature[{k}]")
+                for k, (g, c, r) in enumerate(zip(geom_feature, cfg.geom_feature_channels, cfg.geom_feature_resolutions))]
+        pos = None
+        if positions is not None:
+            pos = torch.as_tensor(positions, device=dev).to(torch.int64).contiguous()
+            if list(pos.shape) != [n, 2]:
+                raise ValueError(f"positions: expected shape [{n}, 2], got {list(pos.shape)}")
+        user = None if user_colors is None else self._f32(user_colors, [n, 3, 3], "user_colors")
+        sfac = None
+        if sfactor is not None:
+            sfac = torch.as_tensor(sfactor, dtype=torch.float32, device=dev).reshape(-1)
+            sfac = self._f32(sfac.expand(n) if sfac.numel() == 1 else sfac, [n], "sfactor")
+        r = cfg.img_resolution
+        outs = {"uvs": torch.empty([n, 3, r, r], dtype=torch.float32, device=dev),
+                "img": torch.empty([n, 3, r, r], dtype=torch.float32, device=dev),
+                "colors": torch.empty([n, 3, 3], dtype=torch.float32, device=dev)}
+        if want_u8:
+            outs["rgba_u8"] = torch.empty([n, r, r, 4], dtype=torch.uint8, device=dev)
+        if want_f32:
+            outs["rgba"] = torch.empty([n, 4, r, r], dtype=torch.float32, device=dev)
+        self.forward_into(outs, n, z=z, ws=ws, geom_feature=geom, positions=pos, noise_mode=noise_mode, render_mode=render_mode,
+                          user_colors=user, sfactor=sfac, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
+        # the inputs converted here are read by work enqueued on the current stream: keep them alive for it
+        cur = torch.cuda.current_stream(dev)
+        for t in [z, ws, pos, user, sfac] + geom:
+            if t is not None:
+                t.record_stream(cur)
+        return outs.get("rgba_u8"), outs.get("rgba"), {"uvs": outs["uvs"], "colors": outs["colors"], "img": outs["img"]}
+
+
+def pack_weights_dev(weight: torch.Tensor, kind: str, resample_filter: Optional[torch.Tensor] = None):
+    """The device packers on their own (tests, tools): kind 'wpk' -> (wpk, wsq), 'f8' -> the f8 format, 'h3_up2' -> the four phase
+    kernels, 'h3' -> nb_pack_conv_weight_h3_dev with co_align 64."""
+    lib = _lib.lib()
+    o, i = weight.shape[:2]
+    w = weight.detach().to(torch.float32).contiguous()
+    dev = w.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    nch, op64 = (i + 15) // 16, (o + 63) // 64 * 64
+    with torch.cuda.device(dev):
+        if kind == "wpk":
+            wpk = torch.empty([(i + 7) // 8 * 8, 9, (o + 31) // 32 * 32], dtype=torch.float32, device=dev)
+            wsq = torch.empty([i, o], dtype=torch.float32, device=dev)
+            _lib.check(lib.nb_pack_conv_weight_dev(_p(w), o, i, _p(wpk), _p(wsq), stream), "pack_conv_weight_dev")
+            return wpk, wsq
+        if kind == "h3":
+            out = torch.empty([nch, 3, 3, 2, 2, op64, 8], dtype=torch.float16, device=dev)
+            _lib.check(lib.nb_pack_conv_weight_h3_dev(_p(w), o, i, 64, 0, _p(out), stream), "pack_conv_weight_h3_dev")
+            return out
+        if kind == "f8":
+            out = torch.empty([nch, 3, 3, 2, 2, op64, 8], dtype=torch.float16, device=dev)
+            _lib.check(lib.nb_pack_conv_weight_h3f8_dev(_p(w), o, i, _p(out), stream), "pack_conv_weight_h3f8_dev")
+            return out
+        if kind == "h3_up2":
+            f = resample_filter.detach().to(device=dev, dtype=torch.float32).contiguous()
+            out = torch.empty([4, nch, 3, 3, 2, 2, op64, 8], dtype=torch.float16, device=dev)
+            _lib.check(lib.nb_pack_conv_weight_h3_up2_dev(_p(w), _p(f), o, i, _p(out), stream), "pack_conv_weight_h3_up2_dev")
+            return out
+    raise ValueError(f"unknown kind {kind!r}")

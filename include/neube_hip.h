@@ -525,6 +525,106 @@ int nb_enc_upsample2x_h2_ex(const float* x, void* y_h2, int out_fmt, int n, int 
  * wpk[ceil8(c_in)][9][ceil32(c_out)] and wsq[c_in][c_out] = sum_k W^2.  Either output may be NULL. */
 int nb_pack_conv_weight(const float* w, int c_out, int c_in, float* wpk, float* wsq);
 
+/* ---- device weight packers (csrc/nb_generator.hip): the packed forms the generator layers take, built from the fp32 weight
+ * W[c_out,c_in,3,3] on the DEVICE (w and every output are device pointers; enqueue only).  Bit for bit what the package's torch
+ * packers (ops.py) produce. */
+
+/* wpk [ceil8(c_in)][9][ceil32(c_out)] zero padded (nb_modconv3x3_f32) and wsq [c_in][c_out] = sum_k W[o,i,k]^2, summed in the
+ * order torch's reduction kernel uses on this platform for 9 contiguous elements: ((s0 + s8 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)).
+ * Either output may be NULL. */
+int nb_pack_conv_weight_dev(const float* w, int c_out, int c_in, float* wpk, float* wsq, void* stream);
+/* The "f8" weight format (nb_pack_conv_weight_h3's container, lo slots in fp8 e4m3; see the f8 section above). */
+int nb_pack_conv_weight_h3f8_dev(const float* w, int c_out, int c_in, void* out, void* stream);
+/* The four up=2 phase kernels of nb_modconv3x3_up2_small_h3 (W folded with the 4x4 resample filter f [4,4], the fold summed in
+ * float64 and rounded to fp32), each in the nb_pack_conv_weight_h3 format, back to back. */
+int nb_pack_conv_weight_h3_up2_dev(const float* w, const float* resample_filter, int c_out, int c_in, void* out, void* stream);
+
+/* ---- the whole generator behind one handle (csrc/nb_generator.hip) -------------------------------------------------------
+ * For C / C++ hosts: create a generator from its fp32 weights once, then enqueue whole forward passes (mapping, styles, noise,
+ * every synthesis layer, the fused ToRGB + compositing) with one call.  The per-batch kernel choices are those of the package's
+ * Python pass (SynthesisNetwork) at the same batch size, and so are the results, bit for bit.
+ *
+ * Exceptions to the header's rules: nb_generator_create allocates device memory and synchronises its stream before it returns,
+ * nb_generator_destroy frees (after a device synchronisation).  nb_generator_forward only enqueues, on one stream and as one
+ * chain of launches: after one eager call at a batch size (it sets per-kernel attributes the first time) it can be captured into
+ * a hipGraph.  One handle runs one forward at a time (the workspaces belong to the handle): for concurrent forwards create one
+ * handle per stream.  The query functions (param / layer tables) make no HIP call and work without a GPU. */
+
+typedef struct NbGeneratorConfig {   /* config.GeneratorConfig */
+    int32_t z_dim, c_dim, w_dim;      /* c_dim must be 0; z_dim, w_dim <= 512 */
+    int32_t img_resolution;           /* power of two >= 4 */
+    int32_t mapping_layers;
+    float   mapping_lr_multiplier;
+    int32_t channel_base, channel_max;
+    float   conv_clamp;               /* < 0 = None */
+    int32_t num_geom;                 /* geometry features, 0..4 */
+    int32_t geom_channels[4];
+    int32_t geom_resolutions[4];      /* all 0 = the default (R/8, R/4), which needs num_geom == 2 */
+} NbGeneratorConfig;
+
+typedef struct NbGeneratorLayerInfo { /* config.LayerSpec */
+    int32_t block_res, up, in_channels, out_channels, geom_channels, w_index;
+} NbGeneratorLayerInfo;
+
+#define NB_CONV_F32 0                 /* conv_mode: "f32", "h3", "f8" (the parity modes); "f6", "f16" -> NB_EUNSUPPORTED */
+#define NB_CONV_H3  1
+#define NB_CONV_F8  2
+#define NB_CONV_F6  3
+#define NB_CONV_F16 4
+#define NB_NOISE_CONST  0             /* noise_mode */
+#define NB_NOISE_NONE   1
+#define NB_NOISE_RANDOM 2             /* -> NB_EUNSUPPORTED */
+#define NB_RENDER_CLEAR 0             /* render_mode: alpha = u + v / 1 (nb_torgb_triad_f32) */
+#define NB_RENDER_FULL  1
+
+typedef struct NbGenerator NbGenerator;
+
+/* Parameters = the state-dict tensors in the order of weights.random_state_dict: count, then name / shape of entry i
+ * (ndim 0 = a scalar; shape[] entries beyond ndim are 0). */
+int nb_generator_param_count(const NbGeneratorConfig* cfg);
+int nb_generator_param_info(const NbGeneratorConfig* cfg, int i, char* name, int len, int64_t shape[4], int* ndim);
+/* Layers = config.GeneratorConfig.layers in execution order (returns their count; *num_ws may be NULL). */
+int nb_generator_layer_count(const NbGeneratorConfig* cfg, int* num_ws);
+int nb_generator_layer_info(const NbGeneratorConfig* cfg, int i, char* name, int len, NbGeneratorLayerInfo* info);
+
+/* params_dev[i]: device fp32 tensor of parameter i (contiguous, shapes as nb_generator_param_info).  Copies and packs what the
+ * forward needs, allocates every workspace for batches up to n_max and synchronises `stream`: the caller may free params_dev
+ * afterwards.  The current device is the generator's device. */
+int nb_generator_create(const NbGeneratorConfig* cfg, const void* const* params_dev, int conv_mode, int n_max, void* stream,
+                        NbGenerator** out);
+int nb_generator_destroy(NbGenerator* gen);
+
+typedef struct NbGeneratorInputs {
+    const float* z;                   /* [n, z_dim], or NULL with ws given */
+    const float* ws;                  /* [n, num_ws, w_dim], or NULL with z given (exactly one of the two) */
+    float truncation_psi;             /* z only: ws[:, :cutoff] = w_avg + psi (ws - w_avg); 1 = off (ws input: must be 1) */
+    int32_t truncation_cutoff;        /* < 0 = every ws */
+    const float* geom[4];             /* geometry features [n, geom_channels[k], res_k, res_k] fp32, one per feature */
+    const int64_t* positions;         /* [n, 2] (y, x) patch positions, or NULL (no positional noise shift) */
+    int32_t noise_mode;               /* NB_NOISE_CONST / NB_NOISE_NONE */
+    int32_t render_mode;              /* NB_RENDER_CLEAR / NB_RENDER_FULL */
+    const float* user_colors;         /* [n, 3, 3] or NULL; NaN entries = the style's own colour */
+    const float* sfactor;             /* [n] or NULL */
+} NbGeneratorInputs;
+
+typedef struct NbGeneratorOutputs {   /* device pointers; NULL = not wanted */
+    uint8_t* rgba_u8;                 /* [n, R, R, 4] */
+    float* rgba;                      /* [n, 4, R, R] */
+    float* img;                       /* [n, 3, R, R] */
+    float* uvs;                       /* [n, 3, R, R] */
+    float* colors;                    /* [n, 3, 3] */
+} NbGeneratorOutputs;
+
+/* One forward pass of batch n <= n_max on `stream` (enqueue only; no allocation, no synchronisation, no blocking copy).
+ * n out of range, another current device than the generator's, a missing z / ws / geometry feature: NB_EINVAL, nothing
+ * enqueued.  noise_mode random: NB_EUNSUPPORTED.  Device pointers of the inputs and outputs must stay valid until the work
+ * has run. */
+int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, void* stream);
+
+/* The kernel every layer's launch will run at batch n: "layer name=kernel name" lines (the strings SynthesisNetwork.layer_kernels
+ * records).  Host only. */
+int nb_generator_describe(NbGenerator* gen, int n, char* buf, int len);
+
 /* ---- box calibration (csrc/nb_calib.hip; measurement infrastructure, not on the generator's path) -----------------
  * A registers-only loop of back-to-back v_mfma_f32_32x32x16_f16 on random operands, one wave per SIMD on every CU of the current
  * device, for about target_ms (blocking).  *tflops = the dense f16 matrix rate this device sustains, *ms = duration of the measured
