@@ -554,12 +554,16 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         fused_rgb = false;
         std::string kname;
         if (me_h3) {
+            const void* wts = in_fmt ? d.w_f8 : d.w_h3;
+            if (!wts) {                                 // (at creation the sizing walk stops here: nb_generator_create fails)
+                nb_set_error("generator: %s has no packed weights for operand format %d", s.name.c_str(), in_fmt);
+                return NB_EINVAL;
+            }
             if (!xh2) {                                 // producer was not a split-f16 kernel: (x ++ geometry) * styles -> operands
                 xh2 = g->h2[0];
                 if (sink.sizing) g->need_h2 = std::max(g->need_h2, h2_bytes(n, s.in_ch, ir * ir));
                 GEN_TRY((in_fmt ? nb_pack_h2f8_f32 : nb_pack_h2_f32)(x, c1, x2, c2, d.styles, xh2, n, ir * ir, st));
             }
-            const void* wts = in_fmt ? d.w_f8 : d.w_h3;
             const bool fuse_rgb = is_last && s.up == 1 && s.out_ch <= 128;
             NbTorgbArgs targs{};
             if (fuse_rgb) {
@@ -614,7 +618,10 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
                 }
             }
         }
-        if (sink.describe) *sink.describe += s.name + "=" + kname + "\n";
+        if (sink.describe) {
+            *sink.describe += s.name + "=" + kname + "\n";
+            if (fused_rgb) *sink.describe += fmt("synthesis.b%d.torgb=", R) + kname + "\n";       // (in the last conv's epilogue)
+        }
         xh2 = next_h2;
         x = y;
         xc = s.out_ch;
@@ -622,9 +629,11 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         x2c = 0;
         if (s.up == 2) continue;
         // ---- what follows a block's last layer ----
-        if (is_last && !fused_rgb)
+        if (is_last && !fused_rgb) {
             GEN_TRY(nb_torgb_triad_f32(x, g->trgb_styles, c_last + 9, g->trgb_w, g->trgb_b, g->trgb_cb, clamp, nullptr, uvs, img, colors,
                                        in->user_colors, in->sfactor, in->render_mode, out->rgba, out->rgba_u8, n, c_last, R * R, st));
+            if (sink.describe) *sink.describe += fmt("synthesis.b%d.torgb=torgb_triad_kernel\n", R);
+        }
         if (gi_after < 0) continue;
         const float* gf = in->geom[geo_idx];
         const int gch = cfg.geom_ch[geo_idx];

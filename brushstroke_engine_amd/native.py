@@ -117,7 +117,8 @@ class NativeGenerator:
             pass
 
     def describe(self, n: int) -> dict:
-        """{layer name: kernel} the forward at batch n launches (the strings SynthesisNetwork.layer_kernels records)."""
+        """{layer name: kernel} the forward at batch n launches (the strings SynthesisNetwork.layer_kernels records; the ToRGB's
+        entry is the last conv's kernel when fused into it)."""
         buf = ctypes.create_string_buffer(8192)
         _lib.check(_lib.lib().nb_generator_describe(self._h, n, buf, len(buf)), "generator_describe")
         return dict(line.split("=", 1) for line in buf.value.decode().splitlines())

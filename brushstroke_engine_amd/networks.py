@@ -364,7 +364,7 @@ class SynthesisNetwork(torch.nn.Module):
         self.fuse_torgb = True            # last conv1 + ToRGB + compositing in one launch (split-f16 path)
         self.noise_in_kernel = True       # large split-f16 layers compute their (position-shifted) noise themselves
         self.positions_once = True        # ... from positions normalised ONCE per batch (nb_norm_positions_f32) instead of per tile (batches > 8)
-        self.layer_kernels: Dict[str, str] = {}
+        self.layer_kernels: Dict[str, str] = {}      # layer name -> kernel; the ToRGB's entry names the last conv's kernel when fused
         self.layer_formats: Dict[str, int] = {}      # operand format each split-f16 layer last ran with (0 H2, 1 f8, 2 f6)
 
     # -- helpers --
@@ -849,6 +849,8 @@ class SynthesisNetwork(torch.nn.Module):
             self.layer_formats[name] = in_fmt
             self.layer_kernels[name] = ("modconv3x3_up1_h3_kernel<%d>" % (2 if s.out_channels > 64 else 1)
                                         if s.up == 1 else self._up2_h3_variant_name(in_fmt, n, s))
+            if fuse_rgb:
+                self.layer_kernels[cfg.torgb_name] = self.layer_kernels[name]        # (ToRGB in the last conv's epilogue)
             ps.keep_alive.append(x_h2)
             self._end_event(ev)
         elif self._small_h3_eligible(s) and c2 == 0 and x is not None:
@@ -1000,6 +1002,7 @@ class SynthesisNetwork(torch.nn.Module):
             o["clamp"], _p(o["logits"]), _p(o["uvs"]), _p(o["img"]), _p(o["colors"]), _p(o["user"]), _p(o["sfac"]),
             o["mode"], _p(o["rgba"]), _p(o["rgba8"]), n, c, r * r, stream), "torgb_triad")
         self._end_event(ev)
+        self.layer_kernels[self.cfg.torgb_name] = "torgb_triad_kernel"
         return self._torgb_finish(o, extra)
 
 

@@ -622,7 +622,7 @@ typedef struct NbGeneratorOutputs {   /* device pointers; NULL = not wanted */
 int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, void* stream);
 
 /* The kernel every layer's launch will run at batch n: "layer name=kernel name" lines (the strings SynthesisNetwork.layer_kernels
- * records).  Host only. */
+ * records), the ToRGB's line included: the last conv's kernel when it is fused there, else torgb_triad_kernel.  Host only. */
 int nb_generator_describe(NbGenerator* gen, int n, char* buf, int len);
 
 /* ---- box calibration (csrc/nb_calib.hip; measurement infrastructure, not on the generator's path) -----------------

@@ -208,19 +208,24 @@ def shifted_const_noise(noise_const, noise_grid, norm_positions):
     only out-of-range corner is ``floor+1 == r`` with weight 0.  grid[...,0] (= lin[i] + pos[:,0]) is the
     *column* coordinate and grid[...,1] (= lin[j] + pos[:,1]) the *row*, hence the transposition.
     ``tests/test_oracle_golden.py`` checks this against ``F.grid_sample`` itself.
+
+    The sample coordinates are float32 in every oracle dtype, as in the reference: ``% 1`` and ``floor`` are discontinuous, and in
+    float64 a sample next to a wrap or a cell edge lands on another cell (often the far side of the image).  Only the
+    interpolation runs in the oracle's dtype.
     """
     r = noise_const.shape[0]
     dt = noise_const.dtype
-    g = (noise_grid.to(dt) + norm_positions.to(dt).unsqueeze(1).unsqueeze(1)) % 1      # [N,r,r,2]
+    f32 = torch.float32
+    g = (noise_grid.to(f32) + norm_positions.to(f32).unsqueeze(1).unsqueeze(1)) % 1      # [N,r,r,2]
     g = g * 2 - 1
     cx = ((g[..., 0] + 1) / 2) * (r - 1)      # column coordinate
     cy = ((g[..., 1] + 1) / 2) * (r - 1)      # row coordinate
     x0 = torch.floor(cx)
     y0 = torch.floor(cy)
-    wx1 = cx - x0
-    wy1 = cy - y0
-    wx0 = (x0 + 1) - cx
-    wy0 = (y0 + 1) - cy
+    wx1 = (cx - x0).to(dt)                    # (exact in float32: the weights are the reference's in any dtype)
+    wy1 = (cy - y0).to(dt)
+    wx0 = ((x0 + 1) - cx).to(dt)
+    wy0 = ((y0 + 1) - cy).to(dt)
     x0i = x0.long()
     y0i = y0.long()
     x1i = x0i + 1
@@ -362,10 +367,8 @@ class OracleGenerator:
         norm_positions = None
         if positions is not None:
             positions = torch.as_tensor(np.asarray(positions)).to(torch.int64)
-            if self.dtype == torch.float64:
-                norm_positions = (positions % self.img_resolution).to(torch.float64) / (self.img_resolution - 1)
-            else:
-                norm_positions = (positions % self.img_resolution) / (self.img_resolution - 1)   # float32 true division
+            # float32 true division in every oracle dtype (the noise coordinates are float32 arithmetic: shifted_const_noise)
+            norm_positions = (positions % self.img_resolution) / (self.img_resolution - 1)
         res = self.synthesis(ws, geom_feature, return_debug_data=return_debug_data, return_features=return_features,
                              blended_features=blended_features, noise_buffers=noise_buffers,
                              norm_noise_positions=norm_positions, **kw)

@@ -1,7 +1,9 @@
 """Child process of tests/test_hip_capi.py: one group of checks of the C generator entry (nb_generator_*) on the GPU.
 
-    python tests/_capi_worker.py packers
+    python tests/_capi_worker.py packers                # device packers == torch packers (style1, tests/_gen_configs.py, ragged shapes)
     python tests/_capi_worker.py python <mode> <R>      # NativeGenerator == Generator.render_triad, describe == layer_kernels, errors
+    python tests/_capi_worker.py matrix <config> <mode> # the same at every batch threshold for a tests/_gen_configs.py net + its rows
+    python tests/_capi_worker.py oracle <config>        # the C entry against the float64 oracle, all modes
     python tests/_capi_worker.py golden <mode>          # the C entry against the reference's golden vectors
     python tests/_capi_worker.py graph <mode> <R>       # captured C forward == eager C forward
     python tests/_capi_worker.py chost <exe> <workdir>  # examples/capi/generate.c == NativeGenerator
@@ -47,25 +49,79 @@ def inputs(cfg, n, seed):
             D(synthetic.positions(cfg, n, seed=seed)))
 
 
+# (c_out, c_in) beside the nets' own layers: single channels, c_in not a multiple of 8 or 16, partial 64-channel c_out slices
+PACK_SHAPES = ((1, 1), (3, 5), (21, 105), (100, 121), (72, 112), (160, 416), (64, 40))
+
+
+def check_packers(w, what, f=None):
+    """Every device packer == its torch packer for one weight; h3_up2 only when f is given.  Returns the wsq ulp difference."""
+    wpk, wsq = ops.pack_conv_weight(w)
+    dpk, dsq = pack_weights_dev(w, "wpk")
+    check(torch.equal(wpk, dpk), f"{what} wpk")
+    check(torch.equal(ops.pack_conv_weight_h3(w).view(torch.int16), pack_weights_dev(w, "h3").view(torch.int16)), f"{what} w_h3")
+    check(torch.equal(ops.pack_conv_weight_h3f8(w).view(torch.int16), pack_weights_dev(w, "f8").view(torch.int16)), f"{what} w_f8")
+    if f is not None:
+        want = ops.pack_conv_weight_h3_up2_phases(w, f)
+        check(torch.equal(want.view(torch.int16), pack_weights_dev(w, "h3_up2", f).view(torch.int16)), f"{what} w_h3_up2")
+    return ulps(wsq, dsq)
+
+
 def packers():
-    for res in (128, 256):
-        cfg = cfgmod.style1_config(res)
+    from _gen_configs import CONFIGS
+    nets = [(f"R={res}", cfgmod.style1_config(res), True) for res in (128, 256)]
+    nets += [(cid, cfg, False) for cid, (cfg, _) in CONFIGS.items()]
+    filt = None
+    for label, cfg, every_up2 in nets:
         sd = wmod.random_state_dict(cfg, seed=3)
         worst_wsq = 0
         for s in cfg.layers:
-            w = D(sd[f"{s.name}.weight"])
-            wpk, wsq = ops.pack_conv_weight(w)
-            dpk, dsq = pack_weights_dev(w, "wpk")
-            check(torch.equal(wpk, dpk), f"R={res} {s.name} wpk")
-            worst_wsq = max(worst_wsq, ulps(wsq, dsq))
-            check(torch.equal(ops.pack_conv_weight_h3(w).view(torch.int16), pack_weights_dev(w, "h3").view(torch.int16)), f"R={res} {s.name} w_h3")
-            check(torch.equal(ops.pack_conv_weight_h3f8(w).view(torch.int16), pack_weights_dev(w, "f8").view(torch.int16)), f"R={res} {s.name} w_f8")
-            if s.up == 2:
-                f = D(sd[f"{s.name}.resample_filter"])
-                want = ops.pack_conv_weight_h3_up2_phases(w, f)
-                check(torch.equal(want.view(torch.int16), pack_weights_dev(w, "h3_up2", f).view(torch.int16)), f"R={res} {s.name} w_h3_up2")
-        print(f"[capi] R={res} wsq max ulp difference to torch: {worst_wsq}", flush=True)
-        check(worst_wsq == 0, f"R={res} wsq bitwise")
+            f = D(sd[f"{s.name}.resample_filter"])
+            filt = f
+            # the phase kernels as nb_generator_create packs them (up=2, input <= 32x32, whole 16-channel chunks); style1: every up=2 layer
+            up2 = s.up == 2 and (every_up2 or (s.in_res <= 32 and s.in_channels % 16 == 0))
+            worst_wsq = max(worst_wsq, check_packers(D(sd[f"{s.name}.weight"]), f"{label} {s.name}", f if up2 else None))
+        print(f"[capi] {label} wsq max ulp difference to torch: {worst_wsq}", flush=True)
+        check(worst_wsq == 0, f"{label} wsq bitwise")
+    rs = np.random.RandomState(17)
+    worst_wsq = 0
+    for co, ci in PACK_SHAPES:
+        w = D((rs.randn(co, ci, 3, 3) * rs.choice([1e-3, 1.0, 30.0], size=(co, ci, 1, 1))).astype(np.float32))
+        worst_wsq = max(worst_wsq, check_packers(w, f"[{co}, {ci}, 3, 3]", filt if ci % 16 == 0 else None))
+    print(f"[capi] ragged shapes wsq max ulp difference to torch: {worst_wsq}", flush=True)
+    check(worst_wsq == 0, "ragged shapes wsq bitwise")
+
+
+def python_pass(G, geom, kw, nkw):
+    """Generator.render_triad as one chain -> ((u8, rgba, uvs, colors, img), layer_kernels, layer_formats); img comes from a second
+    pass over the same inputs (render_triad does not return it)."""
+    u8, rgba, dbg = G.render_triad(geom_feature=geom, want_f32=True, **kw, **nkw)
+    kernels, formats = dict(G.synthesis.layer_kernels), dict(G.synthesis.layer_formats)
+    xkw = {k: v for k, v in kw.items() if k not in ("z", "ws")}
+    extra = {"rgba_u8": False, "rgba": False, "render_mode": xkw.pop("render_mode", "clear"), "user_colors": xkw.pop("user_colors", None),
+             "sfactor": xkw.pop("sfactor", None)}
+    if "z" in kw:
+        img, _ = G(kw["z"], None, geom, return_debug_data=True, _extra_outputs=extra, noise_mode=nkw.get("noise_mode", "const"), **xkw)
+    else:
+        img, _ = G.forward_pre_mapped(kw["ws"], geom, return_debug_data=True, _extra_outputs=extra,
+                                      noise_mode=nkw.get("noise_mode", "const"), **xkw)
+    return (u8, rgba, dbg["uvs"], dbg["colors"], img), kernels, formats
+
+
+def c_pass(ng, geom, kw, nkw):
+    cu8, crgba, cdbg = ng.render_triad(geom_feature=geom, want_f32=True, **kw, **nkw)
+    return cu8, crgba, cdbg["uvs"], cdbg["colors"], cdbg["img"]
+
+
+def check_bitwise(py, c, what):
+    eq = lambda a, b: a is None and b is None or (a is not None and b is not None and torch.equal(a, b))   # noqa: E731
+    torch.cuda.synchronize()
+    same = all(eq(a, b) for a, b in zip(py, c))
+    if not same:
+        (u8, rgba, uvs, colors, img), (cu8, crgba, cuvs, ccolors, cimg) = py, c
+        print(f"  u8 {int((u8.int() - cu8.int()).abs().max())} rgba {float((rgba - crgba).abs().max()):.3e} "
+              f"uvs {float((uvs - cuvs).abs().max()):.3e} colors {float((colors - ccolors).abs().max()):.3e} "
+              f"img {float((img - cimg).abs().max()):.3e}", flush=True)
+    check(same, f"{what}: bitwise equal to Generator.render_triad")
 
 
 def python_vs_c(mode, res):
@@ -74,7 +130,6 @@ def python_vs_c(mode, res):
     G = Generator(cfg, sd, conv_mode=mode).to(DEV)
     G.sub_stream_min_batch = 10 ** 9                         # the Python pass as one chain too
     ng = NativeGenerator.from_generator(G, n_max=max(BATCHES))
-    eq = lambda a, b: a is None and b is None or (a is not None and b is not None and torch.equal(a, b))   # noqa: E731
     for n in BATCHES:
         z, geom, pos = inputs(cfg, n, 100 + n)
         rs = np.random.RandomState(n)
@@ -89,25 +144,8 @@ def python_vs_c(mode, res):
                  ("scalar sfactor", dict(z=z, positions=pos, sfactor=0.8), {}),
                  ("ws input", dict(ws=ws, positions=pos), {})]
         for name, kw, nkw in cases:
-            u8, rgba, dbg = G.render_triad(geom_feature=geom, want_f32=True, **kw, **nkw)
-            kernels = dict(G.synthesis.layer_kernels)
-            xkw = {k: v for k, v in kw.items() if k not in ("z", "ws")}
-            extra = {"rgba_u8": False, "rgba": False, "render_mode": xkw.pop("render_mode", "clear"), "user_colors": xkw.pop("user_colors", None),
-                     "sfactor": xkw.pop("sfactor", None)}
-            if "z" in kw:
-                img, _ = G(kw["z"], None, geom, return_debug_data=True, _extra_outputs=extra, noise_mode=nkw.get("noise_mode", "const"), **xkw)
-            else:
-                img, _ = G.forward_pre_mapped(kw["ws"], geom, return_debug_data=True, _extra_outputs=extra,
-                                              noise_mode=nkw.get("noise_mode", "const"), **xkw)
-            cu8, crgba, cdbg = ng.render_triad(geom_feature=geom, want_f32=True, **kw, **nkw)
-            torch.cuda.synchronize()
-            same = all(eq(a, b) for a, b in ((u8, cu8), (rgba, crgba), (dbg["uvs"], cdbg["uvs"]), (dbg["colors"], cdbg["colors"]),
-                                             (img, cdbg["img"])))
-            if not same:
-                print(f"  u8 {int((u8.int() - cu8.int()).abs().max())} rgba {float((rgba - crgba).abs().max()):.3e} "
-                      f"uvs {float((dbg['uvs'] - cdbg['uvs']).abs().max()):.3e} colors {float((dbg['colors'] - cdbg['colors']).abs().max()):.3e} "
-                      f"img {float((img - cdbg['img']).abs().max()):.3e}", flush=True)
-            check(same, f"{mode} R={res} n={n} {name}: bitwise equal to Generator.render_triad")
+            py, kernels, _ = python_pass(G, geom, kw, nkw)
+            check_bitwise(py, c_pass(ng, geom, kw, nkw), f"{mode} R={res} n={n} {name}")
         desc = ng.describe(n)
         check(desc == kernels, f"{mode} R={res} n={n} describe == layer_kernels")
         # truncation: torch's lerp bits are not guaranteed -> within the mode's pixel tolerance
@@ -135,6 +173,66 @@ def python_vs_c(mode, res):
     ng.close()
 
 
+def matrix(cid, mode):
+    """A tests/_gen_configs.py net through the C entry and the Python pass at every batch of BATCHES: the kernel plan first (nothing
+    is enqueued through the C entry before its plan matches), then bitwise equality, then the decision rows the net exists for."""
+    from _gen_configs import BATCHES as NS, CONFIGS, expected_rows, rows_reached
+    cfg = CONFIGS[cid][0]
+    G = Generator(cfg, wmod.random_state_dict(cfg, seed=5), conv_mode=mode).to(DEV)
+    G.sub_stream_min_batch = 10 ** 9
+    ng = NativeGenerator.from_generator(G, n_max=max(NS))
+    reached = set()
+    for n in NS:
+        z, geom, pos = inputs(cfg, n, 200 + n)
+        ws = G.mapping(z, None)
+        for k, (name, kw) in enumerate((("z+positions", dict(z=z, positions=pos)), ("ws input", dict(ws=ws, positions=pos)))):
+            py, kernels, formats = python_pass(G, geom, kw, {})
+            if k == 0:
+                desc = ng.describe(n)
+                if desc != kernels:
+                    for key in sorted(set(desc) | set(kernels)):
+                        if desc.get(key) != kernels.get(key):
+                            print(f"  {key}: C {desc.get(key)}, Python {kernels.get(key)}", flush=True)
+                check(desc == kernels, f"{cid} {mode} n={n} describe == layer_kernels")
+                rows = rows_reached(cfg, mode, kernels, formats)
+                reached |= rows
+                print(f"[capi rows] {cid} {mode} n={n}: {' '.join(sorted(rows)) or '-'}", flush=True)
+            check_bitwise(py, c_pass(ng, geom, kw, {}), f"{cid} {mode} n={n} {name}")
+    missing = expected_rows(cid, mode) - reached
+    check(not missing, f"{cid} {mode} reaches its rows {sorted(expected_rows(cid, mode))} (missing: {sorted(missing)})")
+    ng.close()
+
+
+def oracle_batch(cfg, sd, n=32):
+    """One float64 CPU oracle pass on a batch of n (constant noise, positions): (z, geom, positions, oracle debug dict)."""
+    from oracle import neube_oracle as orc
+    z, geom, pos = synthetic.batch_z(cfg, n, 300), synthetic.geom_features(cfg, n, seed=30), synthetic.positions(cfg, n, seed=30)
+    img, want = orc.OracleGenerator(cfg, sd, dtype=torch.float64)(z, None, geom, positions=pos, return_debug_data=True,
+                                                                  return_features=[cfg.img_resolution // 2])
+    want["img"] = img
+    return z, geom, pos, want
+
+
+def oracle(cid):
+    """The C entry of a tests/_gen_configs.py net against the float64 oracle, in every mode, at n = 32 and on the first 1 / 9 / 16
+    samples of the same batch."""
+    from _gen_configs import CONFIGS
+    cfg = CONFIGS[cid][0]
+    sd = wmod.random_state_dict(cfg, seed=6)
+    z, geom, pos, want = oracle_batch(cfg, sd)
+    for mode in ("f32", "h3", "f8"):
+        ng = NativeGenerator.from_state_dict(cfg, sd, mode, 32, DEV)
+        worst = {"uvs": 0.0, "img": 0.0, "colors": 0.0}
+        for n in (32, 1, 9, 16):
+            _, _, dbg = ng.render_triad(z=D(z[:n]), geom_feature=[D(g[:n]) for g in geom], positions=D(pos[:n]))
+            e = {k: float((dbg[k].cpu().double() - want[k][:n]).abs().max()) for k in worst}
+            worst = {k: max(worst[k], e[k]) for k in worst}
+            check(e["uvs"] <= PIX[mode] and e["img"] <= PIX[mode] and e["colors"] <= 1e-5,
+                  f"{cid} {mode} n={n} vs float64 oracle: uvs {e['uvs']:.2e} img {e['img']:.2e} colors {e['colors']:.2e}")
+        print(f"[capi oracle] {cid} {mode} max error: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()), flush=True)
+        ng.close()
+
+
 def golden(mode):
     sys.path.insert(0, os.path.join(REPO, "tests"))
     from conftest import load_golden
@@ -152,6 +250,40 @@ def golden(mode):
         print(f"[capi golden R={res} {mode}] colors {e_c:.2e} uvs {e_u:.2e} img {e_i:.2e} uvs.row {e_r:.2e}", flush=True)
         check(e_c <= 1e-5 and max(e_u, e_i, e_r) <= PIX[mode], f"gen_r{res} {mode}")
         ng.close()
+    # tiny net (R=32, the small-image kernels): the cases of gen_tiny.npz whose inputs the C entry takes (A: z + positions, B: no positions)
+    g = load_golden("gen_tiny.npz")
+    cfg = cfgmod.tiny_config(32)
+    ng = NativeGenerator.from_state_dict(cfg, wmod.random_state_dict(cfg, seed=int(g["weights_seed"])), mode, 3, DEV)
+    geom = [D(x) for x in synthetic.geom_features(cfg, 3, seed=int(g["geom_seed"]))]
+    _, _, a = ng.render_triad(z=D(g["z"]), geom_feature=geom, positions=D(g["positions"]))
+    _, _, b = ng.render_triad(z=D(g["z"]), geom_feature=geom)
+    e = {"A colors": float(np.abs(a["colors"].cpu().numpy() - g["A_colors"]).max()),
+         "A uvs": float(np.abs(a["uvs"].cpu().numpy() - g["A_uvs"]).max()), "A img": float(np.abs(a["img"].cpu().numpy() - g["A_img"]).max()),
+         "B img": float(np.abs(b["img"].cpu().numpy() - g["B_img"]).max())}
+    print(f"[capi golden tiny {mode}] " + " ".join(f"{k} {v:.2e}" for k, v in e.items()), flush=True)
+    check(e["A colors"] <= 1e-5 and max(e["A uvs"], e["A img"], e["B img"]) <= PIX[mode], f"gen_tiny {mode}")
+    ng.close()
+    # ten layers at the conv_clamp (the bounds of test_hip_generator.py::test_high_dynamic_range_fixture)
+    g = load_golden("gen_hdr_r128.npz")
+    cfg = cfgmod.style1_config(128)
+    ng = NativeGenerator.from_state_dict(cfg, wmod.hdr_state_dict(cfg, seed=int(g["weights_seed"])), mode, 2, DEV)
+    geom = [D(x) for x in synthetic.geom_features(cfg, 2, seed=int(g["geom_seed"]))]
+    _, _, dbg = ng.render_triad(z=D(g["z"]), geom_feature=geom, positions=D(g["positions"]))
+    e = {k: float(np.abs(dbg[k].cpu().numpy() - g[k]).max()) for k in ("colors", "uvs", "img")}
+    print(f"[capi golden hdr {mode}] " + " ".join(f"{k} {v:.2e}" for k, v in e.items()), flush=True)
+    check(e["colors"] <= 1e-5 and e["uvs"] <= 1e-3 and e["img"] <= 1e-3, f"gen_hdr_r128 {mode}")
+    ng.close()
+    # trained-like weight statistics (the colors / uvs / img bounds of test_hip_generator.py::test_trained_like_fixture)
+    g = load_golden("gen_trained_r128.npz")
+    ng = NativeGenerator.from_state_dict(cfg, wmod.trained_like_state_dict(cfg, seed=int(g["weights_seed"])), mode, 6, DEV)
+    geom = [D(x) for x in synthetic.geom_features(cfg, 6, seed=int(g["geom_seed"]))]
+    _, _, dbg = ng.render_triad(z=D(g["z"]), geom_feature=geom, positions=D(g["positions"]))
+    e = {"colors": float(np.abs(dbg["colors"].cpu().numpy() - g["colors"]).max()),
+         "uvs": float(np.abs(dbg["uvs"].cpu().numpy() - g["uvs"]).max()),
+         "img.sub": float(np.abs(dbg["img"].cpu().numpy()[..., ::2, ::2] - g["img.sub"]).max())}
+    print(f"[capi golden trained {mode}] " + " ".join(f"{k} {v:.2e}" for k, v in e.items()), flush=True)
+    check(e["colors"] <= 1e-5 and e["uvs"] <= PIX[mode] and e["img.sub"] <= PIX[mode], f"gen_trained_r128 {mode}")
+    ng.close()
     g = load_golden("gen_b32_r256.npz")
     cfg = cfgmod.style1_config(256)
     n = 32
@@ -243,10 +375,15 @@ def chost(exe, work):
 if __name__ == "__main__":
     case = sys.argv[1]
     torch.cuda.set_device(0)
+    torch.set_num_threads(min(16, torch.get_num_threads()))        # (the CPU oracle)
     if case == "packers":
         packers()
     elif case == "python":
         python_vs_c(sys.argv[2], int(sys.argv[3]))
+    elif case == "matrix":
+        matrix(sys.argv[2], sys.argv[3])
+    elif case == "oracle":
+        oracle(sys.argv[2])
     elif case == "golden":
         golden(sys.argv[2])
     elif case == "graph":

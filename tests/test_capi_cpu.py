@@ -8,6 +8,8 @@ import pytest
 
 from brushstroke_engine_amd import _lib, build, config as cfgmod, weights as wmod
 from brushstroke_engine_amd.native import layer_table, native_config, param_table
+from brushstroke_engine_amd.networks import Generator
+from _gen_configs import ALL, CONFIGS as GEN_CONFIGS, ROWS
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -30,6 +32,26 @@ def test_param_and_layer_tables(library, cfg):
     assert [s for _, s in table] == [tuple(v.shape) for v in sd.values()]    # shapes (0-dim noise_strength included)
     layers, num_ws = layer_table(cfg)
     assert layers == cfg.layers and num_ws == cfg.num_ws
+
+
+@pytest.mark.parametrize("cid", list(GEN_CONFIGS))
+def test_gen_config_tables_and_python_generator(library, cid):
+    """The nets the GPU tests run through both paths (tests/_gen_configs.py: ragged channels, no conv_clamp, w_dim 40, zero, one and
+    three geometry features at explicit resolutions): the C entry derives the Python tables, and the Python Generator takes each
+    configuration the C entry takes."""
+    cfg, rows = GEN_CONFIGS[cid]
+    assert rows and set(rows) <= set(ROWS) and all(set(m) <= set(ALL) for m in rows.values())
+    sd = wmod.random_state_dict(cfg, 0)
+    table = param_table(cfg)
+    assert [k for k, _ in table] == list(sd.keys())
+    assert [s for _, s in table] == [tuple(v.shape) for v in sd.values()]
+    layers, num_ws = layer_table(cfg)
+    assert layers == cfg.layers and num_ws == cfg.num_ws
+    c = native_config(cfg)
+    assert c.num_geom == len(cfg.geom_feature_channels) and list(c.geom_resolutions[:c.num_geom]) == list(cfg.geom_feature_resolutions)
+    G = Generator(cfg, sd)
+    assert sorted(G.state_dict().keys()) == sorted(sd.keys())
+    assert G.synthesis.geom_feature_resolutions == list(cfg.geom_feature_resolutions)
 
 
 def _cfg(**kw):

@@ -1,11 +1,14 @@
 """GPU checks of the C generator entry (nb_generator_*, include/neube_hip.h): device weight packers, the kernel plan, bitwise
-equality with the Python pass, the reference's golden vectors, graph capture and a C host program.  Every check runs in a child
+equality with the Python pass (also at every batch threshold of the nets in tests/_gen_configs.py), the float64 oracle, the reference's
+golden vectors, graph capture and a C host program.  Every check runs in a child
 process (tests/_capi_worker.py) under a time limit."""
 import os
 import subprocess
 import sys
 
 import pytest
+
+from _gen_configs import CONFIGS
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,6 +30,19 @@ def test_device_packers_match_torch():
 @pytest.mark.parametrize("mode", ["f32", "h3", "f8"])
 def test_native_equals_python_and_describe(mode, res):
     run_worker("python", mode, res, timeout=900)
+
+
+@pytest.mark.parametrize("mode", ["f32", "h3", "f8"])
+@pytest.mark.parametrize("cid", list(CONFIGS))
+def test_native_equals_python_at_batch_thresholds(cid, mode):
+    """Ragged channels, no conv_clamp, w_dim % 16 != 0, other geometry layouts: describe == layer_kernels and bitwise equal outputs
+    at n = 1, 3, 8, 9, 15, 16, 32, and the decision rows the net exists for are reached."""
+    run_worker("matrix", cid, mode)
+
+
+@pytest.mark.parametrize("cid", list(CONFIGS))
+def test_native_against_float64_oracle(cid):
+    run_worker("oracle", cid)
 
 
 @pytest.mark.parametrize("mode", ["f32", "h3", "f8"])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gen_configs import CONFIGS as GEN_CONFIGS
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -237,6 +238,35 @@ def test_odd_channel_counts_vs_oracle(res, cmax, cbase, geom):
                    return_debug_data=True, return_features=[res // 2], noise_mode="const")
         assert float((got["uvs"].cpu() - want["uvs"]).abs().max()) <= tol, mode
         assert float((got[f"features{res // 2}"].cpu() - want[f"features{res // 2}"]).abs().max()) <= 5 * tol, mode
+
+
+@pytest.mark.parametrize("cid", list(GEN_CONFIGS))
+def test_gen_configs_vs_float64_oracle(dev, cid):
+    """The nets of tests/_gen_configs.py (ragged channels on the large split-f16 kernels, refused hand-offs and early packs, no
+    conv_clamp, w_dim % 16 != 0, other geometry layouts) at full batch against ONE float64 oracle pass: n = 32 and the first 1 / 9 / 16
+    samples, every mode; the features at R/2 from a pass that taps them."""
+    from brushstroke_engine_amd import weights as wmod, synthetic
+    from brushstroke_engine_amd.networks import Generator
+    from oracle import neube_oracle as orc
+    cfg = GEN_CONFIGS[cid][0]
+    half = cfg.img_resolution // 2
+    sd = wmod.random_state_dict(cfg, seed=6)
+    z, gf, pos = synthetic.batch_z(cfg, 32, 300), synthetic.geom_features(cfg, 32, seed=30), synthetic.positions(cfg, 32, seed=30)
+    want_img, want = orc.OracleGenerator(cfg, sd, dtype=torch.float64)(z, None, gf, positions=pos, return_debug_data=True,
+                                                                       return_features=[half])
+    for mode in MODES:
+        G = Generator(cfg, sd, conv_mode=mode).to(dev)
+        worst = {}
+        for n in (32, 1, 9, 16):
+            args = (D(z[:n], dev), None, [D(g[:n], dev) for g in gf])
+            img, dbg = G(*args, positions=D(pos[:n], dev), return_debug_data=True, noise_mode="const")
+            _, tap = G(*args, positions=D(pos[:n], dev), return_debug_data=True, return_features=[half], noise_mode="const")
+            e = {"uvs": err(dbg["uvs"], want["uvs"][:n]), "img": err(img, want_img[:n]), "colors": err(dbg["colors"], want["colors"][:n]),
+                 "tapped uvs": err(tap["uvs"], want["uvs"][:n]), f"features{half}": err(tap[f"features{half}"], want[f"features{half}"][:n])}
+            worst = {k: max(worst.get(k, 0.0), v) for k, v in e.items()}
+            assert max(e["uvs"], e["img"], e["tapped uvs"]) <= PIX[mode] and e["colors"] <= 1e-5, (cid, mode, n, e)
+            assert e[f"features{half}"] <= ACT[mode], (cid, mode, n, e)
+        print(f"[gen configs vs float64 {cid} {mode}] " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()))
 
 
 def test_baseline_size_properties(dev):
