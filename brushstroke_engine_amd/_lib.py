@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lock = threading.Lock()
 _lib = None
@@ -131,6 +131,9 @@ PROTOTYPES = {
     "nb_generator_destroy": (C.c_int, [vp]),
     "nb_generator_forward": (C.c_int, [vp, vp, vp, C.c_int, vp]),
     "nb_generator_describe": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
+    # the per-batch layer plan (host only)
+    "nb_plan_options_default": (C.c_int, [vp]),
+    "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
 }
 
 
@@ -179,6 +182,37 @@ class NbGeneratorInputs(C.Structure):
 class NbGeneratorOutputs(C.Structure):
     """``struct NbGeneratorOutputs``."""
     _fields_ = [("rgba_u8", vp), ("rgba", vp), ("img", vp), ("uvs", vp), ("colors", vp)]
+
+
+NB_PLAN_MAX_LAYERS = 24
+NB_PLAN_POS_NONE, NB_PLAN_POS_INT, NB_PLAN_POS_NORM = 0, 1, 2
+NB_KERNEL_F32, NB_KERNEL_SMALL_H3, NB_KERNEL_LARGE_H3 = 0, 1, 2
+NB_PACK_H3, NB_PACK_F8, NB_PACK_F6, NB_PACK_H3_UP2 = 1, 2, 4, 8
+
+
+class NbPlanOptions(C.Structure):
+    """``struct NbPlanOptions`` of include/neube_hip.h."""
+    KNOBS = ("h3_min_pixels", "h3_min_batch", "h3_up2_w16_min_batch", "h3_up2_w8_min_batch", "small_h3", "h2_handoff",
+             "early_geom_pack", "fuse_torgb", "noise_in_kernel", "positions_once", "styles_fast")
+    _fields_ = [(k, C.c_int32) for k in ("conv_mode",) + KNOBS + ("noise_positions", "noise_overrides", "tap_mask", "blend_mask",
+                                                                  "resume_res")]
+
+
+class NbLayerPlan(C.Structure):
+    """``struct NbLayerPlan``."""
+    _fields_ = [("kernel", C.c_char * 64)] + [(k, C.c_int32) for k in ("kind", "in_fmt", "kernel_fmt", "out_fmt", "handoff",
+                                                                       "fused_torgb", "noise_in_kernel", "packs")]
+
+
+class NbGeomPlan(C.Structure):
+    """``struct NbGeomPlan``."""
+    _fields_ = [(k, C.c_int32) for k in ("consumer", "early_pack", "encoder_handoff", "fmt")]
+
+
+class NbPassPlan(C.Structure):
+    """``struct NbPassPlan``."""
+    _fields_ = [(k, C.c_int32) for k in ("num_layers", "num_geom", "inkernel_from", "styles_fast", "styles_noise", "positions_once")] + [
+        ("layers", NbLayerPlan * NB_PLAN_MAX_LAYERS), ("geom", NbGeomPlan * 4)]
 
 
 NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3

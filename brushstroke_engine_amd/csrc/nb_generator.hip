@@ -2,11 +2,10 @@
 // layer tables of a GeneratorConfig, and the host orchestration of one forward pass -- the launches and per-batch kernel choices of
 // SynthesisNetwork._run_layers (networks.py) on one stream, without torch.
 //
-// The orchestration is a single walk (gen_walk) used three ways: to size the workspaces at creation (every batch up to n_max), to
-// name the kernels a batch will run (nb_generator_describe) and to enqueue a forward pass.  Its decisions are ported from
-// SynthesisNetwork (_h3_eligible and friends, the styles / noise path, positions_once, in-kernel noise, the operand hand-off and the
-// early geometry pack) with the constructor's defaults; what differs is only that the early geometry pack runs in-line on the one
-// stream instead of on a side stream (same kernel, same inputs: same bits).
+// The per-batch kernel decisions of a pass live in one place, the planner (nb_synthesis_plan): SynthesisNetwork and the walk below
+// both follow its plan.  The orchestration is a single walk (gen_walk) used two ways: to size the workspaces at creation (every
+// batch up to n_max) and to enqueue a forward pass.  It differs from SynthesisNetwork only in that the early geometry pack runs
+// in-line on the one stream instead of on a side stream (same kernel, same inputs: same bits).
 #include "nb_h3_common.h"
 #include <cmath>
 #include <cstring>
@@ -215,11 +214,6 @@ struct GenCfg {
             if (geom_res[k] == res) return (int)k;
         return -1;
     }
-    int layer_index(const std::string& name) const {
-        for (size_t k = 0; k < layers.size(); ++k)
-            if (layers[k].name == name) return (int)k;
-        return -1;
-    }
 };
 
 std::string fmt(const char* f, int a) {
@@ -314,7 +308,158 @@ int copy_name(const std::string& s, char* buf, int len) {
     return NB_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the per-batch layer plan (nb_synthesis_plan): every kernel decision of SynthesisNetwork's pass and of gen_walk
+// ------------------------------------------------------------------------------------------------
+
+int plan_pass(const GenCfg& g, const NbPlanOptions& o, int n, NbPassPlan* p) {
+    NB_REQUIRE(p, "synthesis_plan: null output");
+    NB_REQUIRE(n >= 1 && n <= 65535, "synthesis_plan: batch %d outside [1, 65535]", n);
+    NB_REQUIRE(o.conv_mode >= NB_CONV_F32 && o.conv_mode <= NB_CONV_F16, "synthesis_plan: unknown conv_mode %d", o.conv_mode);
+    NB_REQUIRE(o.noise_positions >= NB_PLAN_POS_NONE && o.noise_positions <= NB_PLAN_POS_NORM, "synthesis_plan: bad noise_positions %d",
+               o.noise_positions);
+    const int nL = (int)g.layers.size(), ng = (int)g.geom_res.size(), mode = o.conv_mode;
+    NB_REQUIRE(nL <= NB_PLAN_MAX_LAYERS && ng <= 4, "synthesis_plan: %d layers, at most %d", nL, NB_PLAN_MAX_LAYERS);
+    memset(p, 0, sizeof(*p));
+    p->num_layers = nL;
+    p->num_geom = ng;
+    const bool split = mode != NB_CONV_F32;                                   // large layers on the split-f16 kernel family
+    const bool f8 = mode == NB_CONV_F8 || mode == NB_CONV_F6 || mode == NB_CONV_F16;      // ... f8 operands where c_in allows
+    const bool has_clamp = g.c.conv_clamp >= 0.f;
+    const bool clamp_ok = has_clamp && g.c.conv_clamp <= 1024.f;             // activations bounded inside the f16 range
+    auto bit = [](int mask, int res) { return (mask >> __builtin_ctz(res)) & 1; };
+
+    // the large split-f16 kernels: up=1 needs rows of 32 pixels; up=2 inputs of 32k pixel rows, or 16 / 8 (8 x 16 / 8 x 8 quad
+    // tiles: few workgroups per sample, so only from a batch); both enough output pixels to fill the chip with large workgroups
+    auto large = [&](const GenLayer& s) {
+        if (!split || !clamp_ok || n < o.h3_min_batch) return false;
+        const bool px = (long long)n * s.block_res * s.block_res >= o.h3_min_pixels;
+        if (s.up == 1) return s.block_res >= 32 && s.block_res % 32 == 0 && px;
+        const int ir = s.in_res();
+        const bool w8 = ir == 8 && n >= o.h3_up2_w8_min_batch;
+        return ((ir >= 32 && ir % 32 == 0) || (ir == 16 && n >= o.h3_up2_w16_min_batch) || w8) && (w8 || px);
+    };
+    // operand format of a large layer's input: 1 = f8 (whole 16-channel chunks only), 0 = H2; 2 = f6 in conv_mode f6 for the up=2
+    // launches on the software-pipelined up2v kernel (their producers, an up=1 kernel or the geometry pack, write it; the up=2
+    // epilogue does not, so the up=1 layers behind an up=2 layer stay on f8)
+    int rc = NB_OK;
+    auto operand_fmt = [&](const GenLayer& s) {
+        if (!f8 || s.in_ch % 16) return 0;
+        if (mode == NB_CONV_F6 && s.up == 2 && s.in_res() % 32 == 0) {
+            char v[64];
+            const int r = nb_modconv3x3_up2_h3_variant(2, s.in_ch, s.out_ch, n, s.in_res(), s.in_res(), v, sizeof(v));
+            if (r) rc = r;
+            if (!r && strcmp(v, "modconv3x3_up2v_kernel") == 0) return 2;
+        }
+        return 1;
+    };
+
+    // ---- the pass ----
+    const bool positional = o.noise_positions != NB_PLAN_POS_NONE;
+    bool styles_fast = o.styles_fast && g.c.w_dim % 16 == 0;      // (16-byte friendly shapes)
+    for (const GenLayer& s : g.layers) styles_fast = styles_fast && s.out_ch % 4 == 0;
+    p->styles_fast = styles_fast;
+    // small batches: styles and per-sample noise in one launch (a launch costs more than either computes)
+    p->styles_noise = styles_fast && positional && !o.noise_overrides && n <= 8;
+    // the in-kernel noise tiles normalise integer positions per tile; from batch 9 one launch normalises them for the batch
+    p->positions_once = o.positions_once && o.noise_positions == NB_PLAN_POS_INT && n > 8;
+    // from this layer on every layer runs on the large kernels, which compute their shifted noise in their prologue (not with
+    // per-call noise overrides: their transposes do not exist)
+    p->inkernel_from = -1;
+    if (o.noise_in_kernel && positional && !o.noise_overrides) {
+        int k = nL;
+        while (k > 0 && large(g.layers[k - 1])) --k;
+        p->inkernel_from = k < nL ? k : -1;
+    }
+
+    // ---- the layers ----
+    for (int i = 0; i < nL; ++i) {
+        const GenLayer& s = g.layers[i];
+        const GenLayer* nxt = i + 1 < nL ? &g.layers[i + 1] : nullptr;
+        NbLayerPlan& L = p->layers[i];
+        const int res = s.block_res, ir = s.in_res();
+        const bool is_last = res == g.R;
+        L.noise_in_kernel = p->inkernel_from >= 0 && i >= p->inkernel_from;
+        if (split && has_clamp) {
+            L.packs = NB_PACK_H3;
+            if (f8 && s.in_ch % 16 == 0) L.packs |= NB_PACK_F8 | (mode == NB_CONV_F6 && s.up == 2 ? NB_PACK_F6 : 0);
+            if (s.up == 2 && ir <= 32 && s.in_ch % 16 == 0) L.packs |= NB_PACK_H3_UP2;
+        }
+        if (large(s)) {
+            L.kind = NB_KERNEL_LARGE_H3;
+            L.in_fmt = operand_fmt(s);
+            L.kernel_fmt = mode == NB_CONV_F16 && L.in_fmt == 1 ? 3 : L.in_fmt;
+            // the operand hand-off: both ends large and nothing reads the fp32 activations in between; whole 8-channel groups
+            // (16 for f8 operands, the geometry channels behind them included); f6 operands only from an f8 / f6 up=1 loop
+            const bool tapped = s.up == 1 && (is_last || bit(o.tap_mask | o.blend_mask, res));
+            const int out_fmt = nxt && large(*nxt) ? operand_fmt(*nxt) : 0;
+            const int gi = s.up == 1 ? g.geom_index(res) : -1;
+            const int geo_after = gi < 0 ? 0 : g.geom_ch[gi];
+            L.handoff = o.h2_handoff && nxt && large(*nxt) && !tapped && s.out_ch % 8 == 0
+                && (out_fmt == 0 || (s.out_ch % 16 == 0 && geo_after % 16 == 0)) && (out_fmt != 2 || (L.in_fmt != 0 && s.up == 1));
+            L.out_fmt = L.handoff ? out_fmt : 0;
+            L.fused_torgb = o.fuse_torgb && is_last && s.up == 1 && s.out_ch <= 128 && !bit(o.blend_mask, res);
+            if (s.up == 1)
+                snprintf(L.kernel, sizeof(L.kernel), "modconv3x3_up1_h3_kernel<%d>", s.out_ch > 64 ? 2 : 1);
+            else if (const int r = nb_modconv3x3_up2_h3_variant(L.in_fmt, s.in_ch, s.out_ch, n, ir, ir, L.kernel, sizeof(L.kernel)))
+                return r;
+            continue;
+        }
+        // the small-image split-f16 kernels: <= 64x64 conv1 layers, conv0 layers with inputs <= 32x32 (FIR folded into four
+        // per-phase kernels); whole 16-channel chunks, the geometry channels included
+        const bool small_ok = o.small_h3 && split && clamp_ok && s.in_ch % 16 == 0 && s.in_ch <= 512;
+        if (small_ok && ((s.up == 1 && res <= 64) || (s.up == 2 && (L.packs & NB_PACK_H3_UP2) && s.geom_ch % 16 == 0))) {
+            L.kind = NB_KERNEL_SMALL_H3;
+            snprintf(L.kernel, sizeof(L.kernel), "modconv3x3_up1_small_h3_kernel");
+        } else if (const int r = nb_modconv3x3_variant(n, ir, ir, s.out_ch, s.up, L.kernel, sizeof(L.kernel))) {
+            return r;
+        }
+    }
+
+    // ---- the geometry features: packed into their consumer's operands (not for a block the pass resumes after or whose
+    // fp32 output is tapped or blended) ----
+    for (int gi = 0; gi < ng; ++gi) {
+        NbGeomPlan& G = p->geom[gi];
+        const int gres = g.geom_res[gi], gch = g.geom_ch[gi];
+        G.consumer = -1;
+        for (int i = 0; i + 1 < nL; ++i)
+            if (g.layers[i].block_res == gres && g.layers[i].up == 1) G.consumer = i + 1;
+        if (G.consumer < 0 || (o.resume_res && gres <= o.resume_res) || bit(o.tap_mask | o.blend_mask, gres)) continue;
+        const GenLayer &sp = g.layers[G.consumer - 1], &sc = g.layers[G.consumer];
+        if (!(large(sp) && large(sc))) continue;
+        const int ofmt = operand_fmt(sc);
+        G.early_pack = o.early_geom_pack && o.h2_handoff && sp.out_ch % 8 == 0 && (ofmt == 0 || (sp.out_ch % 16 == 0 && gch % 16 == 0));
+        // (feature 0 also feeds the encoder's own decoder: it stays fp32; the encoder's epilogue writes H2 / f8 operands only)
+        G.encoder_handoff = o.h2_handoff && gi == 1 && ofmt != 2 && sp.out_ch % 16 == 0 && gch % 16 == 0;
+        G.fmt = G.early_pack || G.encoder_handoff ? ofmt : 0;
+    }
+    return rc;
+}
+
 }  // namespace
+
+extern "C" int nb_plan_options_default(NbPlanOptions* o) {
+    NB_REQUIRE(o, "plan_options_default: null pointer");
+    memset(o, 0, sizeof(*o));
+    o->conv_mode = NB_CONV_F8;
+    // the large split-f16 kernels pay from 128 x 128 output pixels per batch: below ~64 workgroups the fp32 kernels (smaller
+    // tiles, split-K) have the lower latency (tools/layers_b1.py: at batch 1 the >= 128x128 layers gain 25-65 %, the <= 64x64
+    // layers lose 40-100 %)
+    o->h3_min_pixels = 128 * 128;
+    o->h3_min_batch = 1;
+    o->h3_up2_w16_min_batch = 16;     // 16x16 -> 32x32 conv0 on the large up=2 kernel (8 x 16 quad tiles) from this batch
+    o->h3_up2_w8_min_batch = 16;      // 8x8 -> 16x16 likewise (the FIR-folded form on the small-image kernel re-reads 147 KB of
+                                      // weights per 32 positions)
+    o->small_h3 = o->h2_handoff = o->early_geom_pack = o->fuse_torgb = o->noise_in_kernel = o->positions_once = o->styles_fast = 1;
+    return NB_OK;
+}
+
+extern "C" int nb_synthesis_plan(const NbGeneratorConfig* cfg, const NbPlanOptions* opts, int n, NbPassPlan* out) {
+    NB_REQUIRE(opts, "synthesis_plan: null options");
+    GenCfg g;
+    const int rc = resolve_cfg(cfg, g);
+    return rc ? rc : plan_pass(g, *opts, n, out);
+}
 
 extern "C" int nb_generator_param_count(const NbGeneratorConfig* cfg) {
     GenCfg g;
@@ -365,8 +510,8 @@ struct GenLayerDev {
 
 struct NbGenerator {
     GenCfg cfg;
-    int mode = 0, n_max = 0, device = 0;
-    bool styles_fast = false;
+    NbPlanOptions opts;              // nb_plan_options_default with the generator's conv_mode
+    int n_max = 0, device = 0;
     float act_gain = 0.f;
     std::vector<void*> allocs;
     std::vector<GenLayerDev> L;
@@ -387,28 +532,13 @@ struct NbGenerator {
     size_t need_act = 0, need_h2 = 0;
     std::vector<size_t> need_pre;
 
-    bool split() const { return mode == NB_CONV_H3 || mode == NB_CONV_F8; }
-    bool clamp_ok() const { return cfg.c.conv_clamp >= 0.f && cfg.c.conv_clamp <= 1024.f; }
-    // SynthesisNetwork._h3_eligible / _h3_up2_eligible / _small_h3_eligible / _small_h3_up2_eligible / _operand_fmt with the
-    // constructor's thresholds (h3_min_pixels 128 * 128, h3_up2_w16_min_batch = h3_up2_w8_min_batch = 16, h3_min_batch 1)
-    bool h3(const GenLayer& s, int n) const {
-        return split() && s.up == 1 && s.block_res >= 32 && (long long)n * s.block_res * s.block_res >= 128 * 128 && s.block_res % 32 == 0 && clamp_ok();
-    }
-    bool h3_up2(const GenLayer& s, int n) const {
-        const int ir = s.in_res();
-        const bool w8 = ir == 8 && n >= 16;
-        return split() && s.up == 2 && ((ir >= 32 && ir % 32 == 0) || (ir == 16 && n >= 16) || w8)
-            && (w8 || (long long)n * s.block_res * s.block_res >= 128 * 128) && clamp_ok();
-    }
-    bool large(const GenLayer& s, int n) const { return s.up == 2 ? h3_up2(s, n) : h3(s, n); }
-    bool small_h3(const GenLayer& s) const {
-        return split() && s.up == 1 && s.block_res <= 64 && s.in_ch % 16 == 0 && s.in_ch <= 512 && clamp_ok();
-    }
-    bool small_h3_up2(const GenLayer& s, const GenLayerDev& d) const {
-        return split() && s.up == 2 && s.in_res() <= 32 && s.in_ch % 16 == 0 && s.in_ch <= 512 && d.w_h3_up2 && clamp_ok();
-    }
-    int operand_fmt(const GenLayer* s) const { return (!s || mode != NB_CONV_F8 || s->in_ch % 16) ? 0 : 1; }
     const NbLayerDesc* table(int first) const { return tables + (size_t)first * (L.size() + 1); }
+    // the plan of a forward at batch n: constant noise shifted by integer positions, or none
+    int plan(int n, bool positional, NbPassPlan* p) const {
+        NbPlanOptions o = opts;
+        o.noise_positions = positional ? NB_PLAN_POS_INT : NB_PLAN_POS_NONE;
+        return plan_pass(cfg, o, n, p);
+    }
 };
 
 namespace {
@@ -418,7 +548,6 @@ size_t h2_bytes(int n, int c, int hw) { return (size_t)n * ((c + 7) / 8) * 2 * h
 struct WalkSink {
     bool launch = false;                                 // enqueue (else: decisions only)
     bool sizing = false;                                 // record workspace needs (NbGenerator::need_*)
-    std::string* describe = nullptr;                     // append "layer=kernel" lines
 };
 
 #define GEN_TRY(call)                      \
@@ -429,14 +558,18 @@ struct WalkSink {
         }                                  \
     } while (0)
 
-// One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant or no noise, no taps / blending / resume).
+// One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant or no noise, no taps / blending / resume),
+// following the pass's plan.
 int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, hipStream_t st, const WalkSink& sink) {
     const GenCfg& cfg = g->cfg;
     const std::vector<GenLayer>& specs = cfg.layers;
     const int nL = (int)specs.size(), R = cfg.R, w_dim = cfg.c.w_dim;
     const float clamp = cfg.c.conv_clamp < 0.f ? -1.f : cfg.c.conv_clamp;
     const float alpha = 0.2f, gain = g->act_gain;
-    char vbuf[128];
+    const bool cnoise = in->noise_mode == NB_NOISE_CONST;
+    const int64_t* ipos = cnoise ? in->positions : nullptr;
+    NbPassPlan plan;
+    if (const int rc = g->plan(n, ipos != nullptr, &plan)) return rc;
 
     // ---- mapping (MappingNetwork.forward) ----
     const float* ws = in->ws;
@@ -455,27 +588,20 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     }
 
     // ---- noise sources (_prepare_noise_sources) ----
-    const bool cnoise = in->noise_mode == NB_NOISE_CONST;
-    const int64_t* ipos = cnoise ? in->positions : nullptr;
     const bool shared = ipos == nullptr;
     const float* npos_k = nullptr;
-    if (cnoise && ipos && n > 8) {                      // positions_once
+    if (plan.positions_once) {
         GEN_TRY(nb_norm_positions_f32(ipos, R, g->npos, n, st));
         npos_k = g->npos;
     }
-    int inkernel_from = -1;                            // first layer from which every layer computes its noise itself
-    if (cnoise && ipos) {
-        int k = nL;
-        while (k > 0 && g->large(specs[k - 1], n)) --k;
-        inkernel_from = k < nL ? k : -1;
-    }
+    const int inkernel_from = plan.inkernel_from;      // first layer from which every layer computes its noise itself
 
     // ---- styles and noise images (_launch_styles_and_noise) ----
     const int n_tab = nL + 1;
-    if (g->styles_fast && cnoise && n <= 8 && ipos) {
+    if (plan.styles_noise) {
         GEN_TRY(nb_styles_noise_f32(g->table(inkernel_from < 0 ? nL : inkernel_from), n_tab, ws, cfg.num_ws, w_dim, nullptr, ipos, R, n, st));
     } else {
-        GEN_TRY((g->styles_fast ? nb_styles_fast_f32 : nb_styles_f32)(g->table(nL), n_tab, ws, cfg.num_ws, w_dim, n, st));
+        GEN_TRY((plan.styles_fast ? nb_styles_fast_f32 : nb_styles_f32)(g->table(nL), n_tab, ws, cfg.num_ws, w_dim, n, st));
         if (cnoise) {
             int hi = n_tab;
             if (inkernel_from >= 0) hi = std::min(hi, inkernel_from);
@@ -489,19 +615,15 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
 
     // ---- early geometry packs (_pack_geometry_early; in-line on the one stream) ----
     const int ng = (int)cfg.geom_res.size();
-    std::vector<bool> pre(ng, false);
     for (int gi = 0; gi < ng; ++gi) {
-        const int gres = cfg.geom_res[gi], gch = cfg.geom_ch[gi];
-        const int ip = cfg.layer_index(fmt("synthesis.b%d.conv1", gres)), ic = cfg.layer_index(fmt("synthesis.b%d.conv0", 2 * gres));
-        const GenLayer &sp = specs[ip], &sc = specs[ic];
-        const int ofmt = g->operand_fmt(&sc);
-        if (!(g->h3(sp, n) && g->h3_up2(sc, n) && sp.out_ch % 8 == 0 && (ofmt == 0 || (sp.out_ch % 16 == 0 && gch % 16 == 0))))
-            continue;
+        const NbGeomPlan& gp = plan.geom[gi];
+        if (!gp.early_pack) continue;
+        const int gres = cfg.geom_res[gi], gch = cfg.geom_ch[gi], ic = gp.consumer;
+        const GenLayer& sc = specs[ic];
         if (sink.sizing) g->need_pre[gi] = std::max(g->need_pre[gi], h2_bytes(n, sc.in_ch, gres * gres));
         const int c_prod = sc.in_ch - gch;
-        GEN_TRY((ofmt ? nb_pack_h2f8_part_f32 : nb_pack_h2_part_f32)(in->geom[gi], gch, g->L[ic].styles + c_prod, sc.in_ch, g->pre_h2[gi],
-                                                                     (sc.in_ch + 7) / 8, c_prod / 8, n, gres * gres, st));
-        pre[gi] = true;
+        GEN_TRY((gp.fmt ? nb_pack_h2f8_part_f32 : nb_pack_h2_part_f32)(in->geom[gi], gch, g->L[ic].styles + c_prod, sc.in_ch, g->pre_h2[gi],
+                                                                       (sc.in_ch + 7) / 8, c_prod / 8, n, gres * gres, st));
     }
 
     // ---- the layers (_run_layers / _run_layer / _finish_block) ----
@@ -510,7 +632,6 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     const float* x2 = nullptr;                        // geometry feature still to be concatenated
     int x2c = 0;
     void* xh2 = nullptr;                              // the next layer's complete operand-format input, when its producer wrote it
-    bool fused_rgb = false;
     float* uvs = out->uvs ? out->uvs : g->uvs_ws;
     float* img = out->img ? out->img : g->img_ws;
     float* colors = out->colors ? out->colors : g->colors_ws;
@@ -521,8 +642,9 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     for (int i = 0; i < nL; ++i) {
         const GenLayer& s = specs[i];
         const GenLayerDev& d = g->L[i];
+        const NbLayerPlan& lp = plan.layers[i];
         const int res = s.block_res, ir = s.in_res();
-        const int c2 = x2c;                           // (not the pointer: the sizing and describe walks carry none)
+        const int c2 = x2c;                           // (not the pointer: the sizing walk carries none)
         const int c1 = x ? xc : s.in_ch - c2;
         if (c1 + c2 != s.in_ch) {
             nb_set_error("generator: %s got %d+%d input channels, expected %d", s.name.c_str(), c1, c2, s.in_ch);
@@ -531,7 +653,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         NbNoiseSrc nsrc{};
         const float* noise = nullptr;
         int64_t nstride = 0;
-        if (cnoise && inkernel_from >= 0 && i >= inkernel_from) {
+        if (lp.noise_in_kernel) {
             nsrc = NbNoiseSrc{d.noise_const_t, d.noise_lin, d.noise_strength, npos_k, npos_k ? nullptr : ipos, res, R};
             noise = (const float*)&nsrc;
             nstride = NB_NOISE_IN_KERNEL;
@@ -539,88 +661,59 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
             noise = d.noise;
             nstride = shared ? 0 : (int64_t)res * res;
         }
-        const GenLayer* nxt = i + 1 < nL ? &specs[i + 1] : nullptr;
-        const bool at_block_end = s.up == 1, is_last = res == R;
-        const bool tapped = at_block_end && is_last;
-        const bool me_h3 = g->large(s, n);
-        const bool nxt_h3 = nxt && g->large(*nxt, n);
-        const int in_fmt = g->operand_fmt(&s), out_fmt = nxt_h3 ? g->operand_fmt(nxt) : 0;
-        const int gi_after = at_block_end ? cfg.geom_index(res) : -1;
-        const int geo_after = gi_after < 0 ? 0 : cfg.geom_ch[gi_after];
-        const bool fuse_out = me_h3 && nxt_h3 && !tapped && s.out_ch % 8 == 0
-            && (out_fmt == 0 || (s.out_ch % 16 == 0 && geo_after % 16 == 0));
+        const bool is_last = res == R;
+        const int gi_after = s.up == 1 ? cfg.geom_index(res) : -1;
         float* y = nullptr;
         void* next_h2 = nullptr;
-        fused_rgb = false;
-        std::string kname;
-        if (me_h3) {
-            const void* wts = in_fmt ? d.w_f8 : d.w_h3;
+        if (lp.kind == NB_KERNEL_LARGE_H3) {
+            const void* wts = lp.in_fmt ? d.w_f8 : d.w_h3;
             if (!wts) {                                 // (at creation the sizing walk stops here: nb_generator_create fails)
-                nb_set_error("generator: %s has no packed weights for operand format %d", s.name.c_str(), in_fmt);
+                nb_set_error("generator: %s has no packed weights for operand format %d", s.name.c_str(), lp.in_fmt);
                 return NB_EINVAL;
             }
             if (!xh2) {                                 // producer was not a split-f16 kernel: (x ++ geometry) * styles -> operands
                 xh2 = g->h2[0];
                 if (sink.sizing) g->need_h2 = std::max(g->need_h2, h2_bytes(n, s.in_ch, ir * ir));
-                GEN_TRY((in_fmt ? nb_pack_h2f8_f32 : nb_pack_h2_f32)(x, c1, x2, c2, d.styles, xh2, n, ir * ir, st));
+                GEN_TRY((lp.in_fmt ? nb_pack_h2f8_f32 : nb_pack_h2_f32)(x, c1, x2, c2, d.styles, xh2, n, ir * ir, st));
             }
-            const bool fuse_rgb = is_last && s.up == 1 && s.out_ch <= 128;
             NbTorgbArgs targs{};
-            if (fuse_rgb) {
+            if (lp.fused_torgb) {
                 targs = NbTorgbArgs{g->trgb_styles, g->trgb_w, g->trgb_b, g->trgb_cb, nullptr, uvs, img, colors, in->user_colors,
                                     in->sfactor, out->rgba, out->rgba_u8, s.out_ch + 9, in->render_mode, clamp};
-            } else if (fuse_out) {
-                if (at_block_end && gi_after >= 0 && pre[gi_after]) {
+            } else if (lp.handoff) {
+                if (gi_after >= 0 && plan.geom[gi_after].early_pack) {
                     next_h2 = g->pre_h2[gi_after];
                 } else {
                     next_h2 = other_h2(xh2);
-                    if (sink.sizing) g->need_h2 = std::max(g->need_h2, h2_bytes(n, nxt->in_ch, res * res));
+                    if (sink.sizing) g->need_h2 = std::max(g->need_h2, h2_bytes(n, specs[i + 1].in_ch, res * res));
                 }
             } else {
                 y = other_act(x);
                 if (sink.sizing) g->need_act = std::max(g->need_act, (size_t)n * s.out_ch * res * res * sizeof(float));
             }
             const float* nst = next_h2 ? g->L[i + 1].styles : nullptr;
-            const int c_next = next_h2 ? nxt->in_ch : 0;
+            const int c_next = next_h2 ? specs[i + 1].in_ch : 0;
             if (s.up == 1) {
                 GEN_TRY(nb_modconv3x3_up1_h3_ex(xh2, s.in_ch, wts, d.dcoefs, noise, nstride, d.bias, y, next_h2, nst, c_next, c_next,
-                                                fuse_rgb ? &targs : nullptr, in_fmt, next_h2 ? out_fmt : 0, n, ir, ir, s.out_ch, alpha,
+                                                lp.fused_torgb ? &targs : nullptr, lp.kernel_fmt, lp.out_fmt, n, ir, ir, s.out_ch, alpha,
                                                 gain, clamp, st));
-                kname = fmt("modconv3x3_up1_h3_kernel<%d>", s.out_ch > 64 ? 2 : 1);
             } else {
                 GEN_TRY(nb_modconv3x3_up2_h3_ex(xh2, s.in_ch, wts, d.dcoefs, noise, nstride, d.bias, y, next_h2, nst, c_next, c_next,
-                                                in_fmt, next_h2 ? out_fmt : 0, n, ir, ir, s.out_ch, alpha, gain, clamp, st));
-                if (sink.describe) {
-                    const int rc = nb_modconv3x3_up2_h3_variant(in_fmt, s.in_ch, s.out_ch, n, ir, ir, vbuf, sizeof(vbuf));
-                    if (rc) return rc;
-                    kname = vbuf;
-                }
+                                                lp.kernel_fmt, lp.out_fmt, n, ir, ir, s.out_ch, alpha, gain, clamp, st));
             }
-            fused_rgb = fuse_rgb;
         } else {
             y = other_act(x);
             if (sink.sizing) g->need_act = std::max(g->need_act, (size_t)n * s.out_ch * res * res * sizeof(float));
-            if (g->small_h3(s) && c2 == 0 && x) {
+            if (lp.kind == NB_KERNEL_SMALL_H3 && s.up == 1) {
                 GEN_TRY(nb_modconv3x3_up1_small_h3(x, c1, d.w_h3, d.styles, d.dcoefs, noise, nstride, d.bias, y, n, ir, ir, s.out_ch,
                                                    alpha, gain, clamp, st));
-                kname = "modconv3x3_up1_small_h3_kernel";
-            } else if (g->small_h3_up2(s, d) && c1 % 16 == 0 && c2 % 16 == 0 && x) {
+            } else if (lp.kind == NB_KERNEL_SMALL_H3) {
                 GEN_TRY(nb_modconv3x3_up2_small_h3(x, c1, x2, c2, d.w_h3_up2, d.styles, d.dcoefs, noise, nstride, d.bias, y, n, ir, ir,
                                                    s.out_ch, alpha, gain, clamp, st));
-                kname = "modconv3x3_up1_small_h3_kernel";
             } else {
                 GEN_TRY(nb_modconv3x3_f32(x, c1, x2, c2, d.wpk, d.styles, d.dcoefs, noise, nstride, d.bias, y, n, ir, ir, s.out_ch, s.up,
                                           alpha, gain, clamp, st));
-                if (sink.describe) {
-                    const int rc = nb_modconv3x3_variant(n, ir, ir, s.out_ch, s.up, vbuf, sizeof(vbuf));
-                    if (rc) return rc;
-                    kname = vbuf;
-                }
             }
-        }
-        if (sink.describe) {
-            *sink.describe += s.name + "=" + kname + "\n";
-            if (fused_rgb) *sink.describe += fmt("synthesis.b%d.torgb=", R) + kname + "\n";       // (in the last conv's epilogue)
         }
         xh2 = next_h2;
         x = y;
@@ -629,23 +722,21 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         x2c = 0;
         if (s.up == 2) continue;
         // ---- what follows a block's last layer ----
-        if (is_last && !fused_rgb) {
+        if (is_last && !lp.fused_torgb) {
             GEN_TRY(nb_torgb_triad_f32(x, g->trgb_styles, c_last + 9, g->trgb_w, g->trgb_b, g->trgb_cb, clamp, nullptr, uvs, img, colors,
                                        in->user_colors, in->sfactor, in->render_mode, out->rgba, out->rgba_u8, n, c_last, R * R, st));
-            if (sink.describe) *sink.describe += fmt("synthesis.b%d.torgb=torgb_triad_kernel\n", R);
         }
         if (gi_after < 0) continue;
         const float* gf = in->geom[geo_idx];
         const int gch = cfg.geom_ch[geo_idx];
-        if (xh2 && pre[geo_idx] && xh2 == g->pre_h2[geo_idx]) {
+        if (xh2 && plan.geom[geo_idx].early_pack && xh2 == g->pre_h2[geo_idx]) {
             // packed at the start of the pass
         } else if (xh2) {
             // the block's last layer wrote its channels into the consumer's operands: the geometry channels go behind them
-            const int inext = cfg.layer_index(fmt("synthesis.b%d.conv0", 2 * res));
-            const GenLayer& sn = specs[inext];
+            const GenLayer& sn = specs[i + 1];
             const int c_prod = sn.in_ch - gch;
-            GEN_TRY((g->operand_fmt(&sn) ? nb_pack_h2f8_part_f32 : nb_pack_h2_part_f32)(gf, gch, g->L[inext].styles + c_prod, sn.in_ch, xh2,
-                                                                                       (sn.in_ch + 7) / 8, c_prod / 8, n, res * res, st));
+            GEN_TRY((plan.layers[i + 1].in_fmt ? nb_pack_h2f8_part_f32 : nb_pack_h2_part_f32)(gf, gch, g->L[i + 1].styles + c_prod, sn.in_ch,
+                                                                                              xh2, (sn.in_ch + 7) / 8, c_prod / 8, n, res * res, st));
         } else {
             x2 = gf;
             x2c = gch;
@@ -698,7 +789,8 @@ extern "C" int nb_generator_create(const NbGeneratorConfig* cfg, const void* con
 
     NbGenerator* g = new NbGenerator();
     g->cfg = gc;
-    g->mode = conv_mode;
+    nb_plan_options_default(&g->opts);
+    g->opts.conv_mode = conv_mode;
     g->n_max = n_max;
     g->act_gain = (float)std::sqrt(2.0);
     hipStream_t st = (hipStream_t)stream;
@@ -772,14 +864,13 @@ extern "C" int nb_generator_create(const NbGeneratorConfig* cfg, const void* con
     if (!ok) return fail(NB_ELAUNCH);
     hipLaunchKernelGGL(gen_repeat_kernel, dim3(nb_cdiv(n_max * c4 * 16, 256)), dim3(256), 0, st, b4_const, c4 * 16, n_max, g->const_rep);
     if ((rc = launched())) return fail(rc);
-    const bool split = conv_mode == NB_CONV_H3 || conv_mode == NB_CONV_F8;
-    const bool has_clamp = C.c.conv_clamp >= 0.f;
+    NbPassPlan plan;                                   // (the weight forms a layer needs do not depend on the batch)
+    if ((rc = g->plan(1, true, &plan))) return fail(rc);
     g->L.resize(nL);
-    g->styles_fast = w_dim % 16 == 0;
     for (int i = 0; i < nL; ++i) {
         const GenLayer& s = C.layers[i];
         GenLayerDev& d = g->L[i];
-        g->styles_fast = g->styles_fast && s.out_ch % 4 == 0;
+        const int packs = plan.layers[i].packs;
         d.weight = P[pi++]; d.noise_strength = P[pi++]; d.bias = P[pi++]; d.noise_grid = P[pi++]; d.filter = P[pi++];
         d.noise_const = P[pi++]; d.affine_w = P[pi++]; d.affine_b = P[pi++];
         const int r = s.block_res;
@@ -791,11 +882,9 @@ extern "C" int nb_generator_create(const NbGeneratorConfig* cfg, const void* con
         d.dcoefs = (float*)alloc((size_t)n_max * s.out_ch * sizeof(float));
         d.noise = (float*)alloc((size_t)n_max * r * r * sizeof(float));
         const size_t h3_bytes = (size_t)(s.in_ch + 15) / 16 * 9 * 4 * ((s.out_ch + 63) / 64 * 64) * 8 * sizeof(_Float16);
-        if (split && has_clamp) {
-            d.w_h3 = alloc(h3_bytes);
-            if (conv_mode == NB_CONV_F8 && s.in_ch % 16 == 0) d.w_f8 = alloc(h3_bytes);
-            if (s.up == 2 && s.in_res() <= 32 && s.in_ch % 16 == 0) d.w_h3_up2 = alloc(4 * h3_bytes);
-        }
+        if (packs & NB_PACK_H3) d.w_h3 = alloc(h3_bytes);
+        if (packs & NB_PACK_F8) d.w_f8 = alloc(h3_bytes);
+        if (packs & NB_PACK_H3_UP2) d.w_h3_up2 = alloc(4 * h3_bytes);
         if (!ok) return fail(NB_ELAUNCH);
         if ((rc = nb_pack_conv_weight_dev(d.weight, s.out_ch, s.in_ch, d.wpk, d.wsq, st))) return fail(rc);
         if (d.w_h3 && (rc = nb_pack_conv_weight_h3_dev(d.weight, s.out_ch, s.in_ch, 64, 0, d.w_h3, st))) return fail(rc);
@@ -889,18 +978,12 @@ extern "C" int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* i
 extern "C" int nb_generator_describe(NbGenerator* gen, int n, char* buf, int len) {
     NB_REQUIRE(gen && buf && len > 0, "generator_describe: bad arguments");
     NB_REQUIRE(n >= 1 && n <= gen->n_max, "generator_describe: batch %d outside [1, n_max = %d]", n, gen->n_max);
+    NbPassPlan plan;
+    if (const int rc = gen->plan(n, true, &plan)) return rc;
     std::string s;
-    NbGeneratorInputs din{};
-    static const float dummy = 0.f;
-    static const int64_t dpos[2] = {0, 0};
-    din.z = &dummy;
-    din.positions = dpos;
-    din.truncation_psi = 1.f;
-    NbGeneratorOutputs dout{};
-    WalkSink sink;
-    sink.describe = &s;
-    const int rc = gen_walk(gen, &din, &dout, n, nullptr, sink);
-    if (rc) return rc;
+    for (int i = 0; i < plan.num_layers; ++i) s += gen->cfg.layers[i].name + "=" + plan.layers[i].kernel + "\n";
+    const NbLayerPlan& last = plan.layers[plan.num_layers - 1];
+    s += fmt("synthesis.b%d.torgb=", gen->cfg.R) + (last.fused_torgb ? last.kernel : "torgb_triad_kernel") + "\n";
     NB_REQUIRE(len > (int)s.size(), "generator_describe: buffer of %d bytes, %d needed", len, (int)s.size() + 1);
     memcpy(buf, s.c_str(), s.size() + 1);
     return NB_OK;

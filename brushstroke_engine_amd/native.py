@@ -23,8 +23,6 @@ def native_config(cfg: GeneratorConfig) -> "_lib.NbGeneratorConfig":
     """config.GeneratorConfig -> struct NbGeneratorConfig."""
     if cfg.c_dim != 0:
         raise ValueError("c_dim must be 0")
-    if tuple(cfg.resample_filter) != (1, 3, 3, 1):
-        raise ValueError("the C entry takes the [1, 3, 3, 1] resample filter of the shipped configuration")
     if len(cfg.geom_feature_channels) > 4:
         raise ValueError("at most 4 geometry features")
     c = _lib.NbGeneratorConfig()
@@ -78,6 +76,8 @@ class NativeGenerator:
         nb_generator_create (which copies and packs them) and released."""
         if conv_mode not in _lib.NB_CONV_MODES:
             raise ValueError(f"unknown conv_mode {conv_mode!r}")
+        if tuple(cfg.resample_filter) != (1, 3, 3, 1):
+            raise ValueError("the C entry takes the [1, 3, 3, 1] resample filter of the shipped configuration")
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())

@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 import math
+import types
 from typing import Dict, Optional
 
 import numpy as np
@@ -28,6 +29,7 @@ import torch
 
 from . import _lib, ops
 from .config import GeneratorConfig, LayerSpec
+from .native import native_config
 from .weights import StateDict, random_state_dict, validate_state_dict
 
 _p = ops._p
@@ -48,8 +50,6 @@ DEFAULT_CONV_MODE = "f8"
 # (1.5e-3 ... 3e-3 from fp32: OUTSIDE the 1e-3 parity budget; the reference's own shipped arithmetic for blocks >= 32^2,
 # training/networks.py:634-638).  A timing data point ("what does the split scheme cost"), not a parity mode.
 CONV_MODES = ("h3", "f8", "f6", "f32", "f16")
-_SPLIT_MODES = ("h3", "f8", "f6", "f16")          # modes whose large layers run on the split-f16 kernel family
-_F8_MODES = ("f8", "f6", "f16")                   # ... with f8 operand containers where the channel counts allow
 
 class FullyConnectedLayer(torch.nn.Module):
     """Parameter holder for ``networks.py:92-122``; evaluated inside nb_mapping_f32 / nb_styles_f32."""
@@ -242,6 +242,22 @@ class _Plan:
         return self._upload(descs), keep
 
 
+class _KernelPlan:
+    """A pass's kernel decisions (nb_synthesis_plan's NbPassPlan, include/neube_hip.h) as plain Python values."""
+
+    def __init__(self, raw: "_lib.NbPassPlan"):
+        self.inkernel_from = None if raw.inkernel_from < 0 else raw.inkernel_from
+        self.styles_fast, self.styles_noise, self.positions_once = bool(raw.styles_fast), bool(raw.styles_noise), bool(raw.positions_once)
+        self.layers = [types.SimpleNamespace(kernel=lp.kernel.decode(), **{k: getattr(lp, k) for k, _ in lp._fields_[1:]})
+                       for lp in raw.layers[:raw.num_layers]]
+        self.geom = [types.SimpleNamespace(**{k: getattr(gp, k) for k, _ in gp._fields_}) for gp in raw.geom[:raw.num_geom]]
+
+
+def _res_mask(resolutions) -> int:
+    """Block resolutions -> NbPlanOptions bit mask (bit log2(res))."""
+    return sum({1 << (int(r).bit_length() - 1) for r in resolutions if r})
+
+
 @dataclasses.dataclass
 class _PassOptions:
     """The private options of one synthesis pass -- the underscore keywords of ``SynthesisNetwork.forward`` that this build's
@@ -295,6 +311,7 @@ class _Pass:
     n: int
     device: torch.device
     plan: "_Plan"
+    kplan: "_KernelPlan"
     lazy_geom: object
     geom_feature: list
     return_debug_data: bool
@@ -307,7 +324,6 @@ class _Pass:
     ipos: Optional[torch.Tensor] = None
     npos_k: Optional[torch.Tensor] = None          # ipos normalised once per batch for the layers that compute their noise themselves
     shared: bool = False                     # constant noise without positions: one image for the whole batch
-    inkernel_from: Optional[int] = None      # first layer (resolution order) from which every layer computes its noise itself
     pre_h2: dict = dataclasses.field(default_factory=dict)
     keep_alive: list = dataclasses.field(default_factory=list)
     x: Optional[torch.Tensor] = None
@@ -347,23 +363,16 @@ class SynthesisNetwork(torch.nn.Module):
         # fp32 on O(1) activations, 1.4e-4 with ten layers at the conv_clamp: tests/golden/gen_hdr_r128.npz; budget 1e-3);
         # "h3": all three hi/lo products on the f16 matrix cores (5e-6); "f32": every layer on the exact-fp32 MFMA kernels.
         self.conv_mode = DEFAULT_CONV_MODE
-        # a layer takes the split-f16 kernels when it has enough output pixels to fill the chip with their (large)
-        # workgroups: below ~64 workgroups the fp32 kernels (smaller tiles, split-K) have the lower latency
-        # (tools/layers_b1.py: at batch 1 the >= 128x128 layers gain 25-65 %, the <= 64x64 layers lose 40-100 %)
-        self.h3_min_pixels = 128 * 128
-        self.h3_up2_w16_min_batch = 16        # 16x16 -> 32x32 conv0 on the large up=2 kernel (8 x 16 quad tiles) from this batch
-        self.h3_up2_w8_min_batch = 16         # 8x8 -> 16x16 conv0 likewise (one 8 x 8 quad tile per sample and c_out slice): the
-                                              # FIR-folded form on the small-image kernel re-reads 147 KB of weights per 32 positions
-        self.h3_min_batch = 1
-        # the latency-oriented styles / demodulation launch needs 16-byte friendly shapes (every style1 shape has them)
-        self._styles_fast = cfg.w_dim % 16 == 0 and all(l.out_channels % 4 == 0 for l in cfg.layers)
-        self._h3_batch_ok = True
-        self._n = 1
-        self.h2_handoff = True            # split-f16 layers write the next layer's H2 input directly (no pack pass)
-        self.early_geom_pack = True       # geometry channels of such inputs are packed at the start, on a side stream
-        self.fuse_torgb = True            # last conv1 + ToRGB + compositing in one launch (split-f16 path)
-        self.noise_in_kernel = True       # large split-f16 layers compute their (position-shifted) noise themselves
-        self.positions_once = True        # ... from positions normalised ONCE per batch (nb_norm_positions_f32) instead of per tile (batches > 8)
+        # The thresholds and switches of the per-batch kernel decisions, with the library's defaults (nb_plan_options_default;
+        # include/neube_hip.h, NbPlanOptions, says what each one does).  The decisions themselves are the library's planner's
+        # (pass_plan); tests and tools may change these attributes between passes.
+        defaults = _lib.NbPlanOptions()
+        _lib.check(_lib.lib().nb_plan_options_default(ctypes.byref(defaults)), "plan_options_default")
+        for k in _lib.NbPlanOptions.KNOBS:
+            v = getattr(defaults, k)
+            setattr(self, k, v if k.startswith("h3_") else bool(v))
+        self._native_cfg = native_config(cfg)
+        self._kernel_plans: Dict[tuple, _KernelPlan] = {}
         self.layer_kernels: Dict[str, str] = {}      # layer name -> kernel; the ToRGB's entry names the last conv's kernel when fused
         self.layer_formats: Dict[str, int] = {}      # operand format each split-f16 layer last ran with (0 H2, 1 f8, 2 f6)
 
@@ -379,6 +388,7 @@ class SynthesisNetwork(torch.nn.Module):
     def invalidate(self):
         self.packed = {}
         self._plans = {}
+        self._kernel_plans = {}
 
     def _apply(self, fn, *a, **k):
         self.invalidate()
@@ -387,21 +397,22 @@ class SynthesisNetwork(torch.nn.Module):
     def _ensure_packed(self):
         if self.packed:
             return
-        for s in self.cfg.layers:
+        kplan = self.pass_plan(1)                  # (the weight forms a layer needs do not depend on the batch or the pass)
+        for s, lp in zip(self.cfg.layers, kplan.layers):
             layer = self.layer_module(s)
             wpk, wsq = ops.pack_conv_weight(layer.weight)
-            self.packed[s.name] = {"wpk": wpk, "wsq": wsq,
-                                   "noise_lin": layer.noise_grid[0, :, 0, 0].contiguous(),
-                                   # transposed copy for the convolutions that compute their noise themselves (NbNoiseSrc)
-                                   "noise_const_t": layer.noise_const.t().contiguous()}
-            if self.conv_mode in _SPLIT_MODES and self.cfg.conv_clamp is not None:
-                self.packed[s.name]["w_h3"] = ops.pack_conv_weight_h3(layer.weight)
-                if self.conv_mode in _F8_MODES and s.in_channels % 16 == 0:
-                    self.packed[s.name]["w_f8"] = ops.pack_conv_weight_h3f8(layer.weight)
-                    if self.conv_mode == "f6" and s.up == 2:
-                        self.packed[s.name]["w_f6"] = ops.pack_conv_weight_h3f6(layer.weight)
-                if s.up == 2 and s.in_res <= 32 and s.in_channels % 16 == 0:
-                    self.packed[s.name]["w_h3_up2"] = ops.pack_conv_weight_h3_up2_phases(layer.weight, layer.resample_filter)
+            pk = self.packed[s.name] = {"wpk": wpk, "wsq": wsq,
+                                        "noise_lin": layer.noise_grid[0, :, 0, 0].contiguous(),
+                                        # transposed copy for the convolutions that compute their noise themselves (NbNoiseSrc)
+                                        "noise_const_t": layer.noise_const.t().contiguous()}
+            if lp.packs & _lib.NB_PACK_H3:
+                pk["w_h3"] = ops.pack_conv_weight_h3(layer.weight)
+            if lp.packs & _lib.NB_PACK_F8:
+                pk["w_f8"] = ops.pack_conv_weight_h3f8(layer.weight)
+            if lp.packs & _lib.NB_PACK_F6:
+                pk["w_f6"] = ops.pack_conv_weight_h3f6(layer.weight)
+            if lp.packs & _lib.NB_PACK_H3_UP2:
+                pk["w_h3_up2"] = ops.pack_conv_weight_h3_up2_phases(layer.weight, layer.resample_filter)
         t = self.get_last_block().torgb
         self.packed["torgb"] = {"w": t.weight.reshape(3, -1).contiguous()}
         # The packed tensors were written by launches on the CURRENT stream, but every stream uses them from now on (the tiled
@@ -411,63 +422,21 @@ class SynthesisNetwork(torch.nn.Module):
         if t.weight.is_cuda and not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream(t.weight.device).synchronize()
 
-    def _h3_eligible(self, s: LayerSpec) -> bool:
-        """conv1 layers that run as 3-pass split-f16 MFMA (csrc/nb_modconv_h3.hip): the kernel needs rows of 32
-        pixels and 16-row tiles, and a conv_clamp so that activations are bounded inside the f16 range."""
-        return (self.conv_mode in _SPLIT_MODES and self._h3_batch_ok and s.up == 1 and s.block_res >= 32
-                and self._n * s.block_res ** 2 >= self.h3_min_pixels and s.block_res % 32 == 0 and self.cfg.conv_clamp is not None and self.cfg.conv_clamp <= 1024)
-
-    def _h3_up2_eligible(self, s: LayerSpec) -> bool:
-        """conv0 (up=2) layers that run on the split-f16 4-phase kernel: input rows must be multiples of 32 pixels, or 16
-        pixels (8 x 16 quad tiles: two workgroups per sample and c_out slice, so only worth it at batch >= 16)."""
-        w8 = s.in_res == 8 and self._n >= self.h3_up2_w8_min_batch
-        return (self.conv_mode in _SPLIT_MODES and self._h3_batch_ok and s.up == 2
-                and ((s.in_res >= 32 and s.in_res % 32 == 0) or (s.in_res == 16 and self._n >= self.h3_up2_w16_min_batch) or w8)
-                and (w8 or self._n * s.block_res ** 2 >= self.h3_min_pixels)
-                and self.cfg.conv_clamp is not None and self.cfg.conv_clamp <= 1024)
-
-    small_h3 = True        # <= 64x64 conv1 layers on the small-tile split-f16 kernel (csrc/nb_modconv_small.hip)
-
-    def _small_h3_eligible(self, s: LayerSpec) -> bool:
-        """conv1 layers too small for the large-tile split-f16 kernel: same hi/lo products on 32 x 32 tiles with K split
-        over the waves, fp32 in and out (needs whole 16-channel chunks and the conv_clamp bound like the other f16 paths)."""
-        return (self.small_h3 and self.conv_mode in _SPLIT_MODES and s.up == 1 and s.block_res <= 64
-                and s.in_channels % 16 == 0 and s.in_channels <= 512
-                and self.cfg.conv_clamp is not None and self.cfg.conv_clamp <= 1024)
-
-    def _small_h3_up2_eligible(self, s: LayerSpec) -> bool:
-        """conv0 (up = 2) layers with inputs <= 32x32 that the large-tile up=2 kernel does not take."""
-        return (self.small_h3 and self.conv_mode in _SPLIT_MODES and s.up == 2 and s.in_res <= 32
-                and s.in_channels % 16 == 0 and s.in_channels <= 512 and s.name in self.packed
-                and "w_h3_up2" in self.packed[s.name]
-                and self.cfg.conv_clamp is not None and self.cfg.conv_clamp <= 1024)
-
-    def _operand_fmt(self, s: Optional[LayerSpec]) -> int:
-        """Operand format of a split-f16 layer's input: 1 = "f8" (correction products on block-scaled fp8 MFMAs; whole
-        16-channel chunks only), 0 = H2 (hi/lo f16); 2 = "f6" (round 5: fp6 correction products with per-pixel block scales) -- in
-        conv_mode "f6", for the layers whose kernel takes it: the up=2 launches that run on the 12-row software-pipelined kernel
-        (their producers, an up=1 kernel and the geometry pack, write the format; the up=2 epilogue does not, so the up=1 layers
-        behind an up=2 layer stay on f8 operands)."""
-        if s is None or self.conv_mode not in _F8_MODES or s.in_channels % 16:
-            return 0
-        if self.conv_mode == "f6" and s.up == 2 and s.in_res % 32 == 0 and self._up2_h3_variant_name(2, self._n, s) == "modconv3x3_up2v_kernel":
-            return 2
-        return 1
-
-    def _variant_name(self, n: int, s: LayerSpec) -> str:
-        buf = ctypes.create_string_buffer(128)
-        _lib.check(_lib.lib().nb_modconv3x3_variant(n, s.in_res, s.in_res, s.out_channels, s.up, buf, 128), "variant")
-        return buf.value.decode()
-
-    def _up2_h3_variant_name(self, in_fmt: int, n: int, s: LayerSpec) -> str:
-        """Which up=2 kernel the library picks for this problem (a label for layer_kernels; resolved once per problem)."""
-        key = (in_fmt, n, s.name)
-        cache = self.__dict__.setdefault("_up2_variant_names", {})
-        if key not in cache:
-            buf = ctypes.create_string_buffer(128)
-            _lib.check(_lib.lib().nb_modconv3x3_up2_h3_variant(in_fmt, s.in_channels, s.out_channels, n, s.in_res, s.in_res, buf, 128), "variant")
-            cache[key] = buf.value.decode()
-        return cache[key]
+    def pass_plan(self, n: int, noise_positions: int = _lib.NB_PLAN_POS_INT, noise_overrides: bool = False, tap_mask: int = 0,
+                  blend_mask: int = 0, resume_res: int = 0) -> "_KernelPlan":
+        """The kernel decisions of a pass at batch ``n`` (nb_synthesis_plan) under the current conv_mode and knobs.  The pass shape
+        is NbPlanOptions': positional constant noise (NB_PLAN_POS_*), per-call noise overrides, the block resolutions whose fp32
+        output is tapped / blended (bit log2(res)) and the block a resumed pass starts after.  Cached per instance."""
+        knobs = tuple(getattr(self, k) for k in _lib.NbPlanOptions.KNOBS)
+        key = (n, self.conv_mode, knobs, noise_positions, noise_overrides, tap_mask, blend_mask, resume_res)
+        kp = self._kernel_plans.get(key)
+        if kp is None:
+            o = _lib.NbPlanOptions(_lib.NB_CONV_MODES[self.conv_mode], *knobs, noise_positions, noise_overrides, tap_mask, blend_mask,
+                                   resume_res)
+            raw = _lib.NbPassPlan()
+            _lib.check(_lib.lib().nb_synthesis_plan(ctypes.byref(self._native_cfg), ctypes.byref(o), n, ctypes.byref(raw)), "synthesis_plan")
+            kp = self._kernel_plans[key] = _KernelPlan(raw)
+        return kp
 
     def _get_plan(self, n: int, device, slot: int = 0) -> _Plan:
         self._ensure_packed()
@@ -528,12 +497,16 @@ class SynthesisNetwork(torch.nn.Module):
             raise RuntimeError(f"ws is on {ws.device} but the generator is on {device}")
         ws = ws.to(torch.float32).contiguous()
         n = ws.shape[0]
-        self._h3_batch_ok = n >= self.h3_min_batch
-        self._n = n
         plan = self._get_plan(n, device, opts.plan_slot)
         lazy_geom = geom_feature if hasattr(geom_feature, "encode_for") else None      # encoder.LazyGeometry
         return_features = [] if return_features is None else return_features
         blended_features = {} if blended_features is None else blended_features
+        const = opts.noise_mode == "const"
+        kplan = self.pass_plan(
+            n, noise_positions=(_lib.NB_PLAN_POS_NONE if not const else _lib.NB_PLAN_POS_INT if opts.positions is not None
+                                else _lib.NB_PLAN_POS_NORM if opts.norm_noise_positions is not None else _lib.NB_PLAN_POS_NONE),
+            noise_overrides=const and bool(noise_buffers), tap_mask=_res_mask(list(return_features) + [opts.stop_after]),
+            blend_mask=_res_mask(blended_features), resume_res=0 if opts.resume is None else opts.resume[0])
         if opts.prepare_only or opts.prepared is not None:
             if (lazy_geom is not None or opts.noise_mode != "const" or noise_buffers or opts.resume is not None
                     or opts.stop_after is not None or opts.reuse_styles or blended_features):
@@ -543,7 +516,7 @@ class SynthesisNetwork(torch.nn.Module):
                 raise RuntimeError("_prepared: the handle belongs to another batch size or workspace slot")
         if lazy_geom is None:
             geom_feature = list(geom_feature) if isinstance(geom_feature, (list, tuple)) else [geom_feature]
-        return _Pass(opts=opts, ws=ws, n=n, device=device, plan=plan, lazy_geom=lazy_geom, geom_feature=geom_feature,
+        return _Pass(opts=opts, ws=ws, n=n, device=device, plan=plan, kplan=kplan, lazy_geom=lazy_geom, geom_feature=geom_feature,
                      return_debug_data=return_debug_data, return_features=return_features, blended_features=blended_features,
                      noise_buffers=noise_buffers, table=plan.table)
 
@@ -557,13 +530,12 @@ class SynthesisNetwork(torch.nn.Module):
         ps.pre_h2 = {} if ps.opts.prepared is None else dict(ps.opts.prepared["pre_h2"])
         if ps.lazy_geom is not None:
             self._encode_lazy_geometry(ps)
-        if self.early_geom_pack and self.h2_handoff and ps.opts.prepared is None:
+        if ps.opts.prepared is None:
             self._pack_geometry_early(ps)
 
     def _prepare_noise_sources(self, ps: "_Pass") -> None:
-        """Per-call noise overrides, the patch positions in the form the kernels take them, and the first layer from which every
-        layer computes its (position-shifted) noise itself."""
-        cfg, opts, plan, n, device = self.cfg, ps.opts, ps.plan, ps.n, ps.device
+        """Per-call noise overrides and the patch positions in the form the kernels take them."""
+        opts, plan, n, device = ps.opts, ps.plan, ps.n, ps.device
         if opts.noise_mode == "const":
             if ps.noise_buffers:
                 ps.table, keep = plan.table_with_noise_overrides(self, ps.noise_buffers)
@@ -577,7 +549,7 @@ class SynthesisNetwork(torch.nn.Module):
                 _assert_shape(ps.npos, [n, 2])
                 ps.keep_alive.append(ps.npos)
             ps.shared = ps.npos is None and ps.ipos is None
-            if self.positions_once and ps.ipos is not None and n > 8:
+            if ps.kplan.positions_once:
                 # Integer positions -> normalised ones ONCE per batch (nb_norm_positions_f32: the function the kernels use, same bits).  The layers
                 # that compute their noise themselves normalise at the top of EVERY tile -- from the integers four 64-bit modulo operations
                 # per lane and tile, 44 us of a 1.93 ms step at batch 32 --, the noise launch once per block.  (Batches <= 8 keep the
@@ -586,20 +558,12 @@ class SynthesisNetwork(torch.nn.Module):
                     plan.npos_k = torch.empty([plan.n_max, 2], dtype=torch.float32, device=device)
                 _lib.check(_lib.lib().nb_norm_positions_f32(_p(ps.ipos), self.img_resolution, _p(plan.npos_k), n, ps.stream), "norm_positions")
                 ps.npos_k = plan.npos_k
-        # first layer (in resolution order) from which every layer runs on the large split-f16 kernels: those compute their
-        # position-shifted noise in their own prologue.  Not with per-call noise buffers (their transposes do not exist).
-        if (self.noise_in_kernel and opts.noise_mode == "const" and ps.table is plan.table and (ps.npos is not None or ps.ipos is not None)):
-            elig = [(self._h3_up2_eligible(sp) if sp.up == 2 else self._h3_eligible(sp)) for sp in cfg.layers]
-            k_ = len(elig)
-            while k_ > 0 and elig[k_ - 1]:
-                k_ -= 1
-            ps.inkernel_from = k_ if k_ < len(elig) else None
 
     def _launch_styles_and_noise(self, ps: "_Pass") -> None:
         """Every layer's affine + demodulation coefficients (one launch) and the small layers' noise images (one launch), into the
         workspace slot -- unless an earlier pass of the same batch left them there."""
         cfg, opts, plan, n, lib, stream = self.cfg, ps.opts, ps.plan, ps.n, _lib.lib(), ps.stream
-        table, npos, ipos, inkernel_from, noise_mode = ps.table, ps.npos, ps.ipos, ps.inkernel_from, opts.noise_mode
+        table, npos, ipos, inkernel_from, noise_mode = ps.table, ps.npos, ps.ipos, ps.kplan.inkernel_from, opts.noise_mode
         if ps.npos_k is not None:
             npos, ipos = ps.npos_k, None         # (normalised once per batch, see _prepare_noise_sources)
         resume, stop_after = opts.resume, opts.stop_after
@@ -611,13 +575,13 @@ class SynthesisNetwork(torch.nn.Module):
             if any(i_ < inkernel_from for i_, sp in enumerate(cfg.layers) if sp.block_res > resume[0]) and noise_mode == "const":
                 raise RuntimeError("_reuse_styles: a resumed layer would need a noise image that no launch of this pass writes")
             return
-        if (self._styles_fast and noise_mode == "const" and table is plan.table and n <= 8 and (npos is not None or ipos is not None)):
+        if ps.kplan.styles_noise:
             # small batches: styles + per-sample noise in one launch (a launch costs more than either computes)
             tbl = plan.table if inkernel_from is None else plan.table_without_noise_from(inkernel_from)
             _lib.check(lib.nb_styles_noise_f32(_p(tbl), plan.n_layers, _p(ps.ws), self.num_ws, self.w_dim, _p(npos),
                                                _p(ipos), self.img_resolution, n, stream), "styles_noise")
             return
-        styles_fn = lib.nb_styles_fast_f32 if self._styles_fast else lib.nb_styles_f32
+        styles_fn = lib.nb_styles_fast_f32 if ps.kplan.styles_fast else lib.nb_styles_f32
         _lib.check(styles_fn(_p(plan.table), plan.n_layers, _p(ps.ws), self.num_ws, self.w_dim, n, stream), "styles")
         if noise_mode == "const":
             # only the layers this pass runs (the tiled-canvas schedule splits the generator at R/2: the head pass
@@ -633,40 +597,27 @@ class SynthesisNetwork(torch.nn.Module):
                                             max(sp.block_res for sp in cfg.layers[lo_:hi_]), _p(npos), _p(ipos),
                                             self.img_resolution, n, stream), "noise")
 
-    def _geometry_consumers(self, ps: "_Pass"):
-        """(g_idx, gres, producer index / spec, consumer index / spec, geometry channels, consumer operand format) of every geometry
-        feature that could be handed to its consumer in operand format: injected below the image resolution, in a block this pass
-        runs, and neither tapped nor blended at its resolution."""
-        cfg, opts = self.cfg, ps.opts
-        specs_ = {s_.name: (i_, s_) for i_, s_ in enumerate(cfg.layers)}
-        for g_idx, gres in enumerate(self.geom_feature_resolutions):
-            if (opts.resume is not None and gres <= opts.resume[0]) or gres >= cfg.img_resolution:
-                continue
-            if gres in ps.return_features or gres in ps.blended_features or opts.stop_after == gres:
-                continue
-            ip, sp_ = specs_[f"synthesis.b{gres}.conv1"]
-            ic, sc_ = specs_[f"synthesis.b{2 * gres}.conv0"]
-            yield g_idx, gres, ip, sp_, ic, sc_, self.geom_feature_channels[g_idx], self._operand_fmt(sc_)
+    def _geometry_consumers(self, ps: "_Pass", decision: str):
+        """(g_idx, gres, consumer index / spec, geometry channels, consumer operand format) of every geometry feature whose plan
+        (NbGeomPlan) has ``decision`` ("early_pack" or "encoder_handoff") set."""
+        for g_idx, gp in enumerate(ps.kplan.geom):
+            if getattr(gp, decision):
+                yield (g_idx, self.geom_feature_resolutions[g_idx], gp.consumer, self.cfg.layers[gp.consumer],
+                       self.geom_feature_channels[g_idx], gp.fmt)
 
     def _encode_lazy_geometry(self, ps: "_Pass") -> None:
         """Geometry not encoded yet (encoder.LazyGeometry): let the encoder write the features that feed an H2 / f8 layer input
         straight into that layer's operand tensor (x the consumer's styles, which exist now); the rest comes back as fp32."""
         opts, plan, n, device, lazy_geom = ps.opts, ps.plan, ps.n, ps.device, ps.lazy_geom
         targets = {}
-        if self.h2_handoff:
-            for g_idx, gres, ip, sp_, ic, sc_, gch, ofmt in self._geometry_consumers(ps):
-                if g_idx != 1:
-                    continue                        # (feature 0 also feeds the encoder's own decoder: it stays fp32)
-                # (the encoder's hand-off epilogue writes H2 / f8 operands only: an f6 consumer gets the feature back in
-                #  fp32 and the pack path writes its operands)
-                if (ofmt != 2 and self._h3_eligible(sp_) and self._h3_up2_eligible(sc_) and sp_.out_channels % 16 == 0 and gch % 16 == 0
-                        and tuple(lazy_geom.feature_shape(g_idx)) == (n, gch, gres, gres)
-                        and getattr(lazy_geom, "can_handoff", lambda i_: True)(g_idx)):
-                    dst = torch.empty(ops.h2_shape(n, sc_.in_channels, gres, gres), dtype=torch.float16, device=device)
-                    c_prod = sc_.in_channels - gch
-                    targets[g_idx] = dict(dst=dst, scale_ptr=plan.styles[ic].data_ptr() + 4 * c_prod, scale_stride=sc_.in_channels,
-                                          c8_total=sc_.in_channels // 8, cg0=c_prod // 8, fmt=ofmt)
-                    ps.pre_h2[gres] = (dst, None)
+        for g_idx, gres, ic, sc_, gch, ofmt in self._geometry_consumers(ps, "encoder_handoff"):
+            if (tuple(lazy_geom.feature_shape(g_idx)) == (n, gch, gres, gres)
+                    and getattr(lazy_geom, "can_handoff", lambda i_: True)(g_idx)):
+                dst = torch.empty(ops.h2_shape(n, sc_.in_channels, gres, gres), dtype=torch.float16, device=device)
+                c_prod = sc_.in_channels - gch
+                targets[g_idx] = dict(dst=dst, scale_ptr=plan.styles[ic].data_ptr() + 4 * c_prod, scale_stride=sc_.in_channels,
+                                      c8_total=sc_.in_channels // 8, cg0=c_prod // 8, fmt=ofmt)
+                ps.pre_h2[gres] = (dst, None)
         needed = [gres for gres in self.geom_feature_resolutions if opts.resume is None or gres >= opts.resume[0]]
         if not needed:
             ps.geom_feature = [None] * len(self.geom_feature_resolutions)      # a resumed pass past the last injection
@@ -679,11 +630,8 @@ class SynthesisNetwork(torch.nn.Module):
         """fp32 geometry features x the consumer's styles -> the consumer's operand tensor, on the slot's side stream."""
         plan, n, device, lib, geom_feature = ps.plan, ps.n, ps.device, _lib.lib(), ps.geom_feature
         pack_waited = False           # has plan.pack_stream been ordered behind this call's styles launch yet?
-        for g_idx, gres, ip, sp_, ic, sc_, gch, ofmt in self._geometry_consumers(ps):
+        for g_idx, gres, ic, sc_, gch, ofmt in self._geometry_consumers(ps, "early_pack"):
             if g_idx >= len(geom_feature) or gres in ps.pre_h2 or geom_feature[g_idx] is None:
-                continue
-            if not (self._h3_eligible(sp_) and self._h3_up2_eligible(sc_) and sp_.out_channels % 8 == 0
-                    and (ofmt == 0 or (sp_.out_channels % 16 == 0 and gch % 16 == 0))):
                 continue
             g = geom_feature[g_idx]
             if g.device != device or g.dtype != torch.float32 or not g.is_contiguous() or tuple(g.shape) != (n, gch, gres, gres):
@@ -741,7 +689,7 @@ class SynthesisNetwork(torch.nn.Module):
             elif ps.x is not None:                  # (None: the previous block handed its output over in H2 format)
                 _assert_shape(ps.x, [None, block.in_channels - (0 if ps.x2 is None else ps.x2.shape[1]), res // 2, res // 2])
             for name in names:
-                self._run_layer(ps, block, res, *specs[name])
+                self._run_layer(ps, res, *specs[name])
             if opts.stop_after is not None and res == opts.stop_after:
                 return ps.x
             self._finish_block(ps, block, res, specs)
@@ -749,13 +697,13 @@ class SynthesisNetwork(torch.nn.Module):
             return ps.img, ps.debug_data
         return ps.img
 
-    def _run_layer(self, ps: "_Pass", block, res: int, i: int, s: LayerSpec) -> None:
+    def _run_layer(self, ps: "_Pass", res: int, i: int, s: LayerSpec) -> None:
         """One SynthesisLayer (networks.py:362-391) = one fused launch (+ a pack launch in front of a split-f16 layer whose
         producer was not one).  Reads ps.x / ps.x2 / ps.x_h2, leaves the layer's output there."""
         cfg, opts, plan, n, device, lib, stream = self.cfg, ps.opts, ps.plan, ps.n, ps.device, _lib.lib(), ps.stream
         name, noise_mode, extra = s.name, opts.noise_mode, opts.extra
         x, x2, x_h2 = ps.x, ps.x2, ps.x_h2
-        return_features, blended_features, stop_after = ps.return_features, ps.blended_features, opts.stop_after
+        return_features, stop_after = ps.return_features, opts.stop_after
         layer = self.layer_module(s)
         pk = self.packed[name]
         if opts.mark is not None and name == opts.mark[1]:
@@ -764,8 +712,9 @@ class SynthesisNetwork(torch.nn.Module):
         c1 = s.in_channels - c2 if x is None else x.shape[1]
         if c1 + c2 != s.in_channels:
             raise AssertionError(f"{name}: got {c1}+{c2} input channels, expected {s.in_channels}")
+        lp = ps.kplan.layers[i]
         noise_ptr, nstride = None, 0
-        if noise_mode == "const" and ps.inkernel_from is not None and i >= ps.inkernel_from:
+        if noise_mode == "const" and lp.noise_in_kernel:
             nsrc = _lib.NbNoiseSrc(_p(pk["noise_const_t"]), _p(pk["noise_lin"]), _p(layer.noise_strength),
                                    _p(ps.npos if ps.npos_k is None else ps.npos_k), _p(ps.ipos if ps.npos_k is None else None),
                                    s.block_res, self.img_resolution)
@@ -779,28 +728,15 @@ class SynthesisNetwork(torch.nn.Module):
             ps.keep_alive.append(rnd)
             noise_ptr, nstride = rnd.data_ptr(), s.block_res * s.block_res
         clamp = -1.0 if layer.conv_clamp is None else float(layer.conv_clamp)
-        # split-f16 layers hand activations over in H2 format (pre-multiplied by the consumer's styles).
-        # `x_h2` is this layer's complete H2 input if the previous layer produced it; `next_h2` is the
-        # consumer's input tensor this layer writes into directly when both ends are split-f16 kernels
-        # and nothing taps the fp32 activations in between (feature taps, blending, ToRGB, stop_after).
+        # split-f16 layers hand activations over in H2 / f8 operand format (pre-multiplied by the consumer's styles).
+        # `x_h2` is this layer's complete operand input if the previous layer produced it; `next_h2` is the consumer's input
+        # tensor this layer writes into directly (lp.handoff)
         nxt = cfg.layers[i + 1] if i + 1 < len(cfg.layers) else None
         at_block_end = s.up == 1
-        tapped = at_block_end and (block.is_last or res in return_features or res in blended_features
-                                   or stop_after == res)
-        me_h3 = self._h3_up2_eligible(s) if s.up == 2 else self._h3_eligible(s)
-        nxt_h3 = nxt is not None and (self._h3_eligible(nxt) if nxt.up == 1 else self._h3_up2_eligible(nxt))
-        in_fmt = self._operand_fmt(s)                       # 0 = H2 (hi/lo f16), 1 = f8 corrections
-        out_fmt = self._operand_fmt(nxt) if nxt_h3 else 0
-        geo_after = (self.geom_feature_channels[self.geom_feature_resolutions.index(res)]
-                     if at_block_end and res in self.geom_feature_resolutions else 0)
-        # (the f6 operand format is written by the f8 / f6 up=1 loops only: a producer on H2 operands -- c_in not a
-        #  multiple of 16 -- hands its output over in fp32 and the pack launch writes the consumer's operands)
-        fuse_out = (self.h2_handoff and me_h3 and nxt_h3 and not tapped and s.out_channels % 8 == 0
-                    and (out_fmt == 0 or (s.out_channels % 16 == 0 and geo_after % 16 == 0))
-                    and (out_fmt != 2 or (in_fmt != 0 and s.up == 1)))
         y = next_h2 = None
         ps.fused_rgb = None
-        if me_h3:
+        if lp.kind == _lib.NB_KERNEL_LARGE_H3:
+            in_fmt = lp.in_fmt                              # 0 = H2 (hi/lo f16), 1 = f8 corrections, 2 = f6
             if x_h2 is None:
                 # producer was not a split-f16 kernel: (x ++ geometry) * styles -> H2 / f8 operands
                 evp = self._begin_event("pack_h2")
@@ -812,17 +748,15 @@ class SynthesisNetwork(torch.nn.Module):
                 self._end_event(evp)
             ev = self._begin_event(name)
             wts = pk["w_f6"] if in_fmt == 2 else pk["w_f8"] if in_fmt else pk["w_h3"]
-            fuse_rgb = (self.fuse_torgb and block.is_last and s.up == 1 and s.out_channels <= 128
-                        and res not in blended_features)
             targs = None
-            if fuse_rgb:
+            if lp.fused_torgb:
                 # last conv + ToRGB + compositing in one launch; the fp32 activations are only written
                 # when a caller taps them
                 tg = self._torgb_setup(plan, n, device, extra)
                 targs = self._torgb_args(plan, tg, s.out_channels)
                 if res in return_features or stop_after == res:
                     y = torch.empty([n, s.out_channels, s.block_res, s.block_res], dtype=torch.float32, device=device)
-            elif fuse_out:
+            elif lp.handoff:
                 if at_block_end and res in ps.pre_h2:
                     next_h2 = ps.pre_h2[res][0]                    # geometry channels are (being) packed into it
                 else:
@@ -832,37 +766,32 @@ class SynthesisNetwork(torch.nn.Module):
                 y = torch.empty([n, s.out_channels, s.block_res, s.block_res], dtype=torch.float32, device=device)
             nst = _p(plan.styles[i + 1]) if next_h2 is not None else None
             c_next = nxt.in_channels if next_h2 is not None else 0
-            kfmt = 3 if (self.conv_mode == "f16" and in_fmt == 1) else in_fmt        # f8 operands, hi x hi products only (large kernels)
             if s.up == 1:
                 _lib.check(lib.nb_modconv3x3_up1_h3_ex(
                     _p(x_h2), s.in_channels, _p(wts), _p(plan.dcoefs[i]), noise_ptr, nstride, _p(layer.bias),
                     _p(y), _p(next_h2), nst, c_next, c_next, None if targs is None else ctypes.byref(targs),
-                    kfmt, out_fmt if next_h2 is not None else 0, n, s.in_res, s.in_res, s.out_channels, 0.2,
+                    lp.kernel_fmt, lp.out_fmt, n, s.in_res, s.in_res, s.out_channels, 0.2,
                     layer.act_gain, clamp, stream), name)
             else:
                 _lib.check(lib.nb_modconv3x3_up2_h3_ex(
                     _p(x_h2), s.in_channels, _p(wts), _p(plan.dcoefs[i]), noise_ptr, nstride, _p(layer.bias),
-                    _p(y), _p(next_h2), nst, c_next, c_next, kfmt, out_fmt if next_h2 is not None else 0, n,
+                    _p(y), _p(next_h2), nst, c_next, c_next, lp.kernel_fmt, lp.out_fmt, n,
                     s.in_res, s.in_res, s.out_channels, 0.2, layer.act_gain, clamp, stream), name)
-            if fuse_rgb:
-                ps.fused_rgb = self._torgb_finish(tg, extra)
             self.layer_formats[name] = in_fmt
-            self.layer_kernels[name] = ("modconv3x3_up1_h3_kernel<%d>" % (2 if s.out_channels > 64 else 1)
-                                        if s.up == 1 else self._up2_h3_variant_name(in_fmt, n, s))
-            if fuse_rgb:
-                self.layer_kernels[cfg.torgb_name] = self.layer_kernels[name]        # (ToRGB in the last conv's epilogue)
+            if lp.fused_torgb:
+                ps.fused_rgb = self._torgb_finish(tg, extra)
+                self.layer_kernels[cfg.torgb_name] = lp.kernel        # (ToRGB in the last conv's epilogue)
             ps.keep_alive.append(x_h2)
             self._end_event(ev)
-        elif self._small_h3_eligible(s) and c2 == 0 and x is not None:
+        elif lp.kind == _lib.NB_KERNEL_SMALL_H3 and s.up == 1:
             # small conv1 layer: split-f16 products on 32 x 32 tiles with K split over the waves
             ev = self._begin_event(name)
             y = torch.empty([n, s.out_channels, s.block_res, s.block_res], dtype=torch.float32, device=device)
             _lib.check(lib.nb_modconv3x3_up1_small_h3(
                 _p(x), c1, _p(pk["w_h3"]), _p(plan.styles[i]), _p(plan.dcoefs[i]), noise_ptr, nstride,
                 _p(layer.bias), _p(y), n, s.in_res, s.in_res, s.out_channels, 0.2, layer.act_gain, clamp, stream), name)
-            self.layer_kernels[name] = "modconv3x3_up1_small_h3_kernel"
             self._end_event(ev)
-        elif self._small_h3_up2_eligible(s) and c1 % 16 == 0 and c2 % 16 == 0 and x is not None:
+        elif lp.kind == _lib.NB_KERNEL_SMALL_H3:
             # small conv0 layer: the FIR is folded into four per-phase 3x3 kernels (ops.fold_up2_fir), the
             # phases run through the same small-tile split-f16 kernel
             ev = self._begin_event(name)
@@ -870,7 +799,6 @@ class SynthesisNetwork(torch.nn.Module):
             _lib.check(lib.nb_modconv3x3_up2_small_h3(
                 _p(x), c1, _p(x2), c2, _p(pk["w_h3_up2"]), _p(plan.styles[i]), _p(plan.dcoefs[i]), noise_ptr, nstride,
                 _p(layer.bias), _p(y), n, s.in_res, s.in_res, s.out_channels, 0.2, layer.act_gain, clamp, stream), name)
-            self.layer_kernels[name] = "modconv3x3_up1_small_h3_kernel"
             self._end_event(ev)
         else:
             ev = self._begin_event(name)
@@ -879,8 +807,8 @@ class SynthesisNetwork(torch.nn.Module):
                 _p(x), c1, _p(x2), c2, _p(pk["wpk"]), _p(plan.styles[i]), _p(plan.dcoefs[i]), noise_ptr,
                 nstride, _p(layer.bias), _p(y), n, s.in_res, s.in_res, s.out_channels, s.up, 0.2,
                 layer.act_gain, clamp, stream), name)
-            self.layer_kernels[name] = self._variant_name(n, s)
             self._end_event(ev)
+        self.layer_kernels[name] = lp.kernel
         ps.x_h2 = next_h2
         ps.keep_alive += [x, x2]
         ps.x, ps.x2 = y, None
@@ -937,7 +865,7 @@ class SynthesisNetwork(torch.nn.Module):
             inext, snext = specs[f"synthesis.b{2 * res}.conv0"]
             c_prod = snext.in_channels - x2.shape[1]
             evp = self._begin_event("pack_h2")
-            part = (lib.nb_pack_h2_part_f32, lib.nb_pack_h2f8_part_f32, lib.nb_pack_h2f6_part_f32)[self._operand_fmt(snext)]
+            part = (lib.nb_pack_h2_part_f32, lib.nb_pack_h2f8_part_f32, lib.nb_pack_h2f6_part_f32)[ps.kplan.layers[inext].in_fmt]
             _lib.check(part(_p(x2), x2.shape[1], plan.styles[inext].data_ptr() + 4 * c_prod, snext.in_channels,
                             _p(x_h2), (snext.in_channels + 7) // 8, c_prod // 8, n, res * res, stream),
                        "pack_h2_part")

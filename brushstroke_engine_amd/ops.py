@@ -340,7 +340,7 @@ def _conv2d_launch(x, w, in_scale, out_scale, stride, padding):
         ones = lambda c: _const(1.0, [n, c], x.device)
         return _modulated_conv2d_forward(x, w, ones(ci) if in_scale is None else in_scale, None, up=1, padding=1, demodulate=False,
                                          flip_weight=True, dcoefs=ones(co) if out_scale is None else out_scale)
-    if _s2_valid_h3_eligible(n, ci, h, wd, kh, kw, stride, padding):
+    if _s2_valid_h3_supported(n, ci, h, wd, kh, kw, stride, padding):
         return _conv2d_s2_valid_h3(x, w, in_scale, out_scale)
     ho, wo = (h + 2 * padding - kh) // stride + 1, (wd + 2 * padding - kw) // stride + 1
     if (TRAIN_SPLIT_F16 and kh == 3 and kw == 3 and stride == 1 and padding in (0, 1, 2) and ho >= 16 and wo >= 16
@@ -747,7 +747,7 @@ def pack_conv_weight_h3_dev(weight: torch.Tensor, co_align: int = 64, tf: bool =
     return out
 
 
-def _s2_valid_h3_eligible(n, ci, h, wd, kh, kw, stride, padding) -> bool:
+def _s2_valid_h3_supported(n, ci, h, wd, kh, kw, stride, padding) -> bool:
     if not (TRAIN_SPLIT_F16 and kh == 3 and kw == 3 and stride == 2 and padding == 0 and h % 2 == 1 and wd % 2 == 1):
         return False
     ho, wo = (h - 1) // 2, (wd - 1) // 2

@@ -274,10 +274,8 @@ class TileOps:
         """Create the generator workspaces of ``slots`` for batches of ``n`` on the CALLER's stream, before the batch streams fork
         (a workspace is otherwise created by the first batch that needs it, on that batch's stream, while the other stream is
         already running)."""
-        syn = self.G.synthesis
-        syn._n, syn._h3_batch_ok = n, n >= syn.h3_min_batch
         for sl in slots:
-            syn._get_plan(n, self.device, sl)
+            self.G.synthesis._get_plan(n, self.device, sl)
 
     def map_style(self, z=None, ws=None) -> torch.Tensor:
         if ws is not None:

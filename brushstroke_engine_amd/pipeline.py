@@ -62,10 +62,9 @@ class TriadStepPipeline:
         syn = self.G.synthesis
         if not (syn.noise_in_kernel and syn.conv_mode in ("h3", "f8", "f16")):
             return False
-        syn._n, syn._h3_batch_ok = n, n >= syn.h3_min_batch
         syn._ensure_packed()
-        return all((syn._h3_up2_eligible(sp) if sp.up == 2 else syn._h3_eligible(sp))
-                   for sp in syn.cfg.layers if sp.block_res > self.split_res)
+        kplan = syn.pass_plan(n, resume_res=self.split_res)        # (the tail: positional constant noise, resumed after split_res)
+        return all(lp.noise_in_kernel for sp, lp in zip(syn.cfg.layers, kplan.layers) if sp.block_res > self.split_res)
 
     def submit(self, z, geom_feature, positions, user_colors=None, sfactor=None) -> torch.Tensor:
         if positions is None:

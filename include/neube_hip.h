@@ -625,6 +625,72 @@ int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* in, const Nb
  * records), the ToRGB's line included: the last conv's kernel when it is fused there, else torgb_triad_kernel.  Host only. */
 int nb_generator_describe(NbGenerator* gen, int n, char* buf, int len);
 
+/* ---- the per-batch layer plan (host only: no HIP call, works without a GPU) ------------------------------------------------
+ * Every kernel decision of one synthesis pass at batch n: which kernel each layer runs, its operand formats, the operand hand-off,
+ * the fused ToRGB, in-kernel noise, the styles / noise launches and the early geometry packs.  The package's Python pass
+ * (SynthesisNetwork) and nb_generator_forward both follow it. */
+
+#define NB_PLAN_MAX_LAYERS 24         /* 2 log2(R / 4) + 1 layers: 21 at R = 4096 */
+#define NB_PLAN_POS_NONE 0            /* NbPlanOptions.noise_positions */
+#define NB_PLAN_POS_INT  1            /* constant noise shifted by integer patch positions */
+#define NB_PLAN_POS_NORM 2            /* ... by normalised positions */
+#define NB_KERNEL_F32      0          /* NbLayerPlan.kind: exact-fp32 kernels (nb_modconv3x3_f32) */
+#define NB_KERNEL_SMALL_H3 1          /* split-f16 small-image kernels (nb_modconv3x3_up{1,2}_small_h3) */
+#define NB_KERNEL_LARGE_H3 2          /* split-f16 large-tile kernels (nb_modconv3x3_up{1,2}_h3_ex) */
+#define NB_PACK_H3     1              /* NbLayerPlan.packs: nb_pack_conv_weight_h3 */
+#define NB_PACK_F8     2              /* the "f8" weight format */
+#define NB_PACK_F6     4              /* the "f6" weight format */
+#define NB_PACK_H3_UP2 8              /* the four FIR-folded up=2 phase kernels (nb_pack_conv_weight_h3_up2_dev) */
+
+typedef struct NbPlanOptions {
+    int32_t conv_mode;                /* NB_CONV_* */
+    /* a layer takes the large split-f16 kernels from h3_min_pixels output pixels per batch and from batch h3_min_batch; the
+     * up=2 layers with 16x16 / 8x8 inputs (quad tiles that cover a sample with few workgroups) from these batches */
+    int32_t h3_min_pixels, h3_min_batch, h3_up2_w16_min_batch, h3_up2_w8_min_batch;
+    /* switches (0 / 1): small-image split-f16 kernels; operand hand-off between large layers; early geometry packs; ToRGB fused
+     * into a large last layer; in-kernel noise of the large layers; positions normalised once per batch; the latency-oriented
+     * styles launch (where the shapes allow it) */
+    int32_t small_h3, h2_handoff, early_geom_pack, fuse_torgb, noise_in_kernel, positions_once, styles_fast;
+    /* the pass: NB_PLAN_POS_* (constant noise with positions; NONE for constant noise without them or other noise modes);
+     * noise_overrides = per-call noise_const replacements; block resolutions (bit log2(res)) whose fp32 output the caller taps
+     * (feature taps, a pass that stops after the block) or blends; resume_res = the pass starts after this block (0 = none) */
+    int32_t noise_positions, noise_overrides, tap_mask, blend_mask, resume_res;
+} NbPlanOptions;
+
+typedef struct NbLayerPlan {
+    char kernel[64];                  /* the kernel's name (SynthesisNetwork.layer_kernels, nb_generator_describe) */
+    int32_t kind;                     /* NB_KERNEL_* */
+    int32_t in_fmt;                   /* large: operand format of the input, 0 H2, 1 f8, 2 f6 (else 0) */
+    int32_t kernel_fmt;               /* large: the kernel's in_fmt argument (3 = f8 operands, hi x hi products only: "f16") */
+    int32_t out_fmt;                  /* handoff: the operand format the layer writes for the next one (else 0) */
+    int32_t handoff;                  /* writes the next layer's operand input instead of fp32 output */
+    int32_t fused_torgb;              /* the ToRGB + compositing run in this layer's epilogue */
+    int32_t noise_in_kernel;          /* computes its shifted noise itself (NbNoiseSrc) */
+    int32_t packs;                    /* NB_PACK_* weight forms the layer's launches may need (at any batch) */
+} NbLayerPlan;
+
+typedef struct NbGeomPlan {
+    int32_t consumer;                 /* layer index of the consumer, b{2 res}.conv0 (-1: none, the feature is at R) */
+    int32_t early_pack;               /* packed into the consumer's operands at the start of the pass */
+    int32_t encoder_handoff;          /* the encoder may write it into the consumer's operands */
+    int32_t fmt;                      /* the operand format of either (else 0) */
+} NbGeomPlan;
+
+typedef struct NbPassPlan {
+    int32_t num_layers, num_geom;
+    int32_t inkernel_from;            /* first layer from which every layer computes its noise itself (-1: none) */
+    int32_t styles_fast;              /* nb_styles_fast_f32 (else nb_styles_f32) */
+    int32_t styles_noise;             /* styles and noise images in one launch (nb_styles_noise_f32) */
+    int32_t positions_once;           /* integer positions normalised once per batch (nb_norm_positions_f32) */
+    NbLayerPlan layers[NB_PLAN_MAX_LAYERS];
+    NbGeomPlan geom[4];
+} NbPassPlan;
+
+/* Today's defaults: the thresholds and switches both callers use, conv_mode NB_CONV_F8, a pass without positions. */
+int nb_plan_options_default(NbPlanOptions* opts);
+/* The plan of one pass at batch n (1 <= n <= 65535).  f6 / f16 are planned too. */
+int nb_synthesis_plan(const NbGeneratorConfig* cfg, const NbPlanOptions* opts, int n, NbPassPlan* out);
+
 /* ---- box calibration (csrc/nb_calib.hip; measurement infrastructure, not on the generator's path) -----------------
  * A registers-only loop of back-to-back v_mfma_f32_32x32x16_f16 on random operands, one wave per SIMD on every CU of the current
  * device, for about target_ms (blocking).  *tflops = the dense f16 matrix rate this device sustains, *ms = duration of the measured

@@ -30,7 +30,7 @@ if os.environ.get("NB_UPLOAD") == "main":
         t.record_stream(cur)
         return t
     _nw._Plan._upload = _up
-if os.environ.get('NB_NOFAST'): G.synthesis._styles_fast = False
+if os.environ.get('NB_NOFAST'): G.synthesis.styles_fast = False
 if os.environ.get('NB_NONOISE'):
     with torch.no_grad():
         for nme, prm in G.named_parameters():
@@ -70,7 +70,6 @@ for it in range(80):
     KEEP.clear() if False else None
     if os.environ.get("NB_SWITCH", "1") == "1": G.set_conv_mode("f32")
     if os.environ.get("NB_PREPACK"):
-        G.synthesis._n, G.synthesis._h3_batch_ok = 4, False
         G.synthesis._ensure_packed(); torch.cuda.synchronize()
     if os.environ.get("NB_PREPLAN") == "1":
         for sl in (8, 9): G.synthesis._get_plan(4, torch.device("cuda", 0), sl)
