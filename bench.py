@@ -1,6 +1,6 @@
 """Headline benchmark: stylized 256x256 stroke patches / second at batch 32 on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 256] [--batch 32] [--no-cpu] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 256] [--batch 32] [--dump-outputs DIR] [--full [--no-cpu] ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started without a torchrun environment and --gpus N > 1, it launches the N ranks itself (one process per GPU through
@@ -15,18 +15,23 @@ positions, style1 checkpoint shapes at R=256, fp32).  Inputs are resident in HBM
 region.  With N > 1 every rank renders its own batch (weak scaling, replicated weights) and the
 uint8 RGBA tiles are gathered to rank 0 over RCCL inside the step, overlapped with the next batch.
 
-Prints ONE JSON line on rank 0 (contract in the task brief).  Top level = the PRIMARY arithmetic mode (the library
-default, `f8`): `value`, `ms_per_step`, `roofline` (dominant kernel: algorithmic FLOPs / HIP-event time on the launch
-stream, against the dense MFMA peak of the type that kernel MULTIPLIES in -- MI355X_MICROARCH.md), `dtype` (what
-multiplies; never "f32" for a split mode).  At N=1 the same process then measures the other two modes the same way
-(own Generator, same W warm-up + K timed steps) and reports all three under `modes` = {"f8": .., "h3": .., "f32": ..},
+Prints ONE JSON line on rank 0.  Top level = the PRIMARY arithmetic mode (the library default, `f8`): `value`,
+`ms_per_step`, `dtype` (what multiplies; never "f32" for a split mode).  A plain run does only what that figure needs:
+it sets up, probes the stream count of the concurrent schedule, burns in and warms up, times the K steps and prints the
+line.
+
+--full adds everything else the benchmark measures or checks, in the same process: the registers-only MFMA calibration
+of the board and its power / clock telemetry; per mode, the same K steps back to back on ONE stream (`value_single_stream`)
+with `roofline` (dominant kernel: algorithmic FLOPs / HIP-event time on the launch stream, against the dense MFMA peak of
+the type that kernel MULTIPLIES in -- MI355X_MICROARCH.md).  At N=1 it then measures the other modes the same way (own
+Generator, same W warm-up + K timed steps) and reports them under `modes` = {"f8": .., "h3": .., "f32": .., "f16": ..},
 each with value / ms_per_step / roofline / live parity against the fp32 CPU oracle; `value_fp32_parity` = the `h3`
-number (SURVEY 8d's "fp32 parity mode": products to ~2^-22).  `cpu_baseline` = the CPU oracle (port of the reference
-path) timed on this box's host cores on a bounded sample.
+number (SURVEY 8d's "fp32 parity mode": products to ~2^-22); `latency_batch1` = one patch through the hipGraph-captured
+step; `cpu_baseline` = the CPU oracle (port of the reference path) timed on this box's host cores on a bounded sample.
 
 --dump-outputs DIR writes what the headline leg's last timed step returned to its caller -- the uint8 RGBA tiles of the
-primary mode, rank 0's batch -- as DIR/rgba_u8.npy in float32 (see dump_outputs).  Weights and inputs are seeded, so two
-builds run with the same arguments can be compared output for output.
+primary mode, rank 0's batch -- as DIR/rgba_u8.npy in float32 (see dump_outputs), with or without --full.  Weights and
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -218,8 +223,9 @@ def traffic_lookup(table, kname):
 
 def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, sampler=None, calib=None, outputs=None):
     """W warm-up steps, then exactly K timed steps of the hot path in one arithmetic mode, bracketed by barrier +
-    synchronize; returns this mode's figures (value, ms_per_step, roofline of its dominant kernel).  ``outputs`` (a dict):
-    receives the uint8 RGBA tiles of the last timed step of the leg `value` is measured on, as a host array."""
+    synchronize; returns this mode's figures (value, ms_per_step; with --full also the single-stream leg and the roofline of
+    its dominant kernel).  ``outputs`` (a dict): receives the uint8 RGBA tiles of the last timed step of the leg `value` is
+    measured on, as a host array."""
     from brushstroke_engine_amd.sharding import TileGatherer
     z, geom, pos = inputs
     B = args.batch
@@ -329,78 +335,6 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
                 break
         elif (stable and spent >= 0.5) or spent >= 8.0:
             break
-    for _ in range(args.warmup):
-        step()
-    finish_gathers()
-    torch.cuda.synchronize()
-
-    # Calibration (untimed): 3 steps with a HIP-event pair around EVERY launch give the per-layer table and name the
-    # dominant kernel.  Event pairs cost ~10 us of stream time each (45 launches -> ~0.9 ms per step), so the timed
-    # region below only brackets the launches of that dominant kernel.
-    G.synthesis.layer_events, G.synthesis.event_filter = [], None
-    for _ in range(3):
-        step()
-    finish_gathers()
-    torch.cuda.synchronize()
-    cal_events = G.synthesis.layer_events
-    layer_kernels = dict(G.synthesis.layer_kernels)
-    cal = {}
-    for name, e0, e1 in cal_events:
-        cal.setdefault(name, []).append(e0.elapsed_time(e1))
-    ksum = {}
-    for name, ts in cal.items():
-        if name in layer_kernels:
-            ksum[layer_kernels[name]] = ksum.get(layer_kernels[name], 0.0) + float(np.mean(ts))
-    dom_name = max(ksum, key=ksum.get)
-    dom_layers = {name for name, k in layer_kernels.items() if k == dom_name}
-
-    # events for the timed region are created and recorded once beforehand (event creation is slow in a fresh process),
-    # and the timed loop is rehearsed once, untimed, in exactly its final configuration (same event filter, pooled
-    # events) so that nothing happens for the first time inside the timed region
-    def make_pool():
-        pool = [torch.cuda.Event(enable_timing=True) for _ in range(2 * len(dom_layers) * args.steps + 2)]
-        for e in pool:
-            e.record()
-        torch.cuda.synchronize()
-        return pool
-    G.synthesis.event_pool = make_pool()
-    G.synthesis.layer_events = []
-    none_ = frozenset()
-    t_reh = time.perf_counter()
-    for i_ in range(args.steps):
-        G.synthesis.event_filter = dom_layers if i_ % args.event_every == 0 else none_
-        step()
-    finish_gathers()
-    torch.cuda.synchronize()
-    rehearsal_ms = (time.perf_counter() - t_reh) / args.steps * 1e3
-    G.synthesis.event_pool = make_pool()
-    if use_pg:
-        dist.barrier()
-    torch.cuda.synchronize()
-    G.synthesis.layer_events = []
-    for g_ in [gatherer] + part_gatherers:
-        if g_ is not None:
-            g_.wait_ms()                                 # (reset: count the waits of the timed region only)
-    t0 = time.perf_counter()
-    for i_ in range(args.steps):
-        G.synthesis.event_filter = dom_layers if i_ % args.event_every == 0 else none_
-        last = step()
-    finish_gathers()
-    torch.cuda.synchronize()
-    elapsed_local = time.perf_counter() - t0
-    if use_pg:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    if sampler is not None:
-        sampler.unmark(mode)                    # (moved on below when the concurrent leg follows)
-    if outputs is not None and conc is None:    # (a pipeline returns the tiles; render_triad a tuple, or a joining callable)
-        last = last() if callable(last) else last
-        outputs["rgba_u8"] = (last if torch.is_tensor(last) else last[0]).cpu().numpy()
-    last = None
-    events = G.synthesis.layer_events
-    G.synthesis.layer_events, G.synthesis.event_filter, G.synthesis.event_pool = None, None, None
-
     def reduce_times(el, el_local):
         """MAX over ranks of the timed region, and every rank's own time for its K steps (before the closing barrier)."""
         if not use_pg:
@@ -426,10 +360,90 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
                         "HIP events on the issuing stream around the wait (an RCCL wait stalls the stream, not the host); the "
                         "gather of a step is waited for when its stream's next step has been enqueued, after a whole step of compute"}
 
-    elapsed, per_rank_ms = reduce_times(elapsed, elapsed_local)
-    gather_wait = gather_wait_of([gatherer] + part_gatherers)
-    single = {"value": round(world * B * args.steps / elapsed, 2), "ms_per_step": round(elapsed / args.steps * 1e3, 4), "schedule": schedule_single}
-    schedule = schedule_single
+    # The single-stream leg: W warm-up steps, then K timed steps on the schedule of step().  It is the headline when the schedule
+    # is not the concurrent one; with --full it always runs, and the roofline comes from it.  Only --full brackets launches
+    # with HIP events (calibration pass, dominant kernel in the timed steps): a plain run times the bare steps.
+    single, schedule, cal, events, rehearsal_ms = None, schedule_single, {}, [], None
+    if args.full or conc is None:
+        for _ in range(args.warmup):
+            step()
+        finish_gathers()
+        torch.cuda.synchronize()
+
+        none_ = frozenset()
+        dom_layers = none_
+        if args.full:
+            # Calibration (untimed): 3 steps with a HIP-event pair around EVERY launch give the per-layer table and name the
+            # dominant kernel.  Event pairs cost ~10 us of stream time each (45 launches -> ~0.9 ms per step), so the timed
+            # region below only brackets the launches of that dominant kernel.
+            G.synthesis.layer_events, G.synthesis.event_filter = [], None
+            for _ in range(3):
+                step()
+            finish_gathers()
+            torch.cuda.synchronize()
+            cal_events = G.synthesis.layer_events
+            layer_kernels = dict(G.synthesis.layer_kernels)
+            for name, e0, e1 in cal_events:
+                cal.setdefault(name, []).append(e0.elapsed_time(e1))
+            ksum = {}
+            for name, ts in cal.items():
+                if name in layer_kernels:
+                    ksum[layer_kernels[name]] = ksum.get(layer_kernels[name], 0.0) + float(np.mean(ts))
+            dom_name = max(ksum, key=ksum.get)
+            dom_layers = {name for name, k in layer_kernels.items() if k == dom_name}
+
+        # events for the timed region are created and recorded once beforehand (event creation is slow in a fresh process),
+        # and the timed loop is rehearsed once, untimed, in exactly its final configuration (same event filter, pooled
+        # events) so that nothing happens for the first time inside the timed region
+        def make_pool():
+            pool = [torch.cuda.Event(enable_timing=True) for _ in range(2 * len(dom_layers) * args.steps + 2)]
+            for e in pool:
+                e.record()
+            torch.cuda.synchronize()
+            return pool
+        if args.full:
+            G.synthesis.event_pool = make_pool()
+            G.synthesis.layer_events = []
+        t_reh = time.perf_counter()
+        for i_ in range(args.steps):
+            G.synthesis.event_filter = dom_layers if i_ % args.event_every == 0 else none_
+            step()
+        finish_gathers()
+        torch.cuda.synchronize()
+        rehearsal_ms = (time.perf_counter() - t_reh) / args.steps * 1e3
+        if args.full:
+            G.synthesis.event_pool = make_pool()
+        if use_pg:
+            dist.barrier()
+        torch.cuda.synchronize()
+        if args.full:
+            G.synthesis.layer_events = []
+        for g_ in [gatherer] + part_gatherers:
+            if g_ is not None:
+                g_.wait_ms()                                 # (reset: count the waits of the timed region only)
+        t0 = time.perf_counter()
+        for i_ in range(args.steps):
+            G.synthesis.event_filter = dom_layers if i_ % args.event_every == 0 else none_
+            last = step()
+        finish_gathers()
+        torch.cuda.synchronize()
+        elapsed_local = time.perf_counter() - t0
+        if use_pg:
+            dist.barrier()
+        torch.cuda.synchronize()
+        elapsed = time.perf_counter() - t0
+        if sampler is not None:
+            sampler.unmark(mode)                    # (moved on below when the concurrent leg follows)
+        if outputs is not None and conc is None:    # (a pipeline returns the tiles; render_triad a tuple, or a joining callable)
+            last = last() if callable(last) else last
+            outputs["rgba_u8"] = (last if torch.is_tensor(last) else last[0]).cpu().numpy()
+        last = None
+        events = G.synthesis.layer_events or []
+        G.synthesis.layer_events, G.synthesis.event_filter, G.synthesis.event_pool = None, None, None
+
+        elapsed, per_rank_ms = reduce_times(elapsed, elapsed_local)
+        gather_wait = gather_wait_of([gatherer] + part_gatherers)
+        single = {"value": round(world * B * args.steps / elapsed, 2), "ms_per_step": round(elapsed / args.steps * 1e3, 4), "schedule": schedule_single}
     if conc is not None:
         # the headline leg: the same K steps on the concurrent schedule -- W warm-up steps, one untimed rehearsal of the timed loop,
         # then exactly K steps between barrier + synchronize on both sides; no events inside (launches overlap: their durations say
@@ -470,6 +484,30 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
                     f"(pipeline.ConcurrentTriadSteps, the library's throughput schedule"
                     + (f"; stream count chosen by its probe: {conc.probe}" if conc.probe else "") + "); every step is the plain "
                     "Generator.render_triad pass: bit-identical to the serial loop (tests/test_hip_generator.py)")
+
+    ms_per_step = elapsed / args.steps * 1e3
+    whole = B * 2 * cfg.macs_per_patch() / (ms_per_step * 1e-3) / 1e12
+    headline = {
+        "value": round(world * B * args.steps / elapsed, 2), "unit": "patches/s", "ms_per_step": round(ms_per_step, 4),
+        "steps": args.steps, "warmup": args.warmup, "dtype": MODE_DTYPE[mode], "schedule": schedule,
+        "roofline_whole_step": {
+            "what": "the whole step (all launches of one GPU) against the ceilings of SURVEY 8d: algorithmic FLOPs of the batch / ms_per_step",
+            "achieved": round(whole, 1), "unit": "TFLOP/s", "fp32_matrix_peak": PEAK_F32_MATRIX_TFLOPS,
+            "scheme_ceiling": round(scheme_ceiling(mode), 1), "frac_of_scheme_ceiling": round(whole / scheme_ceiling(mode), 4),
+            "note": "scheme ceiling = the matrix work the arithmetic mode executes per algorithmic FLOP at nominal dense peaks (f8: one f16 "
+                    "+ two fp8 MFMA FLOPs; h3: three f16); the K loops run at ~1.6-1.8 GHz under load (in-kernel s_memtime clock), not 2.4"},
+        "rehearsal_ms_per_step": round(rehearsal_ms, 4),
+        "burn_in_ms_per_step": [round(b, 3) for b in burn_in[:6]] + (["..."] if len(burn_in) > 7 else []) + [round(b, 3) for b in burn_in[6:][-1:]],
+    }
+    if conc is not None:
+        headline["streams"] = conc.streams
+        headline["stream_probe"] = conc.probe
+    if per_rank_ms is not None:
+        headline["ms_per_step_per_rank"] = per_rank_ms
+    if gather_wait is not None:
+        headline["gather_wait_ms"] = gather_wait
+    if not args.full:
+        return headline
 
     # after the timed region: the dominant kernel once more with the whole batch on ONE stream (3 steps), so that its
     # launch duration is also known without another stream's kernels sharing the chip
@@ -582,34 +620,13 @@ def measure_mode(G, mode, args, cfg, inputs, world, rank, dev, backend, gather, 
         roofline["frac_of_sustained"] = round(achieved / calib["mfma_f16_sustained_tflops"], 4)
         roofline["frac_of_sustained_what"] = ("achieved / box_calibration.mfma_f16_sustained_tflops: against what THIS board holds on a "
                                               "registers-only f16 MFMA loop at its own clock under load, instead of the nominal 2.5 PFLOP/s")
-    ms_per_step = elapsed / args.steps * 1e3
-    whole = B * 2 * cfg.macs_per_patch() / (ms_per_step * 1e-3) / 1e12
     extra = {}
     if sampler is not None:
         extra["telemetry"] = sampler.summary(mode)
     if conc is not None:
         extra["value_single_stream"] = single["value"]
         extra["single_stream"] = single
-        extra["streams"] = conc.streams
-        extra["stream_probe"] = conc.probe
-    if per_rank_ms is not None:
-        extra["ms_per_step_per_rank"] = per_rank_ms
-    if gather_wait is not None:
-        extra["gather_wait_ms"] = gather_wait
-    return {
-        **extra,
-        "value": round(world * B * args.steps / elapsed, 2), "unit": "patches/s", "ms_per_step": round(ms_per_step, 4),
-        "steps": args.steps, "warmup": args.warmup, "dtype": MODE_DTYPE[mode], "schedule": schedule,
-        "roofline": roofline,
-        "roofline_whole_step": {
-            "what": "the whole step (all launches of one GPU) against the ceilings of SURVEY 8d: algorithmic FLOPs of the batch / ms_per_step",
-            "achieved": round(whole, 1), "unit": "TFLOP/s", "fp32_matrix_peak": PEAK_F32_MATRIX_TFLOPS,
-            "scheme_ceiling": round(scheme_ceiling(mode), 1), "frac_of_scheme_ceiling": round(whole / scheme_ceiling(mode), 4),
-            "note": "scheme ceiling = the matrix work the arithmetic mode executes per algorithmic FLOP at nominal dense peaks (f8: one f16 "
-                    "+ two fp8 MFMA FLOPs; h3: three f16); the K loops run at ~1.6-1.8 GHz under load (in-kernel s_memtime clock), not 2.4"},
-        "rehearsal_ms_per_step": round(rehearsal_ms, 4),
-        "burn_in_ms_per_step": [round(b, 3) for b in burn_in[:6]] + (["..."] if len(burn_in) > 7 else []) + [round(b, 3) for b in burn_in[6:][-1:]],
-    }
+    return {**headline, **extra, "roofline": roofline}
 
 
 MAX_LINE_BYTES = 4096               # the final stdout line: the driver keeps the last 8 KB of stdout
@@ -685,14 +702,16 @@ def fit_line(c):
 
 
 def compact_line(out):
-    """What goes to stdout: the contract's keys, numbers only (no calibration tables, no per-layer times, no explanatory strings)."""
+    """What goes to stdout: the contract's keys, numbers only (no calibration tables, no per-layer times, no explanatory strings).
+    The figures of a --full run (roofline, box calibration, the other modes ...) only where the record has them."""
     c = _pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "conv_mode", "data"))
     c["vs_baseline"] = None
     c["dtype"] = out["dtype"].split(",")[0].split(":")[0][:90]
     cfg_ = out["config"]
     c["config"] = {"workload": cfg_["workload"].split(";")[0], "batch_per_gpu": cfg_["batch_per_gpu"], "resolution": cfg_["resolution"],
                    "gflop_per_patch": cfg_["gflop_per_patch"], "parallelism": cfg_["parallelism"].split(" inside every step")[0]}
-    c["roofline"] = compact_roofline(out["roofline"])
+    if out.get("roofline"):
+        c["roofline"] = compact_roofline(out["roofline"])
     ws = out.get("roofline_whole_step") or {}
     c["roofline_whole_step"] = _pick(ws, ("achieved", "unit", "scheme_ceiling", "frac_of_scheme_ceiling"))
     if out.get("cpu_baseline"):
@@ -701,7 +720,8 @@ def compact_line(out):
         par = out["cpu_baseline"].get("parity")
         if par:
             c["parity"] = _pick(par, ("max_abs_rgba_vs_oracle", "max_u8_diff", "tolerance", "patches"))
-    c["box_calibration"] = _pick(out.get("box_calibration") or {}, ("mfma_f16_sustained_tflops", "loop_clock_mhz"))
+    if "box_calibration" in out:
+        c["box_calibration"] = _pick(out["box_calibration"] or {}, ("mfma_f16_sustained_tflops", "loop_clock_mhz"))
     tele = _pick(out.get("telemetry") or {}, ("power_w_mean", "sclk_mhz_mean", "power_cap_w", "samples"))
     if tele and tele.get("power_w_mean") is not None:          # (absent when the window held too few samples to mean anything)
         c["telemetry"] = tele
@@ -721,7 +741,8 @@ def compact_line(out):
                     "parity": (r.get("parity") or {}).get("max_abs_rgba_vs_oracle")}
         if m == "f16":
             modes[m]["note"] = "reference's shipped arithmetic (plain f16 products); NOT a parity mode: outside the 1e-3 budget"
-    c["modes"] = modes
+    if modes:
+        c["modes"] = modes
     if out.get("rccl"):
         f = out["rccl"]
         c["rccl"] = _pick(f, ("world", "backend", "nccl_version", "distinct_devices"))
@@ -732,44 +753,49 @@ def compact_line(out):
     return c
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--batch", type=int, default=32, help="patches per GPU per step")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (and with it the live parity of every mode)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the auxiliary legs: batch-1 hipGraph latency, three-steps-in-flight throughput")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything else, in the same process: board calibration and telemetry, the "
+                         "single-stream leg and the roofline of its dominant kernel, the other arithmetic modes (N=1), batch-1 latency, "
+                         "the CPU baseline and every mode's parity against it.  Without it a run does only what `value` needs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg (and with it the live parity of every mode)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the batch-1 hipGraph latency leg")
     ap.add_argument("--conv-mode", default=None, choices=["h3", "f8", "f6", "f32", "f16"],
                     help="the PRIMARY arithmetic mode = top-level value; default: the library default (networks.DEFAULT_CONV_MODE = f8). "
                          "f8: f16 main product + two block-scaled fp8 correction products (pixels within 1e-4 of fp32; budget 1e-3); "
                          "h3: three f16 products on hi/lo-split operands (5e-6); f32: all layers on the fp32 MFMA kernels")
     ap.add_argument("--modes", default=None,
-                    help="comma list of arithmetic modes measured one after the other in this process (each its own Generator, W warm-up + K "
-                         "timed steps) and reported under `modes`; default: all three at N=1, the primary one only at N>1; 'primary' = only it")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU time budget of the cpu_baseline leg")
+                    help="--full: comma list of arithmetic modes measured one after the other in this process (each its own Generator, W "
+                         "warm-up + K timed steps) and reported under `modes`; default: f8, h3, f32, f16 at N=1, the primary one only at N>1; "
+                         "'primary' = only it (what a run without --full measures)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU time budget of the cpu_baseline leg")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the RGBA gather to rank 0")
     ap.add_argument("--schedule", default="concurrent", choices=["concurrent", "single", "pipeline", "prefetch"],
                     help="how the K steps are enqueued.  concurrent (default; the library's throughput schedule, pipeline.ConcurrentTriadSteps): "
-                         "independent steps dealt round-robin to --streams HIP streams with a workspace slot each -- `value` is measured on it, "
-                         "`roofline` and `value_single_stream` on the same K steps back to back on ONE stream (measured in the same run, where "
-                         "every launch has the chip to itself and its HIP-event duration is the kernel's own time).  single: only that leg.  "
-                         "pipeline / prefetch: the two-stream software pipelines of pipeline.py (+2 %% / -0.3 %%; kept for A/Bs)")
+                         "independent steps dealt round-robin to --streams HIP streams with a workspace slot each -- `value` is measured on it; "
+                         "with --full, `roofline` and `value_single_stream` on the same K steps back to back on ONE stream (measured in the same "
+                         "run, where every launch has the chip to itself and its HIP-event duration is the kernel's own time).  single: only "
+                         "that leg.  pipeline / prefetch: the two-stream software pipelines of pipeline.py (+2 %% / -0.3 %%; kept for A/Bs)")
     ap.add_argument("--streams", type=int, default=0, help="streams of the concurrent schedule; 0 = the library's probe picks 1 or 3")
     ap.add_argument("--prefetch", action="store_true", help="= --schedule prefetch")
     ap.add_argument("--pipeline", action="store_true", help="= --schedule pipeline")
     ap.add_argument("--full-line", action="store_true", help="print the FULL record on stdout instead of the compact line (the A/B scripts under "
-                                                             "tools/ read its calibration tables); never what the driver runs")
+                                                             "tools/ read the calibration tables of a --full run from it)")
     ap.add_argument("--detail", default=None, help="where the full record goes (default: bench_detail.json next to this file)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the headline leg's last timed step returned (the primary mode's uint8 RGBA "
                          "tiles of rank 0's batch) as DIR/rgba_u8.npy in float32; a fixed, seeded sample of the patches if the whole "
                          f"would exceed {DUMP_LIMIT_BYTES >> 20} MB")
     ap.add_argument("--event-every", type=int, default=4,
-                    help="bracket the dominant kernel's launches with HIP events in every K-th timed step (an event pair costs ~10 us "
-                         "of stream time, which a single chain of launches cannot hide)")
-    args = ap.parse_args()
+                    help="--full: bracket the dominant kernel's launches with HIP events in every K-th step of the single-stream leg (an "
+                         "event pair costs ~10 us of stream time, which a single chain of launches cannot hide)")
+    args = ap.parse_args(argv)
     if args.event_every < 1:
         ap.error("--event-every must be >= 1")
     if args.steps < 1 or args.warmup < 0:
@@ -780,7 +806,13 @@ def main():
         ap.error("--streams must lie in 0..8")
     if args.dump_outputs and args.res * args.res * 4 * 4 + 8 > DUMP_LIMIT_BYTES - 2 * NPY_HEADER_BYTES:
         ap.error(f"--dump-outputs: one {args.res}x{args.res} patch exceeds {DUMP_LIMIT_BYTES >> 20} MB")
+    if args.modes not in (None, "primary") and not args.full:
+        ap.error("--modes measures other arithmetic modes: that needs --full (a plain run measures the primary mode, --conv-mode)")
+    return args
 
+
+def main():
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # self-launch: N ranks as a child torchrun.  Nothing in this process has touched the GPU (importing torch does
         # not), and it only waits for the child -- no exec of a GPU-initialised process.  The kernel library is built
@@ -853,7 +885,9 @@ def main():
     from brushstroke_engine_amd.sharding import TileGatherer
     if args.conv_mode is None:
         args.conv_mode = DEFAULT_CONV_MODE
-    if args.modes in (None, "all"):
+    if not args.full:
+        modes = [args.conv_mode]                        # (parse_args refuses --modes naming other modes without --full)
+    elif args.modes in (None, "all"):
         # (f6 -- the round-5 experiment, not faster and less accurate than f8 -- only on request: --modes f6 or all)
         # (f16: the reference's shipped precision, OUTSIDE the parity budget -- a timing data point, labelled so in `modes.f16.note`)
         modes = (["f8", "h3", "f32", "f16", "f6"] if args.modes == "all" else ["f8", "h3", "f32", "f16"]) if (world == 1 or args.modes == "all") else [args.conv_mode]
@@ -897,23 +931,24 @@ def main():
     # who is here (N > 1: all-gather of every rank's device; fails unless the ranks sit on N distinct devices)
     from brushstroke_engine_amd import launch as _launch, telemetry as _tele
     fabric = _launch.fabric_report(dev, rank, world, backend, collective=use_pg)
-    # what this board sustains on the instruction the conv kernels are built on (50 ms registers-only f16 MFMA loop), before
-    # anything is timed; then a side thread samples board power and shader clock for the rest of the run
-    calib = None
-    try:
-        import ctypes as _C
-        tf, ms_, clk = _C.c_double(), _C.c_double(), _C.c_double()
-        _nblib.check(_nblib.lib().nb_calibrate_mfma_f16(50.0, _C.byref(tf), _C.byref(ms_), _C.byref(clk), None), "calibrate")
-        calib = {"mfma_f16_sustained_tflops": round(tf.value, 1), "loop_ms": round(ms_.value, 2), "loop_clock_mhz": round(clk.value, 1),
-                 "frac_of_nominal_peak": round(tf.value / PEAK_F16_MATRIX_TFLOPS, 4),
-                 "what": "registers-only loop of back-to-back v_mfma_f32_32x32x16_f16 on random operands, one wave per SIMD on every CU "
-                         "(nb_calibrate_mfma_f16), ~50 ms, run before the first mode; loop_clock_mhz = median in-kernel clock "
-                         "(s_memtime / s_memrealtime)"}
-    except Exception as e:                                       # noqa: BLE001
-        calib = {"mfma_f16_sustained_tflops": None, "what": f"calibration failed: {e}"}
-    # (NB_TELEMETRY=0: no sampler thread at all -- the switch of the sampler-on/off A/B, tools/ab_env.sh NB_TELEMETRY=0)
-    sampler = _tele.PowerClockSampler(_tele.find_hwmon(_tele.pci_bus_id_of(local_rank)) if os.environ.get("NB_TELEMETRY", "1") != "0" else None)
-    sampler.__enter__()
+    # --full: what this board sustains on the instruction the conv kernels are built on (50 ms registers-only f16 MFMA loop),
+    # before anything is timed; then a side thread samples board power and shader clock for the rest of the run
+    calib, sampler = None, None
+    if args.full:
+        try:
+            import ctypes as _C
+            tf, ms_, clk = _C.c_double(), _C.c_double(), _C.c_double()
+            _nblib.check(_nblib.lib().nb_calibrate_mfma_f16(50.0, _C.byref(tf), _C.byref(ms_), _C.byref(clk), None), "calibrate")
+            calib = {"mfma_f16_sustained_tflops": round(tf.value, 1), "loop_ms": round(ms_.value, 2), "loop_clock_mhz": round(clk.value, 1),
+                     "frac_of_nominal_peak": round(tf.value / PEAK_F16_MATRIX_TFLOPS, 4),
+                     "what": "registers-only loop of back-to-back v_mfma_f32_32x32x16_f16 on random operands, one wave per SIMD on every CU "
+                             "(nb_calibrate_mfma_f16), ~50 ms, run before the first mode; loop_clock_mhz = median in-kernel clock "
+                             "(s_memtime / s_memrealtime)"}
+        except Exception as e:                                       # noqa: BLE001
+            calib = {"mfma_f16_sustained_tflops": None, "what": f"calibration failed: {e}"}
+        # (NB_TELEMETRY=0: no sampler thread at all -- the switch of the sampler-on/off A/B, tools/ab_env.sh NB_TELEMETRY=0)
+        sampler = _tele.PowerClockSampler(_tele.find_hwmon(_tele.pci_bus_id_of(local_rank)) if os.environ.get("NB_TELEMETRY", "1") != "0" else None)
+        sampler.__enter__()
     gens, results = {}, {}
     dumped = {} if (args.dump_outputs and rank == 0) else None
     for m in modes:
@@ -941,9 +976,7 @@ def main():
                                                                     f"per step; see gather_wait_ms / ms_per_step_per_rank / rccl)") if gather else " (NO gather: --no-gather)")},
             "schedule": prim["schedule"],
             **({"debug_switches": dbg_env} if dbg_env else {}),
-            "box_calibration": calib,
-            "telemetry": prim.get("telemetry"),
-            "roofline": prim["roofline"],
+            **({"box_calibration": calib, "telemetry": prim.get("telemetry"), "roofline": prim["roofline"]} if args.full else {}),
             "roofline_whole_step": prim["roofline_whole_step"],
             "rehearsal_ms_per_step": prim["rehearsal_ms_per_step"],
             "burn_in_ms_per_step": prim["burn_in_ms_per_step"],
@@ -955,18 +988,19 @@ def main():
             out["rccl"] = fabric
             out["ms_per_step_per_rank"] = prim.get("ms_per_step_per_rank")
             out["gather_wait_ms"] = prim.get("gather_wait_ms")
-        if "h3" in results:
-            # SURVEY 8(d)'s "fp32 parity mode": every fp32 product to ~2^-22 (5e-6 on pixels), the same grade as an fp32 evaluation
-            out["value_fp32_parity"] = results["h3"]["value"]
-            out["value_fp32_parity_what"] = "patches/s of mode h3 (fp32-grade products: 5e-6 from an all-fp32 evaluation); f32 = exact fp32 MFMA"
-        out["modes"] = {m: {k: v for k, v in r.items()} for m, r in results.items()}
-        if world == 1 and not args.no_latency:
-            out["latency_batch1"] = latency_batch1(G, cfg, dev, geom, pos)
-        if world == 1 and not args.no_cpu:
-            out["cpu_baseline"] = cpu_baseline(cfg, sd, seconds_budget=args.cpu_seconds, gens=gens, dev=dev)
-            for m, pr in out["cpu_baseline"].pop("parity_by_mode", {}).items():
-                out["modes"][m]["parity"] = pr
-            out["cpu_baseline"]["parity"] = out["modes"][args.conv_mode].get("parity")
+        if args.full:
+            if "h3" in results:
+                # SURVEY 8(d)'s "fp32 parity mode": every fp32 product to ~2^-22 (5e-6 on pixels), the same grade as an fp32 evaluation
+                out["value_fp32_parity"] = results["h3"]["value"]
+                out["value_fp32_parity_what"] = "patches/s of mode h3 (fp32-grade products: 5e-6 from an all-fp32 evaluation); f32 = exact fp32 MFMA"
+            out["modes"] = {m: {k: v for k, v in r.items()} for m, r in results.items()}
+            if world == 1 and not args.no_latency:
+                out["latency_batch1"] = latency_batch1(G, cfg, dev, geom, pos)
+            if world == 1 and not args.no_cpu:
+                out["cpu_baseline"] = cpu_baseline(cfg, sd, seconds_budget=args.cpu_seconds, gens=gens, dev=dev)
+                for m, pr in out["cpu_baseline"].pop("parity_by_mode", {}).items():
+                    out["modes"][m]["parity"] = pr
+                out["cpu_baseline"]["parity"] = out["modes"][args.conv_mode].get("parity")
         # The full record (calibration tables, per-layer times, every explanatory string: ~20 KB) goes to a FILE; stdout gets ONE
         # compact line (< 4 KB) with the contract's keys -- the driver keeps only the last 8 KB of stdout, and a 20 KB line
         # left its round-4 record unparseable.
@@ -981,7 +1015,8 @@ def main():
         if dumped is not None:
             files = dump_outputs(args.dump_outputs, dumped)
             print(f"[bench] outputs of the last timed step ({args.conv_mode}) written to {args.dump_outputs}: {files}", file=sys.stderr, flush=True)
-    sampler.__exit__(None, None, None)
+    if sampler is not None:
+        sampler.__exit__(None, None, None)
     if use_pg:
         dist.barrier()
         dist.destroy_process_group()

@@ -117,3 +117,34 @@ def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
     idx = np.load(tmp_path / "a" / "rgba_u8_index.npy")
     assert idx.dtype == np.float64 and list(idx) == sorted(set(idx)) and np.array_equal(idx, np.load(tmp_path / "b" / "rgba_u8_index.npy"))
     assert np.array_equal(np.load(tmp_path / "a" / "rgba_u8.npy"), tiles[idx.astype(int)])
+
+
+def test_full_is_off_by_default_and_other_modes_need_it():
+    """A plain run measures the headline figure alone; what else the benchmark measures -- other arithmetic modes among it -- is behind
+    --full, and a plain run asked for other modes fails at once instead of ignoring the request."""
+    import pytest
+    b = _bench()
+    assert b.parse_args([]).full is False
+    assert b.parse_args(["--full"]).full is True
+    assert b.parse_args(["--modes", "primary"]).modes == "primary"
+    assert b.parse_args(["--full", "--modes", "f8,h3"]).modes == "f8,h3"
+    with pytest.raises(SystemExit) as e:
+        b.parse_args(["--modes", "f8,h3"])
+    assert e.value.code == 2
+
+
+def test_compact_line_of_a_plain_record():
+    """The record of a plain run has none of the --full figures: its compact line carries the contract's keys and nothing made up for
+    the figures it lacks."""
+    b = _bench()
+    full = json.load(open(os.path.join(REPO, "profiles", "r04_bench.json")))
+    only_full = ("roofline", "box_calibration", "telemetry", "modes", "value_single_stream", "single_stream", "value_fp32_parity",
+                 "value_fp32_parity_what", "latency_batch1", "cpu_baseline")
+    plain = {k: v for k, v in full.items() if k not in only_full}
+    c = b.compact_line(copy.deepcopy(plain))
+    out = json.loads(b.fit_line(c))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config"):
+        assert k in out, k
+    assert out["value"] == full["value"] and out["ms_per_step"] == full["ms_per_step"] and "dropped" not in out
+    assert not set(out) & set(only_full + ("parity",)), sorted(set(out) & set(only_full))

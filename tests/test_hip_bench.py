@@ -1,7 +1,8 @@
 """bench.py's N>1 control flow on a one-GPU box: `python bench.py --gpus 2` must launch its two ranks itself (child
 torchrun, one process per rank), gather the RGBA tiles inside the step and print ONE JSON line with n_gpus = 2.
 Both ranks share device 0 and the collective backend is gloo (RCCL refuses two ranks on one device); the numbers of
-such a run mean nothing -- the test is about the launch path the driver's `--gpus N` run takes."""
+such a run mean nothing -- the test is about the launch path the driver's `--gpus N` run takes.
+A plain run measures the headline figure alone; the tests that read what else the benchmark measures run it with --full."""
 import json
 import os
 import subprocess
@@ -16,9 +17,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMPACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
                 "data", "config", "roofline", "box_calibration", "modes", "detail_file")
 ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "launches_per_step", "flops_per_launch")
+# what only a --full run measures: never in the line or the record of a plain run
+FULL_ONLY_KEYS = ("roofline", "box_calibration", "telemetry", "modes", "value_single_stream", "single_stream", "value_fp32_parity",
+                  "latency_batch1", "cpu_baseline", "parity")
 
 
-def _last_line(stdout):
+def _last_line(stdout, full=True):
     """The driver keeps the last 8 KB of stdout and parses its last line: that line must be small and complete."""
     lines = [l for l in stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, stdout[-2000:]
@@ -26,9 +30,13 @@ def _last_line(stdout):
     assert len(lines[0]) < 4096, len(lines[0])
     out = json.loads(lines[0])
     for k in COMPACT_KEYS:
-        assert k in out, k
-    for k in ROOFLINE_KEYS:
-        assert k in out["roofline"], k
+        if full or k not in FULL_ONLY_KEYS:
+            assert k in out, k
+    if full:
+        for k in ROOFLINE_KEYS:
+            assert k in out["roofline"], k
+    else:
+        assert not set(out) & set(FULL_ONLY_KEYS), sorted(set(out) & set(FULL_ONLY_KEYS))
     assert set(out["config"]) >= {"workload", "batch_per_gpu", "resolution"} and "model" not in out["config"]
     return out
 
@@ -46,7 +54,7 @@ def _run(args, extra_env=None, timeout=600):
 
 
 def test_bench_self_spawns_two_ranks():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "128", "--batch", "16", "--no-cpu", "--no-latency"],
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "128", "--batch", "16", "--full", "--no-cpu", "--no-latency"],
              {"NB_BENCH_SHARE_GPU": "1", "NB_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_line(r.stdout)
@@ -67,7 +75,7 @@ def test_bench_self_spawns_two_ranks():
 def test_bench_single_schedule_and_f6_on_request():
     """`--schedule single` is the one-stream loop alone (what the A/B tools and the profiler passes run); `--modes f6` still
     measures the round-5 experiment when asked."""
-    r = _run(["--steps", "2", "--warmup", "1", "--res", "128", "--batch", "8", "--no-latency", "--no-cpu", "--schedule", "single",
+    r = _run(["--steps", "2", "--warmup", "1", "--res", "128", "--batch", "8", "--full", "--no-latency", "--no-cpu", "--schedule", "single",
               "--modes", "f8,f6"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_line(r.stdout)
@@ -76,10 +84,10 @@ def test_bench_single_schedule_and_f6_on_request():
 
 
 def test_bench_line_carries_every_arithmetic_mode():
-    """The driver's command (N=1) reports all three arithmetic modes in ONE line: each with its own value, dominant-kernel
+    """`--full` (N=1) reports all three arithmetic modes in ONE line: each with its own value, dominant-kernel
     roofline against the peak of the type it multiplies in, and a live parity figure against the fp32 CPU oracle; the label of
     a split mode never claims "f32"."""
-    r = _run(["--steps", "2", "--warmup", "1", "--res", "128", "--batch", "8", "--no-latency", "--cpu-seconds", "1"])
+    r = _run(["--steps", "2", "--warmup", "1", "--res", "128", "--batch", "8", "--full", "--no-latency", "--cpu-seconds", "1"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_line(r.stdout)
     # (f6, the round-5 experiment: only with --modes f6 / all; f16 = the reference's shipped precision, a timing data point)
@@ -143,19 +151,44 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     and `--steps` sets the timed steps.  The tiles are the ones Generator.render_triad gives for the seeded weights and inputs of
     bench.py (rank 0), bit for bit."""
     import numpy as np
-    import torch
-    from brushstroke_engine_amd import config as cfgmod, synthetic, weights as wmod
-    from brushstroke_engine_amd.networks import Generator
-    r = _run(["--steps", "3", "--warmup", "1", "--res", "128", "--batch", "8", "--no-latency", "--no-cpu", "--modes", "primary",
+    r = _run(["--steps", "3", "--warmup", "1", "--res", "128", "--batch", "8", "--full", "--no-latency", "--no-cpu", "--modes", "primary",
               "--dump-outputs", str(tmp_path)])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_line(r.stdout)
     assert out["steps"] == 3 and out["ms_per_step"] > 0
     got = np.load(tmp_path / "rgba_u8.npy")
     assert got.dtype == np.float32 and got.shape == (8, 128, 128, 4) and os.listdir(tmp_path) == ["rgba_u8.npy"]
-    cfg, dev = cfgmod.style1_config(128), torch.device("cuda:0")
-    G = Generator(cfg, wmod.random_state_dict(cfg, seed=0), conv_mode=out["conv_mode"]).to(dev)
-    u8 = G.render_triad(z=torch.from_numpy(synthetic.batch_z(cfg, 8, first_seed=0)).to(dev).to(torch.float32),
-                        geom_feature=[torch.from_numpy(g).to(dev) for g in synthetic.geom_features(cfg, 8, seed=0)],
-                        positions=torch.from_numpy(synthetic.positions(cfg, 8, seed=0)).to(dev), render_mode="clear")[0]
-    assert np.array_equal(got, u8.cpu().numpy().astype(np.float32))
+    assert np.array_equal(got, _rendered_tiles(out["conv_mode"], 128, 8))
+
+
+def test_plain_run_measures_the_headline_alone(tmp_path):
+    """Without --full the run sets up, warms up, times the K steps on the library's throughput schedule and prints the line: the
+    contract's keys, none of the figures of a --full run (in the line or in the detail record), and --dump-outputs writes the
+    same tiles as Generator.render_triad gives for bench.py's seeded weights and inputs (rank 0), bit for bit."""
+    import numpy as np
+    r = _run(["--steps", "3", "--warmup", "1", "--res", "128", "--batch", "8", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _last_line(r.stdout, full=False)
+    assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["higher_is_better"] is True and out["conv_mode"] == "f8" and not out["dtype"].startswith("f32")
+    assert abs(out["value"] - 8 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert out["streams"] in (1, 3)
+    detail = _detail(out)
+    assert not set(detail) & set(FULL_ONLY_KEYS), sorted(set(detail) & set(FULL_ONLY_KEYS))
+    assert "in flight" in detail["schedule"] and detail["value"] == out["value"]
+    got = np.load(tmp_path / "rgba_u8.npy")
+    assert got.dtype == np.float32 and got.shape == (8, 128, 128, 4) and os.listdir(tmp_path) == ["rgba_u8.npy"]
+    assert np.array_equal(got, _rendered_tiles(out["conv_mode"], 128, 8))
+
+
+def _rendered_tiles(conv_mode, res, batch):
+    """The uint8 RGBA tiles of bench.py's rank-0 batch (seeded weights and inputs) through Generator.render_triad, as float32."""
+    import torch
+    from brushstroke_engine_amd import config as cfgmod, synthetic, weights as wmod
+    from brushstroke_engine_amd.networks import Generator
+    cfg, dev = cfgmod.style1_config(res), torch.device("cuda:0")
+    G = Generator(cfg, wmod.random_state_dict(cfg, seed=0), conv_mode=conv_mode).to(dev)
+    u8 = G.render_triad(z=torch.from_numpy(synthetic.batch_z(cfg, batch, first_seed=0)).to(dev).to(torch.float32),
+                        geom_feature=[torch.from_numpy(g).to(dev) for g in synthetic.geom_features(cfg, batch, seed=0)],
+                        positions=torch.from_numpy(synthetic.positions(cfg, batch, seed=0)).to(dev), render_mode="clear")[0]
+    return u8.cpu().numpy().astype("float32")

@@ -54,7 +54,7 @@ def test_bench_through_rccl_at_world_size_1(launcher):
     """bench.py under `torchrun --nproc-per-node=1` (what the driver's launcher looks like to a rank) and as plain `python bench.py`
     (the rendezvous variables are filled in): process group over RCCL, gather pre-flight, fabric report (all_gather_object), the
     tile gather inside every step of BOTH timed legs from the stream that rendered the tiles, barriers and MAX / SUM reductions."""
-    args = ["--steps", "3", "--warmup", "1", "--res", "128", "--batch", "16", "--no-cpu", "--no-latency", "--modes", "primary"]
+    args = ["--steps", "3", "--warmup", "1", "--res", "128", "--batch", "16", "--full", "--no-cpu", "--no-latency", "--modes", "primary"]
     if launcher == "torchrun":
         r = _torchrun(os.path.join(REPO, "bench.py"), args)
     else:
@@ -68,6 +68,20 @@ def test_bench_through_rccl_at_world_size_1(launcher):
     # >= one wait per timed step: the gather of a step is waited for when its stream's next step has been enqueued (and at the end)
     assert out["gather_wait_ms"]["waits"] >= 3 and out["gather_wait_ms"]["stream_ms_per_step"] is not None
     assert out["value"] > 0 and out["value_single_stream"] > 0 and out["roofline"]["frac"] > 0
+
+
+def test_plain_bench_through_rccl_at_world_size_1():
+    """A plain bench.py run (no --full) through RCCL at world size 1: the headline leg alone, with the gather inside every step, the
+    barriers and reductions around its timed region and the fabric report -- and none of the --full legs."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--res", "128", "--batch", "16"],
+                       env=_env(), cwd=REPO, capture_output=True, text=True, timeout=900)
+    out = _one_line(r)
+    _check_rccl(out["rccl"])
+    assert out["n_gpus"] == 1 and out["rccl"]["ranks_seen"] == [0] and "RCCL gather of RGBA tiles to rank 0" in out["config"]["parallelism"]
+    assert len(out["ms_per_step_per_rank"]) == 1 and out["ms_per_step_per_rank"][0] > 0
+    assert out["gather_wait_ms"]["waits"] >= 3 and out["gather_wait_ms"]["stream_ms_per_step"] is not None
+    assert out["value"] > 0 and out["streams"] in (1, 3)
+    assert not {"roofline", "value_single_stream", "box_calibration", "modes"} & set(out)
 
 
 @pytest.mark.parametrize("level", [2, 0])

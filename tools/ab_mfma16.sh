@@ -13,7 +13,7 @@ for i in 1 2 3; do
     echo "=== pair $i: $lib"
     NB_FMTS=1 python tools/bench_f6_layers.py 2>&1 | grep "^up"
     NB_PHASE_FMT=1 NB_PHASE_H2OUT=1 python tools/phase_times.py 2>&1 | grep -E "^up|k-loop|prologue|epilogue|inside the k-loop"
-    python bench.py --full-line --schedule single --modes primary --no-cpu --no-latency 2>/dev/null | python -c "
+    python bench.py --full --full-line --schedule single --modes primary --no-cpu --no-latency 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 t = d.get('telemetry') or {}

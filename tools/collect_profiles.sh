@@ -9,23 +9,23 @@ cd /tmp && export TMPDIR=/tmp
 # very end, when the counter passes have written the traffic file for THESE kernel sources (a bench.py run right after the
 # rocprofv3 --pmc passes measured its auxiliary three-streams leg 19 % low, twice: the counters leave the clocks in a state of
 # their own for a while)
-(cd /tmp && python3 $R/bench.py --detail $O/bench_pre_detail.json > $O/bench_pre.json 2> $O/bench_pre.err)
-python3 $R/bench.py --res 128 --no-cpu --modes primary --detail $O/bench_r128_f8_detail.json > $O/bench_r128_f8.json 2> $O/bench_r128.err
+(cd /tmp && python3 $R/bench.py --full --detail $O/bench_pre_detail.json > $O/bench_pre.json 2> $O/bench_pre.err)
+python3 $R/bench.py --full --res 128 --no-cpu --modes primary --detail $O/bench_r128_f8_detail.json > $O/bench_r128_f8.json 2> $O/bench_r128.err
 # per-kernel averages of the same command (timing pass: kernel trace + stats only), per mode
 for m in f8 h3 f32; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$m -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --no-latency --schedule single --modes primary --conv-mode $m > $O/stats_$m.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$m -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu --no-latency --schedule single --modes primary --conv-mode $m > $O/stats_$m.log 2>&1
   cp $(ls $O/stats_$m/*/*kernel_stats.csv | head -1) $O/kernel_stats_$m.csv 2>/dev/null
 done
 # counters: each group in its own pass, with the kernel trace only; memory counters per mode, MFMA-busy for the split modes
 for m in f8 h3 f32; do
   for c in "hit:TCC_HIT_sum TCC_MISS_sum" "fetch:FETCH_SIZE" "write:WRITE_SIZE"; do
     n=${c%%:*}
-    rocprofv3 --kernel-trace --pmc ${c#*:} --output-format csv -d $O/pmc_${n}_$m -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-latency --schedule single --modes primary --conv-mode $m > $O/pmc_${n}_$m.log 2>&1
+    rocprofv3 --kernel-trace --pmc ${c#*:} --output-format csv -d $O/pmc_${n}_$m -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-latency --schedule single --modes primary --conv-mode $m > $O/pmc_${n}_$m.log 2>&1
   done
   (cd $R && python tools/pmc_mem_summary.py $O/pmc_hit_$m $O/pmc_fetch_$m $O/pmc_write_$m $O/pmc_mem_$m.json > $O/pmc_mem_$m.txt 2>&1)
 done
 for m in f8 h3; do
-  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_$m -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-latency --schedule single --modes primary --conv-mode $m > $O/pmc_mfma_$m.log 2>&1
+  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma_$m -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-latency --schedule single --modes primary --conv-mode $m > $O/pmc_mfma_$m.log 2>&1
   (cd $R && python tools/pmc_summary.py $O/pmc_mfma_$m > $O/pmc_mfma_busy_$m.txt 2>&1)
 done
 cd $R
@@ -46,7 +46,7 @@ python tools/ab_noise_in_kernel.py 2>/dev/null | grep "noise images" > $O/ab_noi
 PAIRS=2 bash tools/ab_env.sh NB_STAGGER=200 > $O/ab_stagger.txt 2>&1
 python tools/stress_persistent.py > $O/stress_persistent.txt 2>&1           # race hunt: 2 400 persistent launches against the one-workgroup-per-tile results
 # the N > 1 code through RCCL at world size 1 (NB_FORCE_PG=1): bench.py, the lamali canvas, the training step
-NB_FORCE_PG=1 python bench.py --modes primary --no-cpu --no-latency --detail $O/rccl_world1_bench_detail.json > $O/rccl_world1_bench.json 2> $O/rccl_world1_bench.err
+NB_FORCE_PG=1 python bench.py --full --modes primary --no-cpu --no-latency --detail $O/rccl_world1_bench_detail.json > $O/rccl_world1_bench.json 2> $O/rccl_world1_bench.err
 NB_FORCE_PG=1 python tools/bench_lamali.py --steps 3 2> $O/rccl_world1_lamali.err | grep "^{" > $O/rccl_world1_lamali.json
 NB_FORCE_PG=1 python tools/bench_train.py --iters 8 --warmup 2 2> $O/rccl_world1_train.err | grep "^{" > $O/rccl_world1_train.json
 bash $R/tools/microbench/run_all.sh > $O/microbench.txt 2>&1
@@ -69,6 +69,6 @@ NB_BENCH_SHARE_GPU=1 NB_BENCH_BACKEND=gloo python tools/bench_lamali.py --gpus 2
 python tools/bench_train.py > $O/train_bench.json 2> $O/train_bench.err
 bash tools/trace_train.sh 400 > /dev/null 2>&1; head -70 gpurun_out/train_trace_summary.txt > $O/train_trace.txt; python tools/trace_train_agg.py > $O/train_trace_by_kernel.txt 2>&1
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
-(cd /tmp && python3 $R/bench.py --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err)
+(cd /tmp && python3 $R/bench.py --full --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err)
 rm -rf $O/stats_* $O/pmc_hit_* $O/pmc_fetch_* $O/pmc_write_* $O/pmc_mfma_f8 $O/pmc_mfma_h3
 ls $O; tail -c 400 $O/bench.json; tail -2 $O/smoke.txt

@@ -38,7 +38,7 @@ for arg in sys.argv[3:]:
 out = {"modes": modes,
        "_stamp": {"source_digest": build.source_digest(), "git_head": head,
                   "what": "per arithmetic mode and kernel: launch-count-weighted mean of (2 x FETCH_SIZE + WRITE_SIZE) per launch over "
-                          "separate rocprofv3 --pmc passes of `bench.py --modes primary --conv-mode <mode> --steps 2` (batch 32 at R=256 "
+                          "separate rocprofv3 --pmc passes of `bench.py --full --modes primary --conv-mode <mode> --steps 2` (batch 32 at R=256 "
                           "runs as one chain: every launch carries the whole batch of 32 patches)",
                   "per_grid": per_grid}}
 json.dump(out, open(dst, "w"), indent=1)
