@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _lock = threading.Lock()
 _lib = None
@@ -131,6 +131,12 @@ PROTOTYPES = {
     "nb_generator_destroy": (C.c_int, [vp]),
     "nb_generator_forward": (C.c_int, [vp, vp, vp, C.c_int, vp]),
     "nb_generator_describe": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
+    # the geometry encoder behind the generator handle
+    "nb_encoder_param_count": (C.c_int, []),
+    "nb_encoder_param_info": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "nb_generator_encoder_check": (C.c_int, [vp, C.c_int]),
+    "nb_generator_attach_encoder": (C.c_int, [vp, vp, C.c_int, vp]),
+    "nb_generator_forward_geom": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -219,6 +225,7 @@ NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3
 NB_CONV_MODES = {"f32": 0, "h3": 1, "f8": 2, "f6": 3, "f16": 4}
 NB_NOISE_MODES = {"const": 0, "none": 1, "random": 2}
 NB_RENDER_MODES = {"clear": 0, "full": 1}
+NB_GEOM_PREPROC = {None: 0, "none": 0, "-11inverse": 1, "inverse": 2}      # encoder.HipGeometryEncoder's preproc_type strings
 
 
 class NeubeHipError(RuntimeError):

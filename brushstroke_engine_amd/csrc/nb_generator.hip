@@ -9,6 +9,7 @@
 #include "nb_h3_common.h"
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -130,13 +131,32 @@ extern "C" int nb_pack_conv_weight_dev(const float* w, int c_out, int c_in, floa
     return NB_OK;
 }
 
-extern "C" int nb_pack_conv_weight_h3f8_dev(const float* w, int c_out, int c_in, void* out, void* stream) {
-    NB_REQUIRE(w && out && c_out > 0 && c_in > 0 && (uintptr_t)out % 16 == 0, "pack_conv_weight_h3f8_dev: bad arguments");
-    const int nch = (c_in + 15) / 16, co_ld = (c_out + 63) / 64 * 64;
-    hipLaunchKernelGGL(gen_pack_h3f8_kernel, dim3(nb_cdiv(nch * 18 * co_ld, 256)), dim3(256), 0, (hipStream_t)stream, w, c_out, c_in, co_ld,
-                       nch, (uint4*)out);
+// the f8 weight format with c_out padded to co_align (64: the generator's modconv kernels, 128: the encoder's conv kernels)
+static int pack_h3f8(const float* w, int c_out, int c_in, int co_align, void* out, hipStream_t st) {
+    const int nch = (c_in + 15) / 16, co_ld = (c_out + co_align - 1) / co_align * co_align;
+    hipLaunchKernelGGL(gen_pack_h3f8_kernel, dim3(nb_cdiv(nch * 18 * co_ld, 256)), dim3(256), 0, st, w, c_out, c_in, co_ld, nch, (uint4*)out);
     NB_CHECK_LAUNCH("pack_conv_weight_h3f8_dev");
     return NB_OK;
+}
+
+extern "C" int nb_pack_conv_weight_h3f8_dev(const float* w, int c_out, int c_in, void* out, void* stream) {
+    NB_REQUIRE(w && out && c_out > 0 && c_in > 0 && (uintptr_t)out % 16 == 0, "pack_conv_weight_h3f8_dev: bad arguments");
+    return pack_h3f8(w, c_out, c_in, 64, out, (hipStream_t)stream);
+}
+
+// The geometry encoder's conv + eval BatchNorm fold (encoder._fold_bn): s = gamma / sqrt(var + 1e-5), w' = w s, b' = (b - mean) s + beta,
+// in float64 and rounded to fp32 as the numpy does.  w' [c_out][per] goes to rows of `ld` floats, zero padded (the stem's w50: per 49,
+// ld 50).
+__global__ __launch_bounds__(256) void enc_fold_bn_kernel(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, const float* __restrict__ mean,
+                                                          const float* __restrict__ var, int c_out, int per, int ld, float* __restrict__ w_out,
+                                                          float* __restrict__ b_out) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= c_out * ld) return;
+    const int co = idx / ld, j = idx % ld;
+    const double s = (double)gamma[co] / sqrt((double)var[co] + 1e-5);
+    w_out[idx] = j < per ? (float)((double)w[(size_t)co * per + j] * s) : 0.f;
+    if (j == 0) b_out[co] = (float)(((double)b[co] - (double)mean[co]) * s + (double)beta[co]);
 }
 
 extern "C" int nb_pack_conv_weight_h3_up2_dev(const float* w, const float* resample_filter, int c_out, int c_in, void* out, void* stream) {
@@ -531,6 +551,18 @@ struct NbGenerator {
     // workspace sizes (bytes) found by the sizing walk
     size_t need_act = 0, need_h2 = 0;
     std::vector<size_t> need_pre;
+    // the geometry encoder (nb_generator_attach_encoder): folded and packed weights, workspaces for every batch up to n_max
+    struct Encoder {
+        int preproc = -1;                           // NB_GEOM_PREPROC_*; < 0: none attached
+        float *w50 = nullptr, *b0 = nullptr;        // the stem: [64][50] folded weights, bias
+        void* w_h3[6] = {};                         // the six 3x3 layers: hi/lo f16 weights, f8 weights (f8 generators), bias
+        void* w_f8[6] = {};
+        float* b[6] = {};
+        void* ping[2] = {nullptr, nullptr};         // operand tensors between the layers (the decoder's fp32 output without hand-off)
+        float* feat0 = nullptr;                     // the fp32 bottleneck, feature 0
+        void* up = nullptr;                         // its bilinear x2 in operand format
+        std::vector<void*> allocs;
+    } enc;
 
     const NbLayerDesc* table(int first) const { return tables + (size_t)first * (L.size() + 1); }
     // the plan of a forward at batch n: constant noise shifted by integer positions, or none
@@ -558,9 +590,14 @@ struct WalkSink {
         }                                  \
     } while (0)
 
+// Runs between the styles and the early geometry packs (SynthesisNetwork._encode_lazy_geometry): fills the geometry inputs and sets
+// bit gi of *handed for every feature it wrote into its consumer's operand tensor itself.
+using GeomHook = std::function<int(const NbPassPlan&, unsigned* handed)>;
+
 // One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant or no noise, no taps / blending / resume),
 // following the pass's plan.
-int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, hipStream_t st, const WalkSink& sink) {
+int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, hipStream_t st, const WalkSink& sink,
+             const GeomHook* geom_hook = nullptr) {
     const GenCfg& cfg = g->cfg;
     const std::vector<GenLayer>& specs = cfg.layers;
     const int nL = (int)specs.size(), R = cfg.R, w_dim = cfg.c.w_dim;
@@ -613,11 +650,16 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         }
     }
 
+    // ---- geometry from stroke patches (_encode_lazy_geometry) ----
+    unsigned handed = 0;
+    if (geom_hook && sink.launch)
+        if (const int rc = (*geom_hook)(plan, &handed)) return rc;
+
     // ---- early geometry packs (_pack_geometry_early; in-line on the one stream) ----
     const int ng = (int)cfg.geom_res.size();
     for (int gi = 0; gi < ng; ++gi) {
         const NbGeomPlan& gp = plan.geom[gi];
-        if (!gp.early_pack) continue;
+        if (!gp.early_pack || ((handed >> gi) & 1)) continue;
         const int gres = cfg.geom_res[gi], gch = cfg.geom_ch[gi], ic = gp.consumer;
         const GenLayer& sc = specs[ic];
         if (sink.sizing) g->need_pre[gi] = std::max(g->need_pre[gi], h2_bytes(n, sc.in_ch, gres * gres));
@@ -752,9 +794,10 @@ void gen_free(NbGenerator* g) {
     if (!g) return;
     int prev = 0;
     const bool have = hipGetDevice(&prev) == hipSuccess;
-    if (!g->allocs.empty() && hipSetDevice(g->device) == hipSuccess) {
+    if ((!g->allocs.empty() || !g->enc.allocs.empty()) && hipSetDevice(g->device) == hipSuccess) {
         (void)hipDeviceSynchronize();
         for (void* p : g->allocs) (void)hipFree(p);
+        for (void* p : g->enc.allocs) (void)hipFree(p);
     }
     if (have) (void)hipSetDevice(prev);
     delete g;
@@ -951,25 +994,40 @@ extern "C" int nb_generator_create(const NbGeneratorConfig* cfg, const void* con
     return NB_OK;
 }
 
-extern "C" int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, void* stream) {
-    NB_REQUIRE(gen && in && out, "generator_forward: null pointer");
-    NB_REQUIRE(n >= 1 && n <= gen->n_max, "generator_forward: batch %d outside [1, n_max = %d]", n, gen->n_max);
-    NB_REQUIRE((in->z != nullptr) != (in->ws != nullptr), "generator_forward: pass exactly one of z / ws");
-    NB_REQUIRE(in->truncation_psi == 1.f || in->z, "generator_forward: truncation applies to z input only (ws input needs psi = 1)");
-    for (size_t k = 0; k < gen->cfg.geom_res.size(); ++k) NB_REQUIRE(in->geom[k], "generator_forward: geometry feature %d is NULL", (int)k);
+namespace {
+
+// the input rules of a forward pass (`who` prefixes the messages); the geometry features are checked by the caller
+int check_forward(NbGenerator* gen, const NbGeneratorInputs* in, int n, void* stream, const char* who) {
+    NB_REQUIRE(n >= 1 && n <= gen->n_max, "%s: batch %d outside [1, n_max = %d]", who, n, gen->n_max);
+    NB_REQUIRE((in->z != nullptr) != (in->ws != nullptr), "%s: pass exactly one of z / ws", who);
+    NB_REQUIRE(in->truncation_psi == 1.f || in->z, "%s: truncation applies to z input only (ws input needs psi = 1)", who);
+    return NB_OK;
+}
+
+int check_modes_and_device(NbGenerator* gen, const NbGeneratorInputs* in, void* stream, const char* who) {
     if (in->noise_mode != NB_NOISE_CONST && in->noise_mode != NB_NOISE_NONE) {
-        nb_set_error("generator_forward: noise_mode %d not supported (const and none are)", in->noise_mode);
+        nb_set_error("%s: noise_mode %d not supported (const and none are)", who, in->noise_mode);
         return in->noise_mode == NB_NOISE_RANDOM ? NB_EUNSUPPORTED : NB_EINVAL;
     }
-    NB_REQUIRE(in->render_mode == NB_RENDER_CLEAR || in->render_mode == NB_RENDER_FULL, "generator_forward: unknown render_mode %d", in->render_mode);
+    NB_REQUIRE(in->render_mode == NB_RENDER_CLEAR || in->render_mode == NB_RENDER_FULL, "%s: unknown render_mode %d", who, in->render_mode);
     int dev = -1;
-    NB_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev == gen->device, "generator_forward: current device %d is not the generator's (%d)", dev,
+    NB_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev == gen->device, "%s: current device %d is not the generator's (%d)", who, dev,
                gen->device);
     if (stream) {
         hipDevice_t sdev = -1;
         NB_REQUIRE(hipStreamGetDevice((hipStream_t)stream, &sdev) == hipSuccess && sdev == gen->device,
-                   "generator_forward: the stream belongs to device %d, the generator to %d", (int)sdev, gen->device);
+                   "%s: the stream belongs to device %d, the generator to %d", who, (int)sdev, gen->device);
     }
+    return NB_OK;
+}
+
+}  // namespace
+
+extern "C" int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, void* stream) {
+    NB_REQUIRE(gen && in && out, "generator_forward: null pointer");
+    if (const int rc = check_forward(gen, in, n, stream, "generator_forward")) return rc;
+    for (size_t k = 0; k < gen->cfg.geom_res.size(); ++k) NB_REQUIRE(in->geom[k], "generator_forward: geometry feature %d is NULL", (int)k);
+    if (const int rc = check_modes_and_device(gen, in, stream, "generator_forward")) return rc;
     WalkSink sink;
     sink.launch = true;
     return gen_walk(gen, in, out, n, (hipStream_t)stream, sink);
@@ -987,4 +1045,250 @@ extern "C" int nb_generator_describe(NbGenerator* gen, int n, char* buf, int len
     NB_REQUIRE(len > (int)s.size(), "generator_describe: buffer of %d bytes, %d needed", len, (int)s.size() + 1);
     memcpy(buf, s.c_str(), s.size() + 1);
     return NB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the geometry encoder behind the generator handle: stroke patches -> the two features (encoder.HipGeometryEncoder.encode, driven
+// as SynthesisNetwork._encode_lazy_geometry drives it)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct EncLayer {
+    const char* prefix;
+    int c_out, c_in, k, stride;
+};
+// the stem, then the six 3x3 layers of HipGeometryEncoder.convs: three stride-2 stages, 256 -> 32 -> 16 (the bottleneck) and the first
+// decoder stage (behind the bilinear x2)
+const EncLayer kEncLayers[7] = {{"encoder.model.0.conv", 64, 1, 7, 1},   {"encoder.model.1.conv", 128, 64, 3, 2},
+                                {"encoder.model.2.conv", 256, 128, 3, 2}, {"encoder.model.3.conv", 256, 256, 3, 2},
+                                {"encoder.model.4.conv", 32, 256, 3, 1},  {"encoder.model.5.conv", 16, 32, 3, 1},
+                                {"decoder.model.0.conv.conv", 256, 16, 3, 1}};
+constexpr int kEncParamsPerLayer = 6;             // conv weight, conv bias, BatchNorm weight, bias, running mean, running var
+
+std::vector<GenParam> enc_params() {
+    std::vector<GenParam> v;
+    GenCfg tmp;
+    for (const EncLayer& L : kEncLayers) {
+        const std::string p = L.prefix;
+        add_param(tmp, p + ".0.weight", {L.c_out, L.c_in, L.k, L.k});
+        add_param(tmp, p + ".0.bias", {L.c_out});
+        add_param(tmp, p + ".1.weight", {L.c_out});
+        add_param(tmp, p + ".1.bias", {L.c_out});
+        add_param(tmp, p + ".1.running_mean", {L.c_out});
+        add_param(tmp, p + ".1.running_var", {L.c_out});
+    }
+    return tmp.params;
+}
+
+// can an encoder be attached to a generator of this configuration?
+int enc_check(const GenCfg& g, int preproc, const char* who) {
+    const int R = g.R;
+    NB_REQUIRE(g.geom_res.size() == 2 && g.geom_ch[0] == 16 && g.geom_ch[1] == 256 && g.geom_res[0] == R / 8 && g.geom_res[1] == R / 4,
+               "%s: the generator's geometry layout is not the encoder's (two features: 16 channels at R/8, 256 at R/4)", who);
+    NB_REQUIRE(R == 32 || R == 64 || (R >= 128 && R % 128 == 0), "%s: patch size %d is not one the encoder tiles (32, 64 or a multiple of 128)",
+               who, R);
+    NB_REQUIRE(preproc >= NB_GEOM_PREPROC_NONE && preproc <= NB_GEOM_PREPROC_INVERSE, "%s: unknown preproc %d", who, preproc);
+    return NB_OK;
+}
+
+// Operand format between the encoder's layers at batch n (HipGeometryEncoder.encode with TileOps' rule arith = "f8" iff the generator
+// is f8): "f8" from batch 8 at patch sizes the large tiles cover, else H2 (the small-tile kernels of interactive strokes read H2)
+int enc_fmt(const NbGenerator* g, int n) {
+    const int R = g->cfg.R;
+    return g->opts.conv_mode == NB_CONV_F8 && n >= 8 && R >= 128 && R % 128 == 0;
+}
+
+// HipGeometryEncoder.encode on the handle's workspaces.  launch = false: record the largest ping-pong tensor in *need_ping only.
+// Otherwise io->geom[] receives the fp32 features, and feature 1 goes straight into its consumer's operand tensor (pre_h2[1], times
+// the consumer's styles) where the plan's encoder hand-off and the patch size allow it: bit 1 of *handed is then set.
+int enc_walk(NbGenerator* g, const float* x, int n, hipStream_t st, const NbPassPlan* plan, bool launch, size_t* need_ping,
+             NbGeneratorInputs* io, unsigned* handed) {
+    const NbGenerator::Encoder& E = g->enc;
+    const int R = g->cfg.R;
+    const float slope = 0.01f;
+    const int fmt = enc_fmt(g, n);
+    const bool fused = fmt && R % 64 == 0;          // stem + first stride-2 stage in one launch (NB_ENC_FUSE_STEM's default)
+    // the 3x3 layers with <= 32 outputs from >= 32 inputs run on the split-K tiles, which read H2: their producers write H2
+    auto narrow = [](int i) { return kEncLayers[i + 1].c_out <= 32 && kEncLayers[i + 1].c_in >= 32; };
+    auto W = [&](int i, int f) -> const void* { return f ? E.w_f8[i] : E.w_h3[i]; };
+    auto need = [&](size_t b) {
+        if (need_ping) *need_ping = std::max(*need_ping, b);
+    };
+#define ENC_TRY(call)                     \
+    do {                                  \
+        if (launch) {                     \
+            const int rc_ = (call);       \
+            if (rc_ != NB_OK) return rc_; \
+        }                                 \
+    } while (0)
+    int cur = 0, r = R;
+    if (fused) {
+        need(h2_bytes(n, kEncLayers[1].c_out, (R / 2) * (R / 2)));
+        ENC_TRY(nb_enc_stem_conv3x3_f8(x, E.w50, E.b0, E.preproc, W(0, 1), E.b[0], E.ping[0], narrow(1) ? 0 : fmt, n, R, R,
+                                       kEncLayers[1].c_out, slope, st));
+        r = R / 2;
+    } else {
+        need(h2_bytes(n, kEncLayers[0].c_out, R * R));
+        ENC_TRY(nb_enc_stem7x7_f32_h2_ex(x, E.w50, E.b0, E.ping[0], fmt, n, R, R, E.preproc, slope, st));
+    }
+    for (int i = fused ? 1 : 0; i < 4; ++i) {       // three stride-2 stages + 256 -> 32
+        const EncLayer& L = kEncLayers[i + 1];
+        const int ro = r / L.stride, fin = narrow(i) ? 0 : fmt, fout = narrow(i + 1) ? 0 : fmt;
+        need(h2_bytes(n, L.c_out, ro * ro));
+        ENC_TRY(nb_enc_conv3x3_ex(E.ping[cur], L.c_in, W(i, fin), E.b[i], nullptr, E.ping[cur ^ 1], nullptr, 0, fout ? L.c_out / 8 : 0, 0, fin,
+                                  fout, n, r, r, L.c_out, L.stride, slope, st));
+        cur ^= 1;
+        r = ro;
+    }
+    const EncLayer& B = kEncLayers[5];              // 32 -> 16: the bottleneck, feature 0 (fp32)
+    const int fin = narrow(4) ? 0 : fmt;
+    ENC_TRY(nb_enc_conv3x3_ex(E.ping[cur], B.c_in, W(4, fin), E.b[4], E.feat0, nullptr, nullptr, 0, 0, 0, fin, 0, n, r, r, B.c_out, 1, slope, st));
+    ENC_TRY(nb_enc_upsample2x_h2_ex(E.feat0, E.up, fmt, n, B.c_out, r, r, st));
+    const EncLayer& D = kEncLayers[6];              // the first decoder stage, 16 -> 256: feature 1
+    const int r1 = 2 * r;
+    need((size_t)n * D.c_out * r1 * r1 * sizeof(float));
+    if (!launch) return NB_OK;
+    io->geom[0] = E.feat0;
+    const NbGeomPlan& gp = plan->geom[1];
+    // the hand-off needs the large-tile epilogue (HipGeometryEncoder.can_handoff) and the consumer's operand tensor of the early pack
+    if (gp.encoder_handoff && gp.early_pack && (r1 % 32 == 0 || r1 == 16)) {
+        const GenLayer& sc = g->cfg.layers[gp.consumer];
+        const int c_prod = sc.in_ch - D.c_out;
+        ENC_TRY(nb_enc_conv3x3_ex(g->enc.up, D.c_in, W(5, fmt), E.b[5], nullptr, g->pre_h2[1], g->L[gp.consumer].styles + c_prod, sc.in_ch,
+                                  sc.in_ch / 8, c_prod / 8, fmt, gp.fmt, n, r1, r1, D.c_out, 1, slope, st));
+        io->geom[1] = nullptr;
+        *handed |= 2u;
+    } else {
+        float* dec = (float*)E.ping[cur ^ 1];
+        ENC_TRY(nb_enc_conv3x3_ex(E.up, D.c_in, W(5, fmt), E.b[5], dec, nullptr, nullptr, 0, 0, 0, fmt, 0, n, r1, r1, D.c_out, 1, slope, st));
+        io->geom[1] = dec;
+    }
+#undef ENC_TRY
+    return NB_OK;
+}
+
+void enc_free(NbGenerator* g) {
+    if (!g->enc.allocs.empty()) {
+        (void)hipDeviceSynchronize();
+        for (void* p : g->enc.allocs) (void)hipFree(p);
+    }
+    g->enc = NbGenerator::Encoder();
+}
+
+}  // namespace
+
+extern "C" int nb_encoder_param_count(void) { return (int)(sizeof(kEncLayers) / sizeof(kEncLayers[0])) * kEncParamsPerLayer; }
+
+extern "C" int nb_encoder_param_info(int i, char* name, int len, int64_t shape[4], int* ndim) {
+    const std::vector<GenParam> ps = enc_params();
+    NB_REQUIRE(i >= 0 && i < (int)ps.size(), "encoder: parameter index %d out of range [0, %d)", i, (int)ps.size());
+    const GenParam& p = ps[i];
+    if (shape) for (int k = 0; k < 4; ++k) shape[k] = p.shape[k];
+    if (ndim) *ndim = p.ndim;
+    return copy_name(p.name, name, len);
+}
+
+extern "C" int nb_generator_encoder_check(const NbGeneratorConfig* cfg, int preproc) {
+    GenCfg g;
+    const int rc = resolve_cfg(cfg, g);
+    return rc ? rc : enc_check(g, preproc, "encoder_check");
+}
+
+extern "C" int nb_generator_attach_encoder(NbGenerator* gen, const void* const* enc_params_dev, int preproc, void* stream) {
+    NB_REQUIRE(gen, "generator_attach_encoder: null generator");
+    if (const int rc = enc_check(gen->cfg, preproc, "generator_attach_encoder")) return rc;
+    NB_REQUIRE(enc_params_dev, "generator_attach_encoder: null parameter array");
+    const std::vector<GenParam> ps = enc_params();
+    for (size_t i = 0; i < ps.size(); ++i)
+        NB_REQUIRE(enc_params_dev[i], "generator_attach_encoder: parameter %d (%s) is NULL", (int)i, ps[i].name.c_str());
+    int dev = -1;
+    NB_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev == gen->device, "generator_attach_encoder: current device %d is not the generator's (%d)",
+               dev, gen->device);
+    hipStream_t st = (hipStream_t)stream;
+    enc_free(gen);                                   // (a second call replaces the first)
+    NbGenerator::Encoder& E = gen->enc;
+    std::vector<void*> temps;
+    bool ok = true;
+    auto alloc = [&](size_t bytes, std::vector<void*>& list) -> void* {
+        void* p = nullptr;
+        if (!ok || bytes == 0) return nullptr;
+        if (hipMalloc(&p, (bytes + 255) / 256 * 256) != hipSuccess) {
+            ok = false;
+            nb_set_error("generator_attach_encoder: hipMalloc of %zu bytes failed", bytes);
+            return nullptr;
+        }
+        list.push_back(p);
+        return p;
+    };
+    auto finish = [&](int code) {
+        (void)hipStreamSynchronize(st);
+        for (void* p : temps) (void)hipFree(p);
+        if (code != NB_OK) enc_free(gen);
+        return code;
+    };
+    const bool f8 = gen->opts.conv_mode == NB_CONV_F8;
+    const float* const* P = (const float* const*)enc_params_dev;
+    for (int l = 0; l < 7; ++l) {
+        const EncLayer& L = kEncLayers[l];
+        const float* const* p = P + l * kEncParamsPerLayer;       // weight, bias, gamma, beta, mean, var
+        const int per = L.c_in * L.k * L.k, ld = l == 0 ? 50 : per;
+        float* w = (float*)alloc((size_t)L.c_out * ld * sizeof(float), l == 0 ? E.allocs : temps);
+        float* b = (float*)alloc((size_t)L.c_out * sizeof(float), E.allocs);
+        if (!ok) return finish(NB_ELAUNCH);
+        hipLaunchKernelGGL(enc_fold_bn_kernel, dim3(nb_cdiv(L.c_out * ld, 256)), dim3(256), 0, st, p[0], p[1], p[2], p[3], p[4], p[5], L.c_out,
+                           per, ld, w, b);
+        if (hipGetLastError() != hipSuccess) {
+            nb_set_error("generator_attach_encoder: launch of the BatchNorm fold failed");
+            return finish(NB_ELAUNCH);
+        }
+        if (l == 0) {
+            E.w50 = w;
+            E.b0 = b;
+            continue;
+        }
+        // encoder.pack_enc_weight_h3 / pack_enc_weight_f8: the containers with c_out padded to 128
+        const size_t bytes = (size_t)(L.c_in + 15) / 16 * 9 * 4 * ((L.c_out + 127) / 128 * 128) * 8 * sizeof(_Float16);
+        E.b[l - 1] = b;
+        E.w_h3[l - 1] = alloc(bytes, E.allocs);
+        if (f8) E.w_f8[l - 1] = alloc(bytes, E.allocs);
+        if (!ok) return finish(NB_ELAUNCH);
+        int rc = nb_pack_conv_weight_h3_dev(w, L.c_out, L.c_in, 128, 0, E.w_h3[l - 1], st);
+        if (!rc && f8) rc = pack_h3f8(w, L.c_out, L.c_in, 128, E.w_f8[l - 1], st);
+        if (rc) return finish(rc);
+    }
+    // workspaces: the largest each gets at any batch up to n_max (below batch 8, and always for h3 / f32 generators, the stem writes the
+    // 64-channel full-resolution tensor that the fused f8 launch never creates)
+    size_t need_ping = 0;
+    for (int n = 1; n <= gen->n_max; ++n) enc_walk(gen, nullptr, n, st, nullptr, false, &need_ping, nullptr, nullptr);
+    const int R = gen->cfg.R;
+    E.ping[0] = alloc(need_ping, E.allocs);
+    E.ping[1] = alloc(need_ping, E.allocs);
+    E.feat0 = (float*)alloc((size_t)gen->n_max * 16 * (R / 8) * (R / 8) * sizeof(float), E.allocs);
+    E.up = alloc(h2_bytes(gen->n_max, 16, (R / 4) * (R / 4)), E.allocs);
+    if (!ok) return finish(NB_ELAUNCH);
+    if (hipStreamSynchronize(st) != hipSuccess) {
+        nb_set_error("generator_attach_encoder: %s", hipGetErrorString(hipGetLastError()));
+        return finish(NB_ELAUNCH);
+    }
+    E.preproc = preproc;
+    return finish(NB_OK);
+}
+
+extern "C" int nb_generator_forward_geom(NbGenerator* gen, const NbGeneratorInputs* in, const float* geom, const NbGeneratorOutputs* out,
+                                         int n, void* stream) {
+    NB_REQUIRE(gen && in && out, "generator_forward_geom: null pointer");
+    NB_REQUIRE(gen->enc.preproc >= 0, "generator_forward_geom: no encoder attached (nb_generator_attach_encoder)");
+    for (int k = 0; k < 4; ++k)
+        NB_REQUIRE(!in->geom[k], "generator_forward_geom: geometry feature %d given: the encoder computes them (pass stroke patches only)", k);
+    NB_REQUIRE(geom, "generator_forward_geom: null stroke patches");
+    if (const int rc = check_forward(gen, in, n, stream, "generator_forward_geom")) return rc;
+    if (const int rc = check_modes_and_device(gen, in, stream, "generator_forward_geom")) return rc;
+    NbGeneratorInputs io = *in;                      // the encoder fills io.geom[] before the walk reads them
+    hipStream_t st = (hipStream_t)stream;
+    const GeomHook hook = [&](const NbPassPlan& plan, unsigned* handed) {
+        return enc_walk(gen, geom, n, st, &plan, true, nullptr, &io, handed);
+    };
+    WalkSink sink;
+    sink.launch = true;
+    return gen_walk(gen, &io, out, n, st, sink, &hook);
 }

@@ -63,6 +63,20 @@ def layer_table(cfg: GeneratorConfig):
     return out, num_ws.value
 
 
+def encoder_param_table() -> List[tuple]:
+    """[(state-dict key, shape)] in the order nb_generator_attach_encoder takes the encoder parameters (encoder.ENCODER_STATE_SHAPES
+    without num_batches_tracked)."""
+    lib = _lib.lib()
+    count = lib.nb_encoder_param_count()
+    _lib.check(min(count, 0), "encoder_param_count")
+    out, name = [], ctypes.create_string_buffer(256)
+    shape, ndim = (ctypes.c_int64 * 4)(), ctypes.c_int()
+    for i in range(count):
+        _lib.check(lib.nb_encoder_param_info(i, name, 256, shape, ctypes.byref(ndim)), "encoder_param_info")
+        out.append((name.value.decode(), tuple(int(shape[k]) for k in range(ndim.value))))
+    return out
+
+
 class NativeGenerator:
     """One ``NbGenerator`` handle.  Build it with :meth:`from_state_dict` or :meth:`from_generator`."""
 
@@ -123,6 +137,25 @@ class NativeGenerator:
         _lib.check(_lib.lib().nb_generator_describe(self._h, n, buf, len(buf)), "generator_describe")
         return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
+    def attach_encoder(self, encoder_state_dict, preproc_type=None):
+        """Attach the geometry encoder (encoder.HipGeometryEncoder's weights and preproc_type strings): the forward then also takes
+        stroke patches (``geom=``).  The parameters are uploaded, folded and packed by the library and released."""
+        if preproc_type not in _lib.NB_GEOM_PREPROC:
+            raise RuntimeError(f'Unknown preprocessing type "{preproc_type}"')
+        tensors = []
+        for name, shape in encoder_param_table():
+            v = encoder_state_dict[name]
+            t = v if torch.is_tensor(v) else torch.from_numpy(np.array(v, dtype=np.float32))
+            t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+            tensors.append(t)
+        ptrs = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(_lib.lib().nb_generator_attach_encoder(self._h, ptrs, _lib.NB_GEOM_PREPROC[preproc_type], stream),
+                       "generator_attach_encoder")
+
     # ---- forward ----
     def _f32(self, t, shape, name):
         t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
@@ -131,10 +164,13 @@ class NativeGenerator:
         return t
 
     def forward_into(self, outputs: dict, n: int, z=None, ws=None, geom_feature: Sequence = (), positions=None, noise_mode="const",
-                     render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0, truncation_cutoff=None):
+                     render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0, truncation_cutoff=None, geom=None):
         """Enqueue one forward on the current stream into caller-allocated ``outputs`` (keys rgba_u8 / rgba / img / uvs / colors;
         missing = not wanted).  Inputs must already be device tensors of the right dtype and shape (nothing is converted here):
-        the form for graph capture."""
+        the form for graph capture.  ``geom``: stroke patches [n, 1, R, R] fp32 for the attached encoder, instead of
+        ``geom_feature``."""
+        if geom is not None and len(geom_feature):
+            raise ValueError("pass either geom (stroke patches) or geom_feature, not both")
         ins = _lib.NbGeneratorInputs()
         ins.z, ins.ws = _p(z), _p(ws)
         ins.truncation_psi = float(truncation_psi)
@@ -152,22 +188,35 @@ class NativeGenerator:
             setattr(outs, k, _p(outputs.get(k)))
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(_lib.lib().nb_generator_forward(self._h, ctypes.byref(ins), ctypes.byref(outs), n, stream), "generator_forward")
+            if geom is None:
+                _lib.check(_lib.lib().nb_generator_forward(self._h, ctypes.byref(ins), ctypes.byref(outs), n, stream), "generator_forward")
+            else:
+                _lib.check(_lib.lib().nb_generator_forward_geom(self._h, ctypes.byref(ins), _p(geom), ctypes.byref(outs), n, stream),
+                           "generator_forward_geom")
 
     def render_triad(self, z=None, ws=None, geom_feature=None, positions=None, render_mode="clear", user_colors=None, want_u8=True,
-                     want_f32=False, sfactor=None, noise_mode="const", truncation_psi=1.0, truncation_cutoff=None):
-        """Generator.render_triad through the C entry: (rgba_u8 [N,R,R,4] | None, rgba [N,4,R,R] | None, {uvs, colors, img})."""
+                     want_f32=False, sfactor=None, noise_mode="const", truncation_psi=1.0, truncation_cutoff=None, geom=None):
+        """Generator.render_triad through the C entry: (rgba_u8 [N,R,R,4] | None, rgba [N,4,R,R] | None, {uvs, colors, img}).
+        ``geom``: stroke patches [N, 1, R, R] (1 = background) for the attached encoder (:meth:`attach_encoder`), instead of the
+        encoded ``geom_feature``."""
         cfg, dev = self.cfg, self.device
         if (z is None) == (ws is None):
             raise ValueError("pass exactly one of z / ws")
         n = (z if z is not None else ws).shape[0]
         z = None if z is None else self._f32(z, [n, cfg.z_dim], "z")
         ws = None if ws is None else self._f32(ws, [n, cfg.num_ws, cfg.w_dim], "ws")
-        geom_feature = list(geom_feature) if isinstance(geom_feature, (list, tuple)) else [geom_feature]
-        if len(geom_feature) != len(cfg.geom_feature_channels):
-            raise ValueError(f"expected {len(cfg.geom_feature_channels)} geometry features, got {len(geom_feature)}")
-        geom = [self._f32(g, [n, c, r, r], f"geom_feature[{k}]")
-                for k, (g, c, r) in enumerate(zip(geom_feature, cfg.geom_feature_channels, cfg.geom_feature_resolutions))]
+        patches = None
+        if geom is not None:
+            if geom_feature is not None:
+                raise ValueError("pass either geom (stroke patches) or geom_feature, not both")
+            patches = self._f32(geom, [n, 1, cfg.img_resolution, cfg.img_resolution], "geom")
+            geom = []
+        else:
+            geom_feature = list(geom_feature) if isinstance(geom_feature, (list, tuple)) else [geom_feature]
+            if len(geom_feature) != len(cfg.geom_feature_channels):
+                raise ValueError(f"expected {len(cfg.geom_feature_channels)} geometry features, got {len(geom_feature)}")
+            geom = [self._f32(g, [n, c, r, r], f"geom_feature[{k}]")
+                    for k, (g, c, r) in enumerate(zip(geom_feature, cfg.geom_feature_channels, cfg.geom_feature_resolutions))]
         pos = None
         if positions is not None:
             pos = torch.as_tensor(positions, device=dev).to(torch.int64).contiguous()
@@ -187,10 +236,10 @@ class NativeGenerator:
         if want_f32:
             outs["rgba"] = torch.empty([n, 4, r, r], dtype=torch.float32, device=dev)
         self.forward_into(outs, n, z=z, ws=ws, geom_feature=geom, positions=pos, noise_mode=noise_mode, render_mode=render_mode,
-                          user_colors=user, sfactor=sfac, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
+                          user_colors=user, sfactor=sfac, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, geom=patches)
         # the inputs converted here are read by work enqueued on the current stream: keep them alive for it
         cur = torch.cuda.current_stream(dev)
-        for t in [z, ws, pos, user, sfac] + geom:
+        for t in [z, ws, pos, user, sfac, patches] + geom:
             if t is not None:
                 t.record_stream(cur)
         return outs.get("rgba_u8"), outs.get("rgba"), {"uvs": outs["uvs"], "colors": outs["colors"], "img": outs["img"]}

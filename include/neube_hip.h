@@ -625,6 +625,38 @@ int nb_generator_forward(NbGenerator* gen, const NbGeneratorInputs* in, const Nb
  * records), the ToRGB's line included: the last conv's kernel when it is fused there, else torgb_triad_kernel.  Host only. */
 int nb_generator_describe(NbGenerator* gen, int n, char* buf, int len);
 
+/* ---- the geometry encoder behind the generator handle: stroke patches -> RGBA in one chain ------------------------------------
+ * encoder.HipGeometryEncoder (AutoEncoder.encode(res=[0, 1]) of the reference's `sauto` encoder) attached to a generator whose
+ * geometry layout is the encoder's: two features, 16 channels at R/8 and 256 at R/4; R = 32, 64 or a multiple of 128.  The encoder's
+ * operand formats, fused stem and hand-off of feature 1 into its consumer's operand tensor are those of the package's Python pass on
+ * encoder.LazyGeometry (with TileOps' rule: f8 operands between the encoder's layers iff the generator is NB_CONV_F8), and so are the
+ * results, bit for bit. */
+
+/* Encoder parameters: the tensors AutoEncoder.encode(res=[0, 1]) reads, in encoder.ENCODER_STATE_SHAPES order without
+ * num_batches_tracked: encoder.model.{0..5}.conv.{0,1}.* and decoder.model.0.conv.conv.{0,1}.* (42 entries).  Host only. */
+int nb_encoder_param_count(void);
+int nb_encoder_param_info(int i, char* name, int len, int64_t shape[4], int* ndim);
+
+#define NB_GEOM_PREPROC_NONE       0   /* preproc_type None / "none" */
+#define NB_GEOM_PREPROC_M11INVERSE 1   /* "-11inverse": (1 - x) * 2 - 1 */
+#define NB_GEOM_PREPROC_INVERSE    2   /* "inverse": 1 - x */
+
+/* NB_OK if an encoder with this preproc can be attached to a generator of this configuration, else NB_EINVAL with a message.
+ * Host only (nb_generator_attach_encoder applies the same rules first). */
+int nb_generator_encoder_check(const NbGeneratorConfig* cfg, int preproc);
+
+/* Folds BatchNorm (float64, rounded to fp32), packs the weights on the device (hi/lo f16, and the f8 format for an NB_CONV_F8 generator),
+ * allocates the encoder workspaces for every batch up to the handle's n_max and synchronises `stream`: the caller may then free
+ * enc_params_dev (device fp32 tensors, shapes as nb_encoder_param_info).  A second call replaces the first. */
+int nb_generator_attach_encoder(NbGenerator* gen, const void* const* enc_params_dev, int preproc, void* stream);
+
+/* nb_generator_forward from stroke patches: geom [n, 1, R, R] fp32 (1 = background, what nb_geom_tiles_f32 writes); in->geom[] must
+ * all be NULL.  Mapping / styles / noise, the encoder, the synthesis layers and the fused ToRGB, enqueued as one chain on `stream`
+ * (no allocation): capturable into a hipGraph after one eager call at the batch size.  No encoder attached, a geometry feature given,
+ * NULL geom, or any input nb_generator_forward rejects: NB_EINVAL (NB_EUNSUPPORTED for random noise), nothing enqueued. */
+int nb_generator_forward_geom(NbGenerator* gen, const NbGeneratorInputs* in, const float* geom, const NbGeneratorOutputs* out, int n,
+                              void* stream);
+
 /* ---- the per-batch layer plan (host only: no HIP call, works without a GPU) ------------------------------------------------
  * Every kernel decision of one synthesis pass at batch n: which kernel each layer runs, its operand formats, the operand hand-off,
  * the fused ToRGB, in-kernel noise, the styles / noise launches and the early geometry packs.  The package's Python pass
