@@ -376,8 +376,9 @@ int plan_pass(const GenCfg& g, const NbPlanOptions& o, int n, NbPassPlan* p) {
 
     // ---- the pass ----
     const bool positional = o.noise_positions != NB_PLAN_POS_NONE;
-    bool styles_fast = o.styles_fast && g.c.w_dim % 16 == 0;      // (16-byte friendly shapes)
-    for (const GenLayer& s : g.layers) styles_fast = styles_fast && s.out_ch % 4 == 0;
+    // (16-byte friendly shapes; the squared styles of a layer fit in the fast kernel's LDS array, the ToRGB's c + 9 included)
+    bool styles_fast = o.styles_fast && g.c.w_dim % 16 == 0 && g.channels(g.R) + 9 <= NB_MAX_AFF;
+    for (const GenLayer& s : g.layers) styles_fast = styles_fast && s.out_ch % 4 == 0 && s.in_ch <= NB_MAX_AFF;
     p->styles_fast = styles_fast;
     // small batches: styles and per-sample noise in one launch (a launch costs more than either computes)
     p->styles_noise = styles_fast && positional && !o.noise_overrides && n <= 8;

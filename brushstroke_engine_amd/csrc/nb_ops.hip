@@ -469,7 +469,6 @@ extern "C" int nb_mapping_ws_f32(const float* z, const float* fc_w, const float*
 // per-layer styles (affine) + demodulation coefficients, all layers in one launch
 // grid = (n_layers, n); reference: networks.py:366 (affine), :59-62 (dcoefs), :458-460 (ToRGB split/scale)
 // ------------------------------------------------------------------------------------------------
-#define NB_MAX_AFF 1024
 __global__ __launch_bounds__(256) void styles_kernel(const NbLayerDesc* __restrict__ layers, const float* __restrict__ ws,
                                                      int num_ws, int w_dim) {
     __shared__ float wv[512];
@@ -486,20 +485,27 @@ __global__ __launch_bounds__(256) void styles_kernel(const NbLayerDesc* __restri
         acc += L.affine_b[c];
         if (c >= L.n_plain) acc *= L.style_scale;
         L.styles[(size_t)n * L.c_aff + c] = acc;
-        s2[c] = acc * acc;
+        if (c < NB_MAX_AFF) s2[c] = acc * acc;
     }
-    __syncthreads();
+    __syncthreads();                                                // (also orders the styles stores before the reads below)
     if (L.wsq) {
         const int c_in = L.c_aff - L.n_plain;
+        const int c_lds = min(c_in, NB_MAX_AFF - L.n_plain);         // squares in LDS; the rest from the styles just written
+        const float* srow = L.styles + (size_t)n * L.c_aff + L.n_plain;
         for (int o = t; o < L.c_out; o += 256) {
             float acc = 0.f;
-            for (int i = 0; i < c_in; ++i) acc += s2[L.n_plain + i] * L.wsq[(size_t)i * L.c_out + o];
+            int i = 0;
+            for (; i < c_lds; ++i) acc += s2[L.n_plain + i] * L.wsq[(size_t)i * L.c_out + o];
+            for (; i < c_in; ++i) {
+                const float s = srow[i];
+                acc += (s * s) * L.wsq[(size_t)i * L.c_out + o];
+            }
             L.dcoefs[(size_t)n * L.c_out + o] = rsqrtf(acc + 1e-8f);
         }
     }
 }
 
-// Latency-oriented variant (w_dim % 16 == 0, every c_out % 4 == 0; grid = (n_layers, n, NB_STY_PARTS)): four lanes share
+// Latency-oriented variant (w_dim % 16 == 0, every c_out % 4 == 0, every c_aff <= NB_MAX_AFF; grid = (n_layers, n, NB_STY_PARTS)): four lanes share
 // one affine output (16-byte loads of the weight row, two shuffles), and the demodulation sum of a layer is split over
 // NB_STY_PARTS workgroups (each recomputes the cheap affine and takes a slice of the c_out outputs) and, inside a
 // workgroup, over c_in slices whose partial sums meet in LDS - instead of one thread walking all c_in rows.

@@ -169,7 +169,8 @@ int nb_styles_f32(const NbLayerDesc* layers_dev, int n_layers, const float* ws, 
                   void* stream);
 
 /* Same results up to fp32 summation order, latency-oriented launch shape (the batch-1 step starts with it): needs
- * w_dim % 16 == 0, every layer's c_out % 4 == 0 and 16-byte aligned affine_w / wsq. */
+ * w_dim % 16 == 0, every layer's c_out % 4 == 0 and c_aff <= 1024 (the squared styles live in LDS; nb_styles_f32 takes
+ * any c_aff), and 16-byte aligned affine_w / wsq. */
 int nb_styles_fast_f32(const NbLayerDesc* layers_dev, int n_layers, const float* ws, int num_ws, int w_dim, int n,
                        void* stream);
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from _gen_configs import CONFIGS as GEN_CONFIGS
+from brushstroke_engine_amd import config as cfgmod
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -267,6 +268,45 @@ def test_gen_configs_vs_float64_oracle(dev, cid):
             assert max(e["uvs"], e["img"], e["tapped uvs"]) <= PIX[mode] and e["colors"] <= 1e-5, (cid, mode, n, e)
             assert e[f"features{half}"] <= ACT[mode], (cid, mode, n, e)
         print(f"[gen configs vs float64 {cid} {mode}] " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+
+
+# nets whose styles tables run past the 1024 squared styles the latency-oriented styles kernel keeps in LDS: a 1100-channel conv1
+# (R = 4: an up=2 layer of that width is refused by its conv kernel, c_in <= 1024) and a 1020-channel ToRGB (c_aff = 1020 + 9)
+WIDE_AFFINE = {
+    "conv1100": cfgmod.GeneratorConfig(z_dim=64, w_dim=64, img_resolution=4, channel_base=4400, channel_max=1100,
+                                       geom_feature_channels=()),
+    "torgb1029": cfgmod.GeneratorConfig(z_dim=64, w_dim=64, img_resolution=8, channel_base=8192, channel_max=1020,
+                                        geom_feature_channels=()),
+}
+
+
+@pytest.mark.parametrize("cid", list(WIDE_AFFINE))
+def test_wide_affine_vs_float64_oracle(dev, cid):
+    """c_aff > 1024 (f32 mode, n = 1 and 5) against ONE float64 oracle pass; the pass plans the plain styles kernel.  A conv0 whose
+    input (with a geometry feature) is wider than 1024 channels is refused by the up=2 convolution, with an error."""
+    from brushstroke_engine_amd import weights as wmod, synthetic
+    from brushstroke_engine_amd.networks import Generator
+    from oracle import neube_oracle as orc
+    cfg = WIDE_AFFINE[cid]
+    assert max([s.in_channels for s in cfg.layers] + [cfg.channels(cfg.img_resolution) + 9]) > 1024
+    sd = wmod.random_state_dict(cfg, seed=8)
+    z, gf, pos = synthetic.batch_z(cfg, 5, 31), synthetic.geom_features(cfg, 5, seed=31), synthetic.positions(cfg, 5, seed=31)
+    want_img, want = orc.OracleGenerator(cfg, sd, dtype=torch.float64)(z, None, gf, positions=pos, return_debug_data=True)
+    G = Generator(cfg, sd, conv_mode="f32").to(dev)
+    for n in (1, 5):
+        img, dbg = G(D(z[:n], dev), None, [D(g[:n], dev) for g in gf], positions=D(pos[:n], dev), return_debug_data=True,
+                     noise_mode="const")
+        e = {"uvs": err(dbg["uvs"], want["uvs"][:n]), "img": err(img, want_img[:n]), "colors": err(dbg["colors"], want["colors"][:n])}
+        print(f"[wide affine vs float64 {cid} n={n}] " + " ".join(f"{k} {v:.2e}" for k, v in e.items()))
+        assert max(e["uvs"], e["img"]) <= PIX["f32"] and e["colors"] <= 1e-5, (cid, n, e)
+        assert not G.synthesis.pass_plan(n).styles_fast
+    from brushstroke_engine_amd._lib import NeubeHipError
+    cfg = cfgmod.GeneratorConfig(z_dim=64, w_dim=64, img_resolution=16, channel_base=512, channel_max=32,
+                                 geom_feature_channels=(1100,), geom_feature_resolutions=(8,))
+    G = Generator(cfg, wmod.random_state_dict(cfg, seed=8), conv_mode="f32").to(dev)
+    z, gf = synthetic.batch_z(cfg, 1, 31), synthetic.geom_features(cfg, 1, seed=31)
+    with pytest.raises(NeubeHipError, match="exceeds 1024"):
+        G(D(z, dev), None, [D(g, dev) for g in gf], noise_mode="const")
 
 
 def test_baseline_size_properties(dev):

@@ -96,3 +96,21 @@ def test_plan_arguments_are_checked(library):
     o.conv_mode = 9
     assert library.nb_synthesis_plan(ctypes.byref(c), ctypes.byref(o), 1, ctypes.byref(p)) == _lib.NB_EINVAL
     assert b"conv_mode" in library.nb_last_error()
+
+
+def test_styles_fast_only_within_its_lds_array(library):
+    """nb_styles_fast_f32 keeps a layer's squared styles in a 1024-entry LDS array: a table with a c_aff past it (a conv0 with a
+    wide geometry feature, or a ToRGB of 1016+ channels: c + 9) is planned on nb_styles_f32, at every batch and mode."""
+    wide = [cfgmod.GeneratorConfig(z_dim=64, w_dim=64, img_resolution=16, channel_base=512, channel_max=32,
+                                   geom_feature_channels=(1100,), geom_feature_resolutions=(8,)),
+            cfgmod.GeneratorConfig(z_dim=64, w_dim=64, img_resolution=8, channel_base=8192, channel_max=1016,
+                                   geom_feature_channels=(8,), geom_feature_resolutions=(4,))]
+    edge = cfgmod.GeneratorConfig(z_dim=64, w_dim=64, img_resolution=16, channel_base=512, channel_max=32,
+                                  geom_feature_channels=(992,), geom_feature_resolutions=(8,))        # c_aff = 1024 exactly
+    for cfg, fast in [(c, False) for c in wide] + [(edge, True)]:
+        syn = SynthesisNetwork(cfg)
+        for mode in ALL:
+            syn.conv_mode = mode
+            for n in BATCHES:
+                kp = syn.pass_plan(n)
+                assert kp.styles_fast == fast and (fast or not kp.styles_noise), (cfg, mode, n)
