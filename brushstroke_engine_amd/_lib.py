@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _lock = threading.Lock()
 _lib = None
@@ -137,6 +137,12 @@ PROTOTYPES = {
     "nb_generator_encoder_check": (C.c_int, [vp, C.c_int]),
     "nb_generator_attach_encoder": (C.c_int, [vp, vp, C.c_int, vp]),
     "nb_generator_forward_geom": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
+    # staged passes (the generator split around the feature-canvas blend) and the canvas helpers of a C host
+    "nb_generator_forward_staged": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
+    "nb_generator_describe_staged": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
+    "nb_dirty_area_alpha_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
+    "nb_canvas_cells_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+    "nb_canvas_build_cells": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -188,6 +194,11 @@ class NbGeneratorInputs(C.Structure):
 class NbGeneratorOutputs(C.Structure):
     """``struct NbGeneratorOutputs``."""
     _fields_ = [("rgba_u8", vp), ("rgba", vp), ("img", vp), ("uvs", vp), ("colors", vp)]
+
+
+class NbGeneratorStage(C.Structure):
+    """``struct NbGeneratorStage``: one half of a pass split around the feature-canvas blend."""
+    _fields_ = [("stop_res", C.c_int32), ("resume_res", C.c_int32), ("features_out", vp), ("features_in", vp)]
 
 
 NB_PLAN_MAX_LAYERS = 24

@@ -6,6 +6,9 @@
 // one launch replays the whole tile sequence: every thread owns one feature-canvas pixel (x CG channels), keeps
 // the canvas value and mask bit in registers and walks the tiles that cover it in the reference's order.
 #include "nb_common.h"
+#include <cmath>
+#include <cstring>
+#include <vector>
 
 // ------------------------------------------------------------------------------------------------
 // geometry tiles: out[t,0,y,x] = 1 - (255 - g[ty+y, tx+x]) / 255
@@ -256,5 +259,93 @@ extern "C" int nb_paste_tiles_u8(const uint8_t* tiles, int t, int r, const int32
     hipLaunchKernelGGL(paste_tiles_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)tiles, r, dst_yx,
                        crop, (uint32_t*)canvas, h, w, cell_off, cell_tiles);
     NB_CHECK_LAUNCH("paste_tiles");
+    return NB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the blending template: PaintingHelper.generate_dirty_area_alpha (brush.py:159-187) for a dirty area that spans the whole tile --
+// 1 inside the rectangle [r0, r1)^2 (r0 = margin + crop, r1 = width - r0), outside it a linear fall-off of width `margin` over the
+// distance to the nearest edge (to the nearest corner in the corner regions).  The squared distances are small integers, exact in
+// fp32; the square root and the division are evaluated in float64 and rounded once (53 >= 2 * 24 + 2 bits: the correctly rounded
+// fp32 results, whatever the fp32 division / sqrt options of the build), the rest in fp32 in the reference's order.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dirty_area_alpha_kernel(float* __restrict__ alpha0, int width, int margin, int r0, int r1) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= width * width) return;
+    const int y = i / width, x = i - y * width;
+    const bool in_x = x >= r0 && x < r1, in_y = y >= r0 && y < r1;
+    float res = 1.f;
+    if (!(in_x && in_y)) {
+        const float fx = (float)x, fy = (float)y, a = (float)r0, b = (float)r1;
+        const float dx0 = (fx - a) * (fx - a), dx1 = (fx - b + 1.f) * (fx - b + 1.f);
+        const float dy0 = (fy - a) * (fy - a), dy1 = (fy - b + 1.f) * (fy - b + 1.f);
+        const float dx = fminf(dx0, dx1), dy = fminf(dy0, dy1);
+        const float d = in_x ? dy : in_y ? dx : dx + dy;
+        const float root = (float)sqrt((double)d);
+        const float q = (float)((double)root / (double)(float)margin);
+        res = 1.f - q;
+        if (res < 0.f) res = 0.f;
+    }
+    alpha0[i] = res;
+}
+
+extern "C" int nb_dirty_area_alpha_f32(float* alpha0_dev, int width, int margin, int crop, void* stream) {
+    NB_REQUIRE(alpha0_dev, "dirty_area_alpha: null pointer");
+    NB_REQUIRE(width >= 1 && width <= 16384 && margin > 0 && crop >= 0, "dirty_area_alpha: bad sizes (width %d, margin %d, crop %d)", width, margin,
+               crop);
+    const long long r0 = (long long)margin + crop, r1 = (long long)width - r0;
+    NB_REQUIRE(r0 < r1, "dirty_area_alpha: blend margin %d + crop margin %d leave no interior in a tile of %d", margin, crop, width);
+    hipLaunchKernelGGL(dirty_area_alpha_kernel, dim3(nb_cdiv(width * width, 256)), dim3(256), 0, (hipStream_t)stream, alpha0_dev, width, margin,
+                       (int)r0, (int)r1);
+    NB_CHECK_LAUNCH("dirty_area_alpha");
+    return NB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// cell lists (host only): the CSR list of the header's "Cells" paragraph for rectangles (y0, x0, y1, x1), end-exclusive, clipped
+// to the h x w grid -- painting.build_cells.  A list without entries is one zero, so that its device copy is never empty.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+template <class F>
+void for_each_cell(const int32_t* rects, int t, int h, int w, F&& f) {
+    const int ncx = nb_cdiv(w, NB_CELL_W);
+    for (int i = 0; i < t; ++i) {
+        const int y0 = rects[4 * i] > 0 ? rects[4 * i] : 0, x0 = rects[4 * i + 1] > 0 ? rects[4 * i + 1] : 0;
+        const int y1 = rects[4 * i + 2] < h ? rects[4 * i + 2] : h, x1 = rects[4 * i + 3] < w ? rects[4 * i + 3] : w;
+        if (y1 <= y0 || x1 <= x0) continue;
+        for (int cy = y0 / NB_CELL_H; cy <= (y1 - 1) / NB_CELL_H; ++cy)
+            for (int cx = x0 / NB_CELL_W; cx <= (x1 - 1) / NB_CELL_W; ++cx) f(cy * ncx + cx, i);
+    }
+}
+
+int check_cells(const int32_t* rects, int t, int h, int w, const char* who) {
+    NB_REQUIRE(t >= 0 && (rects || t == 0), "%s: null rectangles", who);
+    NB_REQUIRE(h >= 1 && w >= 1 && (long long)nb_cdiv(h, NB_CELL_H) * nb_cdiv(w, NB_CELL_W) < (1ll << 30), "%s: bad grid size %d x %d", who, h, w);
+    return NB_OK;
+}
+
+}  // namespace
+
+extern "C" int nb_canvas_cells_count(const int32_t* rects, int t, int h, int w) {
+    if (const int rc = check_cells(rects, t, h, w, "canvas_cells_count")) return rc;
+    long long count = 0;
+    for_each_cell(rects, t, h, w, [&](int, int) { ++count; });
+    NB_REQUIRE(count < (1ll << 31), "canvas_cells_count: %lld entries do not fit the 32-bit offsets", count);
+    return count > 0 ? (int)count : 1;
+}
+
+extern "C" int nb_canvas_build_cells(const int32_t* rects, int t, int h, int w, int32_t* cell_off, int32_t* cell_items) {
+    if (const int rc = check_cells(rects, t, h, w, "canvas_build_cells")) return rc;
+    NB_REQUIRE(cell_off && cell_items, "canvas_build_cells: null output");
+    const int count = nb_canvas_cells_count(rects, t, h, w);
+    if (count < 0) return count;
+    const int ncells = nb_cdiv(h, NB_CELL_H) * nb_cdiv(w, NB_CELL_W);
+    memset(cell_off, 0, sizeof(int32_t) * ((size_t)ncells + 1));
+    cell_items[0] = 0;
+    for_each_cell(rects, t, h, w, [&](int c, int) { ++cell_off[c + 1]; });
+    for (int c = 0; c < ncells; ++c) cell_off[c + 1] += cell_off[c];
+    std::vector<int32_t> fill(cell_off, cell_off + ncells);          // rectangles are visited in ascending order: so is every cell's list
+    for_each_cell(rects, t, h, w, [&](int c, int i) { cell_items[fill[c]++] = i; });
     return NB_OK;
 }

@@ -4,8 +4,9 @@
 //
 // The per-batch kernel decisions of a pass live in one place, the planner (nb_synthesis_plan): SynthesisNetwork and the walk below
 // both follow its plan.  The orchestration is a single walk (gen_walk) used two ways: to size the workspaces at creation (every
-// batch up to n_max) and to enqueue a forward pass.  It differs from SynthesisNetwork only in that the early geometry pack runs
-// in-line on the one stream instead of on a side stream (same kernel, same inputs: same bits).
+// batch up to n_max, whole passes and every stage) and to enqueue a forward pass -- whole, or one stage of the painting engine's
+// split (NbGeneratorStage: a head that stops after a block, a tail that resumes behind it).  It differs from SynthesisNetwork only in
+// that the early geometry pack runs in-line on the one stream instead of on a side stream (same kernel, same inputs: same bits).
 #include "nb_h3_common.h"
 #include <cmath>
 #include <cstring>
@@ -566,10 +567,13 @@ struct NbGenerator {
     } enc;
 
     const NbLayerDesc* table(int first) const { return tables + (size_t)first * (L.size() + 1); }
-    // the plan of a forward at batch n: constant noise shifted by integer positions, or none
-    int plan(int n, bool positional, NbPassPlan* p) const {
+    // the plan of a forward at batch n: constant noise shifted by integer positions, or none; a pass that stops after block
+    // stop_res taps that block's fp32 output, one that resumes starts after block resume_res (0 = a whole pass)
+    int plan(int n, bool positional, NbPassPlan* p, int stop_res = 0, int resume_res = 0) const {
         NbPlanOptions o = opts;
         o.noise_positions = positional ? NB_PLAN_POS_INT : NB_PLAN_POS_NONE;
+        o.tap_mask = stop_res ? 1 << __builtin_ctz(stop_res) : 0;
+        o.resume_res = resume_res;
         return plan_pass(cfg, o, n, p);
     }
 };
@@ -595,10 +599,12 @@ struct WalkSink {
 // bit gi of *handed for every feature it wrote into its consumer's operand tensor itself.
 using GeomHook = std::function<int(const NbPassPlan&, unsigned* handed)>;
 
-// One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant or no noise, no taps / blending / resume),
-// following the pass's plan.
+// One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant or no noise, no feature taps / blending),
+// following the pass's plan.  stage (validated by the caller) makes it one half of the painting engine's split: stop_res = the pass of
+// `_stop_after` (ends with block stop_res, whose last layer writes stage->features_out; no ToRGB), resume_res = the pass of `_resume`
+// (starts behind block resume_res from stage->features_in).
 int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutputs* out, int n, hipStream_t st, const WalkSink& sink,
-             const GeomHook* geom_hook = nullptr) {
+             const GeomHook* geom_hook = nullptr, const NbGeneratorStage* stage = nullptr) {
     const GenCfg& cfg = g->cfg;
     const std::vector<GenLayer>& specs = cfg.layers;
     const int nL = (int)specs.size(), R = cfg.R, w_dim = cfg.c.w_dim;
@@ -606,8 +612,11 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     const float alpha = 0.2f, gain = g->act_gain;
     const bool cnoise = in->noise_mode == NB_NOISE_CONST;
     const int64_t* ipos = cnoise ? in->positions : nullptr;
+    const int stop_res = stage ? stage->stop_res : 0, resume_res = stage ? stage->resume_res : 0;
+    const NbGeneratorOutputs no_outputs{};
+    if (!out) out = &no_outputs;
     NbPassPlan plan;
-    if (const int rc = g->plan(n, ipos != nullptr, &plan)) return rc;
+    if (const int rc = g->plan(n, ipos != nullptr, &plan, stop_res, resume_res)) return rc;
 
     // ---- mapping (MappingNetwork.forward) ----
     const float* ws = in->ws;
@@ -641,13 +650,18 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     } else {
         GEN_TRY((plan.styles_fast ? nb_styles_fast_f32 : nb_styles_f32)(g->table(nL), n_tab, ws, cfg.num_ws, w_dim, n, st));
         if (cnoise) {
-            int hi = n_tab;
-            if (inkernel_from >= 0) hi = std::min(hi, inkernel_from);
-            if (hi > 0) {
-                int max_res = 0;
-                for (int i = 0; i < std::min(hi, nL); ++i) max_res = std::max(max_res, specs[i].block_res);
-                GEN_TRY(nb_noise_f32(g->table(nL), hi, max_res, npos_k, npos_k ? nullptr : ipos, R, n, st));
+            // only the layers this pass runs: a head needs no noise image behind its last block, a tail none of the skipped blocks
+            int lo = 0, hi = n_tab;
+            for (int i = 0; i < nL; ++i) lo += resume_res && specs[i].block_res <= resume_res;
+            if (stop_res) {
+                hi = 0;
+                for (int i = 0; i < nL; ++i) hi += specs[i].block_res <= stop_res;
             }
+            if (inkernel_from >= 0) hi = std::min(hi, inkernel_from);
+            int max_res = 0;
+            for (int i = lo; i < std::min(hi, nL); ++i) max_res = std::max(max_res, specs[i].block_res);
+            if (hi > lo && max_res > 0)
+                GEN_TRY(nb_noise_f32(g->table(nL) + lo, hi - lo, max_res, npos_k, npos_k ? nullptr : ipos, R, n, st));
         }
     }
 
@@ -670,7 +684,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     }
 
     // ---- the layers (_run_layers / _run_layer / _finish_block) ----
-    const float* x = g->const_rep;                    // fp32 NCHW input of the next layer (NULL: handed over in operand format)
+    const float* x = resume_res ? nullptr : g->const_rep;       // fp32 NCHW input of the next layer (NULL: handed over in operand format)
     int xc = cfg.channels(4);
     const float* x2 = nullptr;                        // geometry feature still to be concatenated
     int x2c = 0;
@@ -687,6 +701,21 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         const GenLayerDev& d = g->L[i];
         const NbLayerPlan& lp = plan.layers[i];
         const int res = s.block_res, ir = s.in_res();
+        if (resume_res && res <= resume_res) {
+            // a block the resumed pass skips (_run_layers): its output is the caller's, and the geometry index moves on
+            if (s.up == 1 && res == resume_res) {
+                x = stage->features_in;
+                xc = s.out_ch;
+            }
+            if (s.up == 1 && cfg.geom_index(res) >= 0) {
+                if (res == resume_res) {
+                    x2 = in->geom[geo_idx];
+                    x2c = cfg.geom_ch[geo_idx];
+                }
+                ++geo_idx;
+            }
+            continue;
+        }
         const int c2 = x2c;                           // (not the pointer: the sizing walk carries none)
         const int c1 = x ? xc : s.in_ch - c2;
         if (c1 + c2 != s.in_ch) {
@@ -705,6 +734,8 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
             nstride = shared ? 0 : (int64_t)res * res;
         }
         const bool is_last = res == R;
+        const bool head_last = stop_res && s.up == 1 && res == stop_res;      // the tapped layer: fp32 into the caller's buffer
+        const bool fused_torgb = lp.fused_torgb && !head_last;
         const int gi_after = s.up == 1 ? cfg.geom_index(res) : -1;
         float* y = nullptr;
         void* next_h2 = nullptr;
@@ -720,7 +751,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
                 GEN_TRY((lp.in_fmt ? nb_pack_h2f8_f32 : nb_pack_h2_f32)(x, c1, x2, c2, d.styles, xh2, n, ir * ir, st));
             }
             NbTorgbArgs targs{};
-            if (lp.fused_torgb) {
+            if (fused_torgb) {
                 targs = NbTorgbArgs{g->trgb_styles, g->trgb_w, g->trgb_b, g->trgb_cb, nullptr, uvs, img, colors, in->user_colors,
                                     in->sfactor, out->rgba, out->rgba_u8, s.out_ch + 9, in->render_mode, clamp};
             } else if (lp.handoff) {
@@ -730,6 +761,8 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
                     next_h2 = other_h2(xh2);
                     if (sink.sizing) g->need_h2 = std::max(g->need_h2, h2_bytes(n, specs[i + 1].in_ch, res * res));
                 }
+            } else if (head_last) {
+                y = stage->features_out;
             } else {
                 y = other_act(x);
                 if (sink.sizing) g->need_act = std::max(g->need_act, (size_t)n * s.out_ch * res * res * sizeof(float));
@@ -738,15 +771,15 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
             const int c_next = next_h2 ? specs[i + 1].in_ch : 0;
             if (s.up == 1) {
                 GEN_TRY(nb_modconv3x3_up1_h3_ex(xh2, s.in_ch, wts, d.dcoefs, noise, nstride, d.bias, y, next_h2, nst, c_next, c_next,
-                                                lp.fused_torgb ? &targs : nullptr, lp.kernel_fmt, lp.out_fmt, n, ir, ir, s.out_ch, alpha,
+                                                fused_torgb ? &targs : nullptr, lp.kernel_fmt, lp.out_fmt, n, ir, ir, s.out_ch, alpha,
                                                 gain, clamp, st));
             } else {
                 GEN_TRY(nb_modconv3x3_up2_h3_ex(xh2, s.in_ch, wts, d.dcoefs, noise, nstride, d.bias, y, next_h2, nst, c_next, c_next,
                                                 lp.kernel_fmt, lp.out_fmt, n, ir, ir, s.out_ch, alpha, gain, clamp, st));
             }
         } else {
-            y = other_act(x);
-            if (sink.sizing) g->need_act = std::max(g->need_act, (size_t)n * s.out_ch * res * res * sizeof(float));
+            y = head_last ? stage->features_out : other_act(x);
+            if (sink.sizing && !head_last) g->need_act = std::max(g->need_act, (size_t)n * s.out_ch * res * res * sizeof(float));
             if (lp.kind == NB_KERNEL_SMALL_H3 && s.up == 1) {
                 GEN_TRY(nb_modconv3x3_up1_small_h3(x, c1, d.w_h3, d.styles, d.dcoefs, noise, nstride, d.bias, y, n, ir, ir, s.out_ch,
                                                    alpha, gain, clamp, st));
@@ -763,9 +796,10 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         xc = s.out_ch;
         x2 = nullptr;
         x2c = 0;
+        if (head_last) return NB_OK;                  // (_stop_after: no ToRGB, no geometry behind the block)
         if (s.up == 2) continue;
         // ---- what follows a block's last layer ----
-        if (is_last && !lp.fused_torgb) {
+        if (is_last && !fused_torgb) {
             GEN_TRY(nb_torgb_triad_f32(x, g->trgb_styles, c_last + 9, g->trgb_w, g->trgb_b, g->trgb_cb, clamp, nullptr, uvs, img, colors,
                                        in->user_colors, in->sfactor, in->render_mode, out->rgba, out->rgba_u8, n, c_last, R * R, st));
         }
@@ -785,6 +819,10 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
             x2c = gch;
         }
         ++geo_idx;
+    }
+    if (resume_res == R) {                            // resumed behind the last block: nothing but its ToRGB is left
+        GEN_TRY(nb_torgb_triad_f32(stage->features_in, g->trgb_styles, c_last + 9, g->trgb_w, g->trgb_b, g->trgb_cb, clamp, nullptr, uvs, img,
+                                   colors, in->user_colors, in->sfactor, in->render_mode, out->rgba, out->rgba_u8, n, c_last, R * R, st));
     }
     return NB_OK;
 }
@@ -982,6 +1020,17 @@ extern "C" int nb_generator_create(const NbGeneratorConfig* cfg, const void* con
         sink.sizing = true;
         for (int n = 1; n <= n_max; ++n)
             if ((rc = gen_walk(g, &din, &dout, n, st, sink))) return fail(rc);
+        // ... and every stage of nb_generator_forward_staged: a resumed pass packs the caller's fp32 features where a whole pass hands
+        // operands over (or packs them early into a tensor of its own); a head's tapped layer writes into the caller's buffer
+        for (int res : C.blocks)
+            for (int half = 0; half < 2; ++half) {
+                NbGeneratorStage sg{};
+                (half ? sg.resume_res : sg.stop_res) = res;
+                sg.features_out = (float*)&sentinel[7];
+                sg.features_in = (const float*)&sentinel[7];
+                for (int n = 1; n <= n_max; ++n)
+                    if ((rc = gen_walk(g, &din, &dout, n, st, sink, nullptr, &sg))) return fail(rc);
+            }
         g->act[0] = (float*)alloc(g->need_act); g->act[1] = (float*)alloc(g->need_act);
         g->h2[0] = alloc(g->need_h2); g->h2[1] = alloc(g->need_h2);
         for (size_t k = 0; k < C.geom_res.size(); ++k) g->pre_h2[k] = alloc(g->need_pre[k]);
@@ -1292,4 +1341,91 @@ extern "C" int nb_generator_forward_geom(NbGenerator* gen, const NbGeneratorInpu
     WalkSink sink;
     sink.launch = true;
     return gen_walk(gen, &io, out, n, st, sink, &hook);
+}
+
+// ------------------------------------------------------------------------------------------------
+// staged passes: the two halves of the painting engine's split around the feature-canvas blend (painting.PaintingHelper._schedule:
+// SynthesisNetwork with _stop_after / _resume; the reference blends inside its one pass, networks_modified.py:168-222)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the rules of a stage that need no handle (`who` prefixes the messages)
+int check_stage(const NbGeneratorStage* stage, const char* who) {
+    NB_REQUIRE(stage, "%s: null stage", who);
+    NB_REQUIRE((stage->stop_res != 0) != (stage->resume_res != 0), "%s: exactly one of stop_res / resume_res must be set (got %d / %d)", who,
+               stage->stop_res, stage->resume_res);
+    const int res = stage->stop_res ? stage->stop_res : stage->resume_res;
+    NB_REQUIRE(res >= 4 && (res & (res - 1)) == 0, "%s: %d is not a block resolution (a power of two in [4, R])", who, res);
+    return NB_OK;
+}
+
+}  // namespace
+
+extern "C" int nb_generator_forward_staged(NbGenerator* gen, const NbGeneratorInputs* in, const float* geom, const NbGeneratorStage* stage,
+                                           const NbGeneratorOutputs* out, int n, void* stream) {
+    const char* who = "generator_forward_staged";
+    if (const int rc = check_stage(stage, who)) return rc;
+    NB_REQUIRE(gen && in, "%s: null pointer", who);
+    const GenCfg& cfg = gen->cfg;
+    const int res = stage->stop_res ? stage->stop_res : stage->resume_res;
+    NB_REQUIRE(res <= cfg.R, "%s: %d is not a block resolution (a power of two in [4, %d])", who, res, cfg.R);
+    const int ng = (int)cfg.geom_res.size();
+    bool need_geom = false;                          // does the pass read a geometry feature at all?
+    if (stage->stop_res) {
+        NB_REQUIRE(stage->features_out, "%s: null features_out", who);
+        NB_REQUIRE(!out || !(out->rgba_u8 || out->rgba || out->img || out->uvs || out->colors),
+                   "%s: a pass that stops after a block has no ToRGB: every output pointer must be NULL", who);
+        need_geom = ng > 0;
+    } else {
+        NB_REQUIRE(stage->features_in, "%s: null features_in", who);
+        NB_REQUIRE(out, "%s: null outputs", who);
+        for (int k = 0; k < ng; ++k) need_geom = need_geom || cfg.geom_res[k] >= res;
+    }
+    if (const int rc = check_forward(gen, in, n, stream, who)) return rc;
+    const bool encode = need_geom && geom != nullptr;
+    if (encode) {
+        NB_REQUIRE(gen->enc.preproc >= 0, "%s: stroke patches given but no encoder attached (nb_generator_attach_encoder)", who);
+        for (int k = 0; k < 4; ++k)
+            NB_REQUIRE(!in->geom[k], "%s: geometry feature %d given: the encoder computes them (pass stroke patches only)", who, k);
+    } else if (need_geom) {
+        for (int k = 0; k < ng; ++k)
+            NB_REQUIRE(in->geom[k] || (stage->resume_res && cfg.geom_res[k] < res), "%s: geometry feature %d is NULL", who, k);
+    }
+    if (const int rc = check_modes_and_device(gen, in, stream, who)) return rc;
+    NbGeneratorInputs io = *in;
+    if (!need_geom)
+        for (int k = 0; k < 4; ++k) io.geom[k] = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const GeomHook hook = [&](const NbPassPlan& plan, unsigned* handed) {
+        return enc_walk(gen, geom, n, st, &plan, true, nullptr, &io, handed);
+    };
+    WalkSink sink;
+    sink.launch = true;
+    return gen_walk(gen, &io, out, n, st, sink, encode ? &hook : nullptr, stage);
+}
+
+extern "C" int nb_generator_describe_staged(NbGenerator* gen, int n, int stop_res, int resume_res, char* buf, int len) {
+    const char* who = "generator_describe_staged";
+    NbGeneratorStage sg{};
+    sg.stop_res = stop_res;
+    sg.resume_res = resume_res;
+    if (const int rc = check_stage(&sg, who)) return rc;
+    NB_REQUIRE(gen && buf && len > 0, "%s: bad arguments", who);
+    const int res = stop_res ? stop_res : resume_res, R = gen->cfg.R;
+    NB_REQUIRE(res <= R, "%s: %d is not a block resolution (a power of two in [4, %d])", who, res, R);
+    NB_REQUIRE(n >= 1 && n <= gen->n_max, "%s: batch %d outside [1, n_max = %d]", who, n, gen->n_max);
+    NbPassPlan plan;
+    if (const int rc = gen->plan(n, true, &plan, stop_res, resume_res)) return rc;
+    std::string s;
+    for (int i = 0; i < plan.num_layers; ++i) {
+        const int br = gen->cfg.layers[i].block_res;
+        if (stop_res ? br <= stop_res : br > resume_res) s += gen->cfg.layers[i].name + "=" + plan.layers[i].kernel + "\n";
+    }
+    if (resume_res) {                                // the tail's ToRGB: fused into the last conv, or on its own (always behind block R)
+        const NbLayerPlan& last = plan.layers[plan.num_layers - 1];
+        s += fmt("synthesis.b%d.torgb=", R) + (resume_res < R && last.fused_torgb ? last.kernel : "torgb_triad_kernel") + "\n";
+    }
+    NB_REQUIRE(len > (int)s.size(), "%s: buffer of %d bytes, %d needed", who, len, (int)s.size() + 1);
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return NB_OK;
 }

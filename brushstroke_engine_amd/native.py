@@ -130,11 +130,15 @@ class NativeGenerator:
         except Exception:                    # noqa: BLE001  (interpreter shutdown)
             pass
 
-    def describe(self, n: int) -> dict:
+    def describe(self, n: int, stop_res: int = 0, resume_res: int = 0) -> dict:
         """{layer name: kernel} the forward at batch n launches (the strings SynthesisNetwork.layer_kernels records; the ToRGB's
-        entry is the last conv's kernel when fused into it)."""
+        entry is the last conv's kernel when fused into it).  ``stop_res`` / ``resume_res``: the layers of that staged pass
+        (:meth:`head` / :meth:`tail`) instead of the whole pass."""
         buf = ctypes.create_string_buffer(8192)
-        _lib.check(_lib.lib().nb_generator_describe(self._h, n, buf, len(buf)), "generator_describe")
+        if stop_res or resume_res:
+            _lib.check(_lib.lib().nb_generator_describe_staged(self._h, n, stop_res, resume_res, buf, len(buf)), "generator_describe_staged")
+        else:
+            _lib.check(_lib.lib().nb_generator_describe(self._h, n, buf, len(buf)), "generator_describe")
         return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
     def attach_encoder(self, encoder_state_dict, preproc_type=None):
@@ -164,11 +168,13 @@ class NativeGenerator:
         return t
 
     def forward_into(self, outputs: dict, n: int, z=None, ws=None, geom_feature: Sequence = (), positions=None, noise_mode="const",
-                     render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0, truncation_cutoff=None, geom=None):
+                     render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0, truncation_cutoff=None, geom=None,
+                     stage=None):
         """Enqueue one forward on the current stream into caller-allocated ``outputs`` (keys rgba_u8 / rgba / img / uvs / colors;
         missing = not wanted).  Inputs must already be device tensors of the right dtype and shape (nothing is converted here):
         the form for graph capture.  ``geom``: stroke patches [n, 1, R, R] fp32 for the attached encoder, instead of
-        ``geom_feature``."""
+        ``geom_feature``.  ``stage``: an ``_lib.NbGeneratorStage`` for one half of a split pass
+        (nb_generator_forward_staged; :meth:`head` / :meth:`tail` build it)."""
         if geom is not None and len(geom_feature):
             raise ValueError("pass either geom (stroke patches) or geom_feature, not both")
         ins = _lib.NbGeneratorInputs()
@@ -188,7 +194,10 @@ class NativeGenerator:
             setattr(outs, k, _p(outputs.get(k)))
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            if geom is None:
+            if stage is not None:
+                _lib.check(_lib.lib().nb_generator_forward_staged(self._h, ctypes.byref(ins), _p(geom), ctypes.byref(stage), ctypes.byref(outs),
+                                                                  n, stream), "generator_forward_staged")
+            elif geom is None:
                 _lib.check(_lib.lib().nb_generator_forward(self._h, ctypes.byref(ins), ctypes.byref(outs), n, stream), "generator_forward")
             else:
                 _lib.check(_lib.lib().nb_generator_forward_geom(self._h, ctypes.byref(ins), _p(geom), ctypes.byref(outs), n, stream),
@@ -243,6 +252,29 @@ class NativeGenerator:
             if t is not None:
                 t.record_stream(cur)
         return outs.get("rgba_u8"), outs.get("rgba"), {"uvs": outs["uvs"], "colors": outs["colors"], "img": outs["img"]}
+
+    # ---- staged passes: the generator split around the feature-canvas blend (painting.PaintingHelper._schedule) ----
+    def head(self, n: int, stop_res: int, features_out, z=None, ws=None, geom_feature: Sequence = (), geom=None, positions=None,
+             noise_mode="const", truncation_psi=1.0, truncation_cutoff=None):
+        """Enqueue the pass up to block ``stop_res`` (``forward_pre_mapped(_stop_after=stop_res)``): the block's fp32 output, before
+        blending, goes into ``features_out`` [n, channels(stop_res), stop_res, stop_res].  Device tensors of the right dtype and
+        shape, as :meth:`forward_into` takes them."""
+        stage = _lib.NbGeneratorStage(int(stop_res), 0, _p(features_out), None)
+        self.forward_into({}, n, z=z, ws=ws, geom_feature=geom_feature, positions=positions, noise_mode=noise_mode,
+                          truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, geom=geom, stage=stage)
+        return features_out
+
+    def tail(self, n: int, resume_res: int, features_in, outputs: dict, z=None, ws=None, geom_feature: Sequence = (), geom=None,
+             positions=None, noise_mode="const", render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0,
+             truncation_cutoff=None):
+        """Enqueue the pass behind block ``resume_res`` (``render_triad(_resume=(resume_res, features_in))``) into the caller's
+        ``outputs`` (keys as :meth:`forward_into`).  Only the geometry features at resolutions >= ``resume_res`` are read
+        (``geom_feature`` entries below may be None)."""
+        stage = _lib.NbGeneratorStage(0, int(resume_res), None, _p(features_in))
+        self.forward_into(outputs, n, z=z, ws=ws, geom_feature=geom_feature, positions=positions, noise_mode=noise_mode,
+                          render_mode=render_mode, user_colors=user_colors, sfactor=sfactor, truncation_psi=truncation_psi,
+                          truncation_cutoff=truncation_cutoff, geom=geom, stage=stage)
+        return outputs
 
 
 def pack_weights_dev(weight: torch.Tensor, kind: str, resample_filter: Optional[torch.Tensor] = None):

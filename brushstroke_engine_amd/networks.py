@@ -592,7 +592,7 @@ class SynthesisNetwork(torch.nn.Module):
             # launch stops at the first of them (layers are ordered by resolution, eligibility grows with it)
             if inkernel_from is not None:
                 hi_ = min(hi_, inkernel_from)
-            if hi_ > lo_:
+            if hi_ > lo_ and cfg.layers[lo_:hi_]:       # (a pass resumed behind the last block runs no layer)
                 _lib.check(lib.nb_noise_f32(table.data_ptr() + lo_ * ctypes.sizeof(_lib.NbLayerDesc), hi_ - lo_,
                                             max(sp.block_res for sp in cfg.layers[lo_:hi_]), _p(npos), _p(ipos),
                                             self.img_resolution, n, stream), "noise")
@@ -678,6 +678,11 @@ class SynthesisNetwork(torch.nn.Module):
                     if res == resume[0]:
                         ps.x2 = ps.geom_feature[ps.geo_idx].to(torch.float32).contiguous()
                     ps.geo_idx += 1
+                if res == resume[0] and block.is_last:
+                    # resumed behind the last block (feature blending at the output resolution): nothing but its ToRGB is left
+                    ps.img, triad = self._torgb(plan, ps.x, n, ps.stream, opts.extra)
+                    if ps.return_debug_data:
+                        ps.debug_data.update(triad)
                 continue
             names = ([f"synthesis.b{res}.conv0"] if res > 4 else []) + [f"synthesis.b{res}.conv1"]
             if res == 4:

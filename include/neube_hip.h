@@ -462,6 +462,23 @@ int nb_canvas_replay_pieces_f32(const NbTilePiece* pieces, int n, int c, int hw,
 int nb_paste_tiles_u8(const uint8_t* tiles, int t, int r, const int32_t* dst_yx, int crop, uint8_t* canvas, int h, int w,
                       const int32_t* cell_off, const int32_t* cell_tiles, void* stream);
 
+/* The alpha0 template of nb_canvas_replay_*_f32 written on the device: PaintingHelper.generate_dirty_area_alpha (forger/ui/brush.py:159-187)
+ * for a dirty area spanning the whole tile of `width` pixels: 1 inside the square inset by margin + crop, a linear fall-off of width
+ * `margin` outside it (distance to the nearest edge; to the nearest corner in the corner regions), 0 beyond.  alpha0_dev [width, width]
+ * fp32.  fp32 throughout with correctly rounded sqrt and division, in the reference's expression order: bit for bit what the numpy
+ * of the reference computes.  margin <= 0, or margin + crop leaving no interior: NB_EINVAL.  (The engine passes the blend margin 16 and
+ * the tile's crop margin, both divided by the blending level's down factor: brush.py:190-227.) */
+int nb_dirty_area_alpha_f32(float* alpha0_dev, int width, int margin, int crop, void* stream);
+
+/* The cell lists above for a host without numpy (HOST ONLY: no HIP call, host pointers).  rects [t, 4] int32 (y0, x0, y1, x1),
+ * end-exclusive, clipped to the h x w grid here; rectangles that miss the grid are dropped.  For the replay the rectangles are the
+ * tiles' areas on the feature canvas (brush.py:253-258: the tile origin floored to the blending grid, divided by the down factor),
+ * for the paste the tiles' interiors.  nb_canvas_cells_count returns the number of list entries (>= 1: a list without entries is a
+ * single 0, so that its device copy is never empty) or a negative NB_E* code; nb_canvas_build_cells fills cell_off
+ * [ceil(h / NB_CELL_H) * ceil(w / NB_CELL_W) + 1] and cell_items [that count], every cell's rectangles in ascending order. */
+int nb_canvas_cells_count(const int32_t* rects, int t, int h, int w);
+int nb_canvas_build_cells(const int32_t* rects, int t, int h, int w, int32_t* cell_off, int32_t* cell_items);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
@@ -657,6 +674,36 @@ int nb_generator_attach_encoder(NbGenerator* gen, const void* const* enc_params_
  * NULL geom, or any input nb_generator_forward rejects: NB_EINVAL (NB_EUNSUPPORTED for random noise), nothing enqueued. */
 int nb_generator_forward_geom(NbGenerator* gen, const NbGeneratorInputs* in, const float* geom, const NbGeneratorOutputs* out, int n,
                               void* stream);
+
+/* ---- staged passes: the generator split around the feature-canvas blend --------------------------------------------------------
+ * The reference blends a tile's features with the feature canvas INSIDE its one synthesis pass (networks_modified.py:168-222:
+ * BlendedFeatures.blend, forger/train/stitching.py:24-25, on the output of the blending block).  Here the blend of all tiles is one
+ * launch (nb_canvas_replay_f32) between two batched generator passes, so the pass is cut at the blending block:
+ *   head (stop_res):   mapping ... block stop_res; the block's last layer writes its fp32 output, before blending, into features_out.
+ *                      No ToRGB runs: every pointer of NbGeneratorOutputs must be NULL (out itself may be NULL).  Styles are
+ *                      computed for every layer, noise images only for the layers that run.
+ *   tail (resume_res): the pass starts behind block resume_res from features_in (the blended features) and ends with the ToRGB and
+ *                      compositing; if resume_res is a geometry resolution that feature joins features_in as the next block's input.
+ *                      resume_res = R runs nothing but nb_torgb_triad_f32.  Noise images only for the blocks behind resume_res.
+ * Exactly one of stop_res / resume_res is non-zero, a block resolution 4..R.  geom: stroke patches for the attached encoder (as
+ * nb_generator_forward_geom; in->geom[] then all NULL) or NULL with the features in in->geom[].  A tail needs only the features at
+ * resolutions >= resume_res; when it needs none, geom and in->geom[] are ignored and the encoder does not run.  The two passes of a
+ * tile batch are SynthesisNetwork's `_stop_after` / `_resume` passes of the package (painting.PaintingHelper._schedule), bit for bit.
+ * Enqueue only, one stream, no allocation: capturable into a hipGraph after one eager call at the batch size and stage.  A bad
+ * stage, a NULL features pointer, a missing feature or any input nb_generator_forward rejects: NB_EINVAL (NB_EUNSUPPORTED for random
+ * noise), nothing enqueued. */
+typedef struct NbGeneratorStage {
+    int32_t stop_res;          /* 0, or a block resolution 4..R: the pass ends after block stop_res */
+    int32_t resume_res;        /* 0, or a block resolution 4..R: the pass starts after block resume_res */
+    float* features_out;       /* stop_res: [n, channels(stop_res), stop_res, stop_res] fp32, the block's output before blending */
+    const float* features_in;  /* resume_res: [n, channels(resume_res), resume_res, resume_res] fp32 (blended) */
+} NbGeneratorStage;
+int nb_generator_forward_staged(NbGenerator* gen, const NbGeneratorInputs* in, const float* geom, const NbGeneratorStage* stage,
+                                const NbGeneratorOutputs* out, int n, void* stream);
+
+/* nb_generator_describe for a staged pass: the lines of the layers the pass runs (the strings SynthesisNetwork.layer_kernels
+ * records for them), and for a tail the ToRGB's line.  Host only. */
+int nb_generator_describe_staged(NbGenerator* gen, int n, int stop_res, int resume_res, char* buf, int len);
 
 /* ---- the per-batch layer plan (host only: no HIP call, works without a GPU) ------------------------------------------------
  * Every kernel decision of one synthesis pass at batch n: which kernel each layer runs, its operand formats, the operand hand-off,
