@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lock = threading.Lock()
 _lib = None
@@ -143,6 +143,11 @@ PROTOTYPES = {
     "nb_dirty_area_alpha_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
     "nb_canvas_cells_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
     "nb_canvas_build_cells": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    # drawing preparation (csrc/nb_geomprep.hip): Otsu geometry into the padded buffer, tile picks, crop + on-white
+    "nb_geom_prepare_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "nb_tile_stroke_counts_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "nb_composite_on_white_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "nb_stitching_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -231,6 +236,8 @@ class NbPassPlan(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("num_layers", "num_geom", "inkernel_from", "styles_fast", "styles_noise", "positions_once")] + [
         ("layers", NbLayerPlan * NB_PLAN_MAX_LAYERS), ("geom", NbGeomPlan * 4)]
 
+
+NB_GEOM_PREP_WS_BYTES = 1040
 
 NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3
 NB_CONV_MODES = {"f32": 0, "h3": 1, "f8": 2, "f6": 3, "f16": 4}

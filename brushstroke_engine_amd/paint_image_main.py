@@ -60,6 +60,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--conv_mode", default=None, choices=["f8", "h3", "f32"],
                     help="arithmetic of the conv layers (default: networks.DEFAULT_CONV_MODE = f8: f16 main product + fp8 corrections, "
                          "~1e-4 from fp32 on pixels; h3: three f16 products, 5e-6; f32: exact fp32 MFMA)")
+    ap.add_argument("--host_prepare", action="store_true",
+                    help="threshold, pad and tile the drawing with numpy on the host (default: on the device; same output file)")
     ap.add_argument("--gpus", type=int, default=1, help="N > 1: launch N ranks (one per GPU) and shard the tiles over them")
     return ap
 
@@ -89,13 +91,19 @@ def main(argv=None) -> str:
         library.set_style(args.style_id, opts)
     else:
         library.set_interpolated_style(args.style_id, args.style_id2, args.style_blend_alpha, opts)
-    geom = painting.read_geometry_image(args.geom_image)
+    from PIL import Image
+    drawing = np.array(Image.open(args.geom_image))
     helper = painting.PaintingHelper(ops, batch=args.batch, uvs_mapper=mapper)
     helper.set_feature_blending(args.feature_blending_level)
     helper.set_render_mode(args.render_mode)
     with torch.no_grad():
-        result = helper.paint_image(geom, opts, crop_margin=args.crop_margin, stitching_mode=args.stitching_mode,
-                                    on_white=args.on_white)
+        # (the kernels take 8-bit gray / RGB / RGBA; 1-bit, 16-bit and gray + alpha files keep the numpy route)
+        if args.host_prepare or drawing.dtype != np.uint8 or (drawing.ndim == 3 and drawing.shape[2] not in (1, 3, 4)):
+            result = helper.paint_image(painting.prepare_geometry_image(drawing), opts, crop_margin=args.crop_margin,
+                                        stitching_mode=args.stitching_mode, on_white=args.on_white)
+        else:
+            result = helper.paint_drawing(drawing, opts, crop_margin=args.crop_margin, stitching_mode=args.stitching_mode,
+                                          on_white=args.on_white)
     output_file = None
     if result is not None:                                         # rank 0
         style_name = args.style_id
@@ -103,7 +111,6 @@ def main(argv=None) -> str:
             style_name += "_%0.1f%s" % (args.style_blend_alpha, args.style_id2)
         output_file = args.output_file_prefix + "_" + args.render_mode + "_" + str(style_name) + ".png"
         os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
-        from PIL import Image
         Image.fromarray(result).save(output_file)
         logger.info(f"Saved result to: {output_file}")
         print(output_file)

@@ -48,7 +48,7 @@ def threshold_otsu(image: np.ndarray) -> float:
     """Otsu threshold of an integer image over its occupied value range -- the algorithm of
     ``skimage.filters.threshold_otsu`` (scikit-image 0.19, one bin per integer value), which
     ``forger/util/img_proc.py:66-71`` calls.  scikit-image is not installed in the build image, so this helper is
-    NOT pinned against it (DESIGN.md says so); it only prepares input geometry, before the measured path."""
+    NOT pinned against it (DESIGN.md says so).  ``nb_geom_prepare_u8`` computes the same threshold on the device."""
     img = np.asarray(image)
     if img.size == 0:
         raise ValueError("empty image")
@@ -115,6 +115,15 @@ def generate_stitching_crops(stroke_image: np.ndarray, patch_width: int, mode: s
             if mode == "all" or np.sum(padded[y:y + patch_width, x:x + patch_width] < 0.001) > 10:
                 crops.append((y, x, patch_width, patch_width))
     return crops, padded
+
+
+def stitching_grid(h: int, w: int, patch_width: int, overlap_margin: int) -> Tuple[int, int, int, int, int]:
+    """(nrows, ncols, stride, padded_h, padded_w) of ``generate_stitching_crops`` for an [h, w] image (``nb_stitching_grid``)."""
+    import ctypes as C
+    v = [C.c_int() for _ in range(5)]
+    _lib.check(_lib.lib().nb_stitching_grid(int(h), int(w), int(patch_width), int(overlap_margin), *[C.byref(x) for x in v]),
+               "stitching_grid")
+    return tuple(x.value for x in v)
 
 
 def dirty_area_alpha(width: int, margin: int, crop_margin: int = 0) -> np.ndarray:
@@ -517,6 +526,48 @@ class TileOps:
             _lib.check(_lib.lib().nb_paste_tiles_u8(_p(tiles_u8), t, r, _p(dst_yx), crop, _p(canvas_u8), h, w,
                                                     _p(cell_off), _p(cell_tiles), self._stream()), "paste_tiles")
 
+    # -- drawing preparation (csrc/nb_geomprep.hip) --
+    def prepare_geometry(self, img, out_shape=None, offset=(0, 0)) -> torch.Tensor:
+        """``prepare_geometry_image(img)[..., 0]`` computed on the device and placed at ``offset`` of a [out_h, out_w] uint8
+        buffer that is 255 elsewhere (``nb_geom_prepare_u8``).  ``img``: decoded drawing, uint8 [H,W], [H,W,3] or [H,W,4],
+        numpy (uploaded here) or a device tensor."""
+        if not torch.is_tensor(img):
+            img = np.asarray(img)
+            if img.dtype != np.uint8:
+                raise ValueError(f"prepare_geometry: the drawing must be uint8, got {img.dtype}")
+            img = self.to_device(img)
+        if img.dtype != torch.uint8 or img.dim() not in (2, 3):
+            raise ValueError(f"prepare_geometry: uint8 [H,W] or [H,W,C] expected, got {img.dtype} {tuple(img.shape)}")
+        img = img.contiguous()
+        h, w = img.shape[:2]
+        ch = 1 if img.dim() == 2 else img.shape[2]
+        out_h, out_w = (h, w) if out_shape is None else out_shape
+        out = torch.empty([out_h, out_w], dtype=torch.uint8, device=self.device)
+        if getattr(self, "_prep_ws", None) is None:
+            self._prep_ws = torch.empty([_lib.NB_GEOM_PREP_WS_BYTES // 4], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_geom_prepare_u8(_p(img), h, w, ch, _p(out), out_h, out_w, int(offset[0]), int(offset[1]),
+                                                     _p(self._prep_ws), self._stream()), "geom_prepare")
+        return out
+
+    def stroke_counts(self, geom_dev: torch.Tensor, r: int, stride: int, nrows: int, ncols: int) -> torch.Tensor:
+        """[nrows, ncols] int32 on the device: stroke pixels (== 0) in the r x r window of every tile (``nb_tile_stroke_counts_u8``)."""
+        gh, gw = geom_dev.shape
+        counts = torch.empty([nrows, ncols], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_tile_stroke_counts_u8(_p(geom_dev), gh, gw, r, stride, nrows, ncols, _p(counts), self._stream()),
+                       "tile_stroke_counts")
+        return counts
+
+    def composite_on_white(self, canvas: torch.Tensor, y0: int, x0: int, h: int, w: int) -> torch.Tensor:
+        """[h, w, 3] uint8: the window of the RGBA canvas at (y0, x0) over white (``nb_composite_on_white_u8``)."""
+        ch, cw = canvas.shape[:2]
+        out = torch.empty([h, w, 3], dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_composite_on_white_u8(_p(canvas), ch, cw, y0, x0, h, w, _p(out), self._stream()),
+                       "composite_on_white")
+        return out
+
 
 # ------------------------------------------------------------------------------------------------
 # clear-background mapping (reference: StyleUVSMapper, forger/ui/mapper.py:16-72, 117-135)
@@ -658,9 +709,10 @@ class PaintingHelper:
         return world > 1 or (os.environ.get("NB_FORCE_PG") == "1" and dist.is_available() and dist.is_initialized())
 
     # -- the schedule --
-    def _schedule(self, geom_img: np.ndarray, geom_yx: np.ndarray, areas_yx: np.ndarray, positions: Optional[np.ndarray],
+    def _schedule(self, geom_img, geom_yx: np.ndarray, areas_yx: np.ndarray, positions: Optional[np.ndarray],
                   opts: GanBrushOptions, crop_margin: int) -> Optional[torch.Tensor]:
-        """Tiles i = 0..T-1 in paint order: geometry cut from ``geom_img`` [H,W] uint8 (255 = background) at
+        """Tiles i = 0..T-1 in paint order: geometry cut from ``geom_img`` [H,W] uint8 (255 = background; numpy, or a tensor that
+        is on the device already) at
         ``geom_yx[i]``, canvas area at ``areas_yx[i]`` (already floored to the blending grid), noise position
         ``positions[i]`` (None: unshifted noise).  Returns the RGBA tiles [T,R,R,4] uint8 on rank 0 (None elsewhere)
         and leaves the feature canvas updated -- the result of the reference's tile-by-tile loop."""
@@ -676,7 +728,7 @@ class PaintingHelper:
         n_pad = -(-T // world)                                                 # equal per-rank count for collectives
         counts = [shard_bounds(T, r, world)[1] - shard_bounds(T, r, world)[0] for r in range(world)]
 
-        geom_dev = ops.to_device(np.ascontiguousarray(geom_img))
+        geom_dev = geom_img.contiguous() if torch.is_tensor(geom_img) else ops.to_device(np.ascontiguousarray(geom_img))
         ws1 = ops.map_style(z=opts.style_z, ws=opts.style_ws)                  # one brush style for all tiles
         user = opts.user_colors()
         sfac = None
@@ -870,10 +922,10 @@ class PaintingHelper:
             self._comm_events = {}
         return out
 
-    def render_tiles(self, geom_padded: np.ndarray, crops: Sequence[Tuple[int, int]], opts: GanBrushOptions,
+    def render_tiles(self, geom_padded, crops: Sequence[Tuple[int, int]], opts: GanBrushOptions,
                      crop_margin: int = 0, out_canvas: Optional[torch.Tensor] = None):
         """Render the tiles whose top-left corners (y, x) are ``crops`` from the padded geometry [H,W] uint8
-        (255 = background) and paste them into ``out_canvas`` [H,W,4] uint8 on the device (rank 0; created if None).
+        (255 = background; numpy or a device tensor) and paste them into ``out_canvas`` [H,W,4] uint8 on the device (rank 0; created if None).
         Equivalent to calling the reference's ``render_stroke`` on the tiles in order with
         ``opts.set_position(x, y)`` (paint_image_main.py:157-177).  Returns the canvas on rank 0, None elsewhere."""
         ops, R = self.ops, self.patch_width
@@ -954,3 +1006,38 @@ class PaintingHelper:
             return out
         full = to_host(canvas)
         return (out, full, crops, padded) if return_full else out
+
+    def paint_drawing(self, img: np.ndarray, opts: GanBrushOptions, crop_margin: int = 10, stitching_mode: str = "all",
+                      on_white: bool = False, return_full: bool = False):
+        """``paint_image(prepare_geometry_image(img), ...)`` with the preparation on the device: the decoded drawing (uint8 [H,W],
+        [H,W,3] or [H,W,4]) is uploaded once, thresholded straight into the padded geometry (``nb_geom_prepare_u8``), the tiles are
+        picked from per-tile stroke counts (``nb_tile_stroke_counts_u8``), the schedule runs on the device-resident geometry and the
+        result is cropped / composited on white on the device.  Same bytes as the host route.  An ``ops`` without the preparation
+        kernels (the CPU stand-ins of the tests) takes the numpy helpers."""
+        ops, R, m = self.ops, self.patch_width, int(crop_margin)
+        if not all(hasattr(ops, k) for k in ("prepare_geometry", "stroke_counts", "composite_on_white")):
+            return self.paint_image(prepare_geometry_image(img), opts, crop_margin=crop_margin, stitching_mode=stitching_mode,
+                                    on_white=on_white, return_full=return_full)
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3, 4)):
+            raise ValueError(f"paint_drawing: uint8 [H,W], [H,W,3] or [H,W,4] expected, got {img.dtype} {img.shape}")
+        h0, w0 = img.shape[:2]
+        nrows, ncols, stride, ph, pw = stitching_grid(h0 + m, w0 + m, R, 2 * m)
+        padded = ops.prepare_geometry(img, (ph, pw), (m, m))
+        if stitching_mode == "all":
+            keep = np.ones((nrows, ncols), bool)
+        else:
+            keep = ops.to_host(ops.stroke_counts(padded, R, stride, nrows, ncols)) > 10
+        crops = [(int(r) * stride, int(c) * stride, R, R) for r, c in zip(*np.nonzero(keep))]       # row-major, as the host loop
+        self.make_new_canvas(ph, pw, self.feature_blending_level)
+        canvas = self.render_tiles(padded, crops, opts, crop_margin=m)
+        if canvas is None:
+            return None
+        if on_white:
+            result = ops.composite_on_white(canvas, m, m, h0, w0)
+        else:
+            result = canvas[m:m + h0, m:m + w0].contiguous()
+        out = ops.to_host(result)
+        if not return_full:
+            return out
+        return out, ops.to_host(canvas), crops, ops.to_host(padded)[..., None]

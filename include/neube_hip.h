@@ -479,6 +479,49 @@ int nb_dirty_area_alpha_f32(float* alpha0_dev, int width, int margin, int crop, 
 int nb_canvas_cells_count(const int32_t* rects, int t, int h, int w);
 int nb_canvas_build_cells(const int32_t* rects, int t, int h, int w, int32_t* cell_off, int32_t* cell_items);
 
+/* ---- drawing preparation: from a decoded drawing to the padded geometry, the tile picks and the image on white ------------------
+ * What forger/viz/paint_image_main.py does on the host before and after its tile loop.  The three device entries only enqueue on
+ * `stream` (no allocation, no synchronisation, no read-back: they can be captured into a hipGraph); all pointers but those of
+ * nb_stitching_grid are device pointers. */
+
+/* _read_any_geo (paint_image_main.py:30-57) with threshold_img (forger/util/img_proc.py:66-71: skimage's threshold_otsu, one bin per
+ * integer value) on a decoded drawing, written straight into the padded geometry of paint_image_main.py:58-61 and
+ * generate_stitching_crops (forger/viz/style_transfer.py:24-31).  img [h,w,channels] uint8 (HWC), channels 1 (gray), 3 (RGB) or
+ * 4 (RGBA); out [out_h,out_w] uint8: the thresholded drawing (255 = background, 0 = stroke) at (off_y, off_x), 255 around it.
+ *   gray (fp32)  the value | ((r + g) + b) / 3 | mean * alpha + 255 * (1 - alpha) with alpha = a / 255 -- separate, unfused multiply,
+ *                subtract and add, correctly rounded divisions;
+ *   stretch      subtract the global minimum if it is > 0, then scale by (float)(255.0 / (double)max) if 0 < max < 255; truncate to uint8;
+ *   threshold    Otsu over the occupied value range in float64, cumulative sums in sequential order, first maximum of
+ *                var12 = w1 * w2 * (m1 - m2)^2 (a constant image: its value);
+ *   out          gray8 > threshold ? 255 : 0.
+ * Byte for byte what the numpy code of the reference produces.  The passes recompute the gray value from img: no scratch the size of
+ * the drawing.  ws: NB_GEOM_PREP_WS_BYTES of 4-byte aligned device scratch, cleared by the call itself, holding on completion as
+ * uint32 words: [0] / [1] the bit patterns of the fp32 minimum / maximum gray value, [2] the threshold, [4..259] the histogram of
+ * the stretched uint8 image (its counts sum to h * w).  Calls that share a ws must be ordered (one stream).
+ * NB_EINVAL: a null pointer, another channel count, an image that does not fit into out at the offset, h * w >= 2^31. */
+#define NB_GEOM_PREP_WS_BYTES 1040
+int nb_geom_prepare_u8(const uint8_t* img, int h, int w, int channels, uint8_t* out, int out_h, int out_w, int off_y, int off_x,
+                       void* ws, void* stream);
+
+/* Stroke pixels per tile: counts[row * ncols + col] = number of pixels equal to 0 in the r x r window of geom [gh,gw] at
+ * (row * stride, col * stride); pixels outside the image are background.  The `np.sum(padded[...] < 0.001)` of
+ * generate_stitching_crops (style_transfer.py:15-48) for every tile in one launch: with a mode other than "all" the host copies
+ * the nrows * ncols counts back and keeps, in row-major order, the tiles with a count above 10. */
+int nb_tile_stroke_counts_u8(const uint8_t* geom, int gh, int gw, int r, int stride, int nrows, int ncols, int32_t* counts,
+                             void* stream);
+
+/* The crop and `--on_white` of paint_image_main.py:179-183 in one pass: canvas [ch,cw,4] RGBA8 (4-byte aligned), out [h,w,3] =
+ * trunc(clip(rgb * a + 255 * (1 - a), 0, 255)) of the window at (y0, x0), a = alpha / 255 correctly rounded, unfused fp32. */
+int nb_composite_on_white_u8(const uint8_t* canvas, int ch, int cw, int y0, int x0, int h, int w, uint8_t* out, void* stream);
+
+/* The tile grid of generate_stitching_crops (style_transfer.py:15-32) for an [h,w] image (HOST ONLY: no HIP call, works without a
+ * GPU): stride = patch_width - 2 * overlap_margin, nrows = h / stride + 1, ncols = w / stride + 1, tile (row, col) at
+ * (row * stride, col * stride), padded size = rows-or-cols * stride + patch_width.  paint_image_main pads the drawing by its crop
+ * margin m first (h + m, w + m here, offsets (m, m) for nb_geom_prepare_u8) and tiles with overlap_margin = 2 m.
+ * NB_EINVAL when patch_width - 2 * overlap_margin <= 0. */
+int nb_stitching_grid(int h, int w, int patch_width, int overlap_margin, int* nrows, int* ncols, int* stride, int* padded_h,
+                      int* padded_w);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
