@@ -248,6 +248,41 @@ __device__ __forceinline__ unsigned nb_pk4_fp8(float a, float b, float c, float 
     return (unsigned)w;
 }
 
+// ---- The fused 4 x 4 FIR of the up = 2 epilogues (modconv3x3_up2_h3_kernel, modconv3x3_up2v_kernel): the per-output arithmetic,
+//      ROWS FIRST.  The phase planes hold, per quad position, the even / odd output rows and columns of the transposed convolution:
+//      the pre-filter image's rows run O(i), E(i), O(i + 1), E(i + 1), ... (O from the planes oe / oo, E from ee / eo at quad row i),
+//      its columns likewise o(j), e(j), o(j + 1), ... (o from eo / oo, e from ee / oe).  An output = one vertical four-tap FIR over
+//      four horizontally filtered rows; both kernels evaluate it through these functions, in this order, whichever item of
+//      whichever tile form an output falls in -- that is what keeps all forms bit-identical to each other. ----
+// 4-tap polyphase FIR 0.25 a + 0.75 b + 0.75 c + 0.25 d as one multiply + three fused multiply-adds (the reference's upfirdn2d is a
+// convolution whose summation order and fusing are the backend's)
+__device__ __forceinline__ f32x4 nb_up2_fir4(f32x4 a, f32x4 b, f32x4 c, f32x4 d) {
+    f32x4 q75, q25;
+    q75 = 0.75f; q25 = 0.25f;
+    return __builtin_elementwise_fma(q25, d, __builtin_elementwise_fma(q75, c, __builtin_elementwise_fma(q75, b, 0.25f * a)));
+}
+// One row of the pre-filter image at a quad's two output columns, filtered horizontally: e / o = the row's even- / odd-column
+// planes at the quad's position (5 slot reads: o at quad columns j .. j + 2, e at j, j + 1).  h[px] = the quad's left / right pixel.
+__device__ __forceinline__ void nb_up2_hrow(const f32x4* e, const f32x4* o, f32x4 (&h)[2]) {
+    const f32x4 o0 = o[0], e0 = e[0], o1 = o[1], e1 = e[1], o2 = o[2];
+    h[0] = nb_up2_fir4(o0, e0, o1, e1);
+    h[1] = nb_up2_fir4(e0, o1, e1, o2);
+}
+// One output row of a quad from four consecutive filtered rows: the vertical FIR, then g (o d + noise + bias), lrelu, clamp with g
+// folded into d, noise and bias (d4, nz*, b4 hold g d, g noise, g bias).  lrelu = max(t, alpha t) for 0 <= alpha <= 1 (the launcher
+// checks); med3 with +inf is a max without the NaN canonicalisation instructions fmaxf() costs.  clampv = +inf: no clamp.
+__device__ __forceinline__ void nb_up2_vout(const f32x4 (&r0)[2], const f32x4 (&r1)[2], const f32x4 (&r2)[2], const f32x4 (&r3)[2], f32x4 d4,
+                                            f32x4 b4, float nz0, float nz1, float alpha, float clampv, f32x4 (&v)[2]) {
+#pragma unroll
+    for (int px = 0; px < 2; ++px) {
+        f32x4 t = __builtin_elementwise_fma(nb_up2_fir4(r0[px], r1[px], r2[px], r3[px]), d4, b4 + (px ? nz1 : nz0));
+        const f32x4 ta = t * alpha;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t[i] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_fmed3f(t[i], ta[i], __builtin_inff()), -clampv, clampv);
+        v[px] = t;
+    }
+}
+
 // Hand-off epilogue of the up=1 kernels (H2 or "f8" output into the consumer's operand tensor), straight from the
 // accumulators: no LDS image, no barrier.  D[row = c_out, col = pixel]: a lane holds, for ITS pixel, four consecutive
 // channels (4 lh .. 4 lh + 3) of each 8-channel group g; activation / consumer style / hi-lo split run packed over those

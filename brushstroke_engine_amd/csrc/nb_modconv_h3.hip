@@ -2008,43 +2008,21 @@ __global__ __launch_bounds__(NW_ * 64, 2) void modconv3x3_up2_h3_kernel(const H3
             const f32x4* eo = ee + 1 * Y1P;
             const f32x4* oe = ee + 2 * Y1P;
             const f32x4* oo = ee + 3 * Y1P;
-            // 4-tap polyphase FIR 0.25 a + 0.75 b + 0.75 c + 0.25 d as one multiply + three fused multiply-adds (the
-            // reference's upfirdn2d is a convolution whose summation order and fusing are the backend's)
-            auto fir4 = [](f32x4 a, f32x4 b, f32x4 c, f32x4 d) {
-                f32x4 q75, q25;
-                q75 = 0.75f; q25 = 0.25f;
-                return __builtin_elementwise_fma(q25, d, __builtin_elementwise_fma(q75, c, __builtin_elementwise_fma(q75, b, 0.25f * a)));
-            };
-            // vertical pass at the quad's 5 intermediate columns: even ones (ve) from (ee, oe) at quad columns tj, tj+1,
-            // odd ones (vo) from (eo, oo) at tj .. tj+2; [dy] = output row of the quad
-            f32x4 ve[2][2], vo[3][2];
+            // horizontal pass first (nb_up2_hrow, nb_h3_common.h): the quad's five pre-filter rows O(ti), E(ti), O(ti + 1), E(ti + 1),
+            // O(ti + 2) at its two output columns; then one vertical FIR per output row (nb_up2_vout) -- the per-output order of
+            // modconv3x3_up2v_kernel, which shares the filtered rows along a column run of quads
+            f32x4 hr[5][2];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (c < 2) {
-                    const f32x4 e0 = ee[c], e1 = ee[PW + c], o0 = oe[c], o1 = oe[PW + c], o2 = oe[2 * PW + c];
-                    ve[c][0] = fir4(o0, e0, o1, e1); ve[c][1] = fir4(e0, o1, e1, o2);
-                }
-                const f32x4 e0 = eo[c], e1 = eo[PW + c], o0 = oo[c], o1 = oo[PW + c], o2 = oo[2 * PW + c];
-                vo[c][0] = fir4(o0, e0, o1, e1); vo[c][1] = fir4(e0, o1, e1, o2);
+            for (int m = 0; m < 5; ++m) {
+                if (m & 1) nb_up2_hrow(ee + (m >> 1) * PW, eo + (m >> 1) * PW, hr[m]);
+                else nb_up2_hrow(oe + (m >> 1) * PW, oo + (m >> 1) * PW, hr[m]);
             }
             const f32x4 d4 = *reinterpret_cast<const f32x4*>(s_dco + c4), b4 = *reinterpret_cast<const f32x4*>(s_bias + c4);
             const int qi = I0 + ti, qj = J0 + tj;
-            // g (o d + noise + bias), lrelu, clamp with g folded into d, noise and bias (s_dco, s_noise, s_bias hold g d,
-            // g noise, g bias)
-            auto act4 = [&](f32x4 o, float nz) {
-                f32x4 t = __builtin_elementwise_fma(o, d4, b4 + nz);
-                const f32x4 ta = t * p.alpha;
-                // lrelu = max(t, alpha t) for 0 <= alpha <= 1 (the launcher checks); med3 with +inf is a max without the NaN
-                // canonicalisation instructions fmaxf() costs
-#pragma unroll
-                for (int i = 0; i < 4; ++i) t[i] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_fmed3f(t[i], ta[i], __builtin_inff()), -clampv, clampv);
-                return t;
-            };
             f32x4 v[2][2];                            // [dy][px]
 #pragma unroll
             for (int dy = 0; dy < 2; ++dy) {
                 const f32x2 nz = *reinterpret_cast<const f32x2*>(s_noise + (2 * ti + dy) * (2 * TQW) + 2 * tj);
-                // horizontal pass: even pixel = fir4(vo[0], ve[0], vo[1], ve[1]), odd pixel = fir4(ve[0], vo[1], ve[1], vo[2])
                 // The two noise values get registers of their own.  Left in the loaded pair, the compiler adds the second one
                 // as `v_pk_add_f32 d, bias, v[pair] op_sel:[0,1]` (low result reads the pair's HIGH dword), and that
                 // instruction returned, for 8-16 lanes of the upper half-wave and run-to-run differently, the sum with the
@@ -2053,8 +2031,7 @@ __global__ __launch_bounds__(NW_ * 64, 2) void modconv3x3_up2_h3_kernel(const H3
                 float nz0 = nz[0], nz1 = nz[1];
                 asm volatile("v_mov_b32 %0, %0" : "+v"(nz0));
                 asm volatile("v_mov_b32 %0, %0" : "+v"(nz1));
-                v[dy][0] = act4(fir4(vo[0][dy], ve[0][dy], vo[1][dy], ve[1][dy]), nz0);
-                v[dy][1] = act4(fir4(ve[0][dy], vo[1][dy], ve[1][dy], vo[2][dy]), nz1);
+                nb_up2_vout(hr[dy], hr[dy + 1], hr[dy + 2], hr[dy + 3], d4, b4, nz0, nz1, p.alpha, clampv, v[dy]);
             }
             if constexpr (OUTM == 0) {
                 if (qi < H && !(p.dbg & 1)) {

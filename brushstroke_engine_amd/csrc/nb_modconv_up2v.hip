@@ -1,8 +1,9 @@
 // up = 2 split-f16 convolution ("f8" operands), 8-wave form with a SOFTWARE-PIPELINED K loop for gfx950.
 //
 // Same math, same tile (12 x 32 quads x 32 c_out, two position blocks and all four output phases per wave = 128 accumulator
-// registers, two waves per SIMD), same three-stage LDS ring and the same epilogue as modconv3x3_up2_h3_kernel
-// (nb_modconv_h3.hip) -- and the same per-output summation order: bit-identical results.  What differs is the K loop, which is the
+// registers, two waves per SIMD), same three-stage LDS ring and the same phase slots, stores and per-output arithmetic
+// (nb_up2_hrow / nb_up2_vout, nb_h3_common.h) as modconv3x3_up2_h3_kernel (nb_modconv_h3.hip): bit-identical results.  Its epilogue
+// items are column runs of quads that share the horizontally filtered rows (round 8).  What differs besides is the K loop, which is the
 // one measured on the one-wave-per-SIMD kernel of round 4 (nb_modconv_up2w.hip, removed in round 6 -- docs/perf_history.md: 97 % of its cycles were matrix work):
 //   * one basic block per chunk: LDS-DMA pieces are issued from statements that set their lane mask themselves (an `if` around a
 //     piece is a branch, and the compiler moves MFMAs across the resulting blocks);
@@ -733,14 +734,14 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
             if (mix_isx) issue_piece(std::integral_constant<int, KMIX>{}, 0, 0);
         }
     }
-    // ---- epilogue: modconv3x3_up2_h3_kernel's, statement for statement (2 rounds of 16 c_out; comments there) ----
+    // ---- epilogue: modconv3x3_up2_h3_kernel's phase slots, arithmetic per output and stores (2 rounds of 16 c_out; comments there);
+    //      the items are column runs of quads instead of single quads ----
     // (the lane / wave coordinates through an opaque statement: everything the epilogue derives from them -- slot addresses, quad
     //  coordinates, channel offsets: ~45 per-lane values -- is the same for every tile, so the compiler would hoist it all out of the
     //  tile loop and keep it in (spilled) registers across the K loop; recomputed per tile it is a few dozen integer instructions)
     int l31e = l31, lhe = lh, wve = wv;
     asm volatile("" : "+v"(l31e), "+v"(lhe), "+s"(wve));
     const int Wo = 2 * W, Ho = 2 * H;
-    constexpr int nquads = TQH * TQW;
     constexpr int Y1P = TG::Y1P;
     // (12 rows: the phase slots start behind stage 0's activation planes, where the next tile's first chunk is landing)
     f32x4* y4 = reinterpret_cast<f32x4*>(smem_v + TG::Y4_OFF);
@@ -767,51 +768,17 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
         if constexpr (!TG::PREFETCH) { if (R == 0) write_noise(e_n, e_I0, e_J0); }     // (13 rows: behind the phase slots; read from round 0 on)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if (p.tstamps) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); te_w += t_ - te0; te0 = t_; }
-        auto quad_item = [&](const int wi) {
-            const int hq = wi * 32 + l31e;
-            const int gs = hq / nquads, qd = hq - gs * nquads;
-            const int ti = qd / TQW, tj = qd - ti * TQW;
-            if (e_I0 + ti >= H) return;
-            const int c4 = 16 * R + 8 * gs + 4 * lhe;  // the lane's four channels within the slice
-            const f32x4* ee = y4 + ((gs * 2 + lhe) * 4) * Y1P + ti * PW + tj;
-            const f32x4* eo = ee + 1 * Y1P;
-            const f32x4* oe = ee + 2 * Y1P;
-            const f32x4* oo = ee + 3 * Y1P;
-            auto fir4 = [](f32x4 a, f32x4 b, f32x4 c, f32x4 d) {
-                f32x4 q75, q25;
-                q75 = 0.75f; q25 = 0.25f;
-                return __builtin_elementwise_fma(q25, d, __builtin_elementwise_fma(q75, c, __builtin_elementwise_fma(q75, b, 0.25f * a)));
-            };
-            f32x4 ve[2][2], vo[3][2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (c < 2) {
-                    const f32x4 e0 = ee[c], e1 = ee[PW + c], o0 = oe[c], o1 = oe[PW + c], o2 = oe[2 * PW + c];
-                    ve[c][0] = fir4(o0, e0, o1, e1); ve[c][1] = fir4(e0, o1, e1, o2);
-                }
-                const f32x4 e0 = eo[c], e1 = eo[PW + c], o0 = oo[c], o1 = oo[PW + c], o2 = oo[2 * PW + c];
-                vo[c][0] = fir4(o0, e0, o1, e1); vo[c][1] = fir4(e0, o1, e1, o2);
-            }
-            const f32x4 d4 = *reinterpret_cast<const f32x4*>(s_dco + c4), b4 = *reinterpret_cast<const f32x4*>(s_bias + c4);
+        // One item per wave and round: a COLUMN RUN of quads.  A round is 32 quad columns x 2 channel groups x 2 channel halves = 128
+        // lane columns (lane = column, lane half = channel half: neighbouring lanes read neighbouring 16-byte slots) x 4 runs per
+        // column: 12 rows = 3 + 3 + 3 + 3 quads, 13 rows = 4 + 3 + 3 + 3.  Wave w takes run w / 2 of channel group w & 1, so the two
+        // 4-quad runs of a 13-row tile sit on waves 0 and 1 = SIMDs 0 and 1.  A run of n quads filters its 2 n + 3 pre-filter rows
+        // horizontally ONCE each (5 slot reads, 2 four-tap FIRs: nb_up2_hrow) in row order and keeps the last three filtered rows in
+        // registers; every output row then is one vertical FIR over four of them (nb_up2_vout): 30 FIRs and 45 slot reads per three
+        // quads instead of 42 and 75.  An output's operations do not depend on the run it falls in nor on its place there.  Quad rows
+        // below the image (ragged last tile row) end the run early -- a wave-uniform trip count.
+        // the run's quad `k`: v[dy][px] -> global memory (per quad as in modconv3x3_up2_h3_kernel: same stores, same formats)
+        auto store_quad = [&](const int gs, const int ti, const int tj, const int c4, const f32x4 (&v)[2][2]) {
             const int qi = e_I0 + ti, qj = e_J0 + tj;
-            auto act4 = [&](f32x4 o, float nz) {
-                f32x4 t = __builtin_elementwise_fma(o, d4, b4 + nz);
-                const f32x4 ta = t * p.alpha;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) t[i] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_fmed3f(t[i], ta[i], __builtin_inff()), -clampv, clampv);
-                return t;
-            };
-            f32x4 v[2][2];                            // [dy][px]
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy) {
-                const f32x2 nz = *reinterpret_cast<const f32x2*>(s_noise + (2 * ti + dy) * (2 * TQW) + 2 * tj);
-                // (the two noise values get registers of their own: see the note on v_pk_add_f32 op_sel in modconv3x3_up2_h3_kernel)
-                float nz0 = nz[0], nz1 = nz[1];
-                asm volatile("v_mov_b32 %0, %0" : "+v"(nz0));
-                asm volatile("v_mov_b32 %0, %0" : "+v"(nz1));
-                v[dy][0] = act4(fir4(vo[0][dy], ve[0][dy], vo[1][dy], ve[1][dy]), nz0);
-                v[dy][1] = act4(fir4(ve[0][dy], vo[1][dy], ve[1][dy], vo[2][dy]), nz1);
-            }
             if constexpr (OUTM == 0) {
                 if (qi < H && !(p.dbg & 1)) {
 #pragma unroll
@@ -873,13 +840,48 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
                 }
             }
         };
-        // wave-iterations of 32 quads x both channel halves per round: 12 rows 24 = 3 per wave; 13 rows 26 = 3 per wave + a fourth on
-        // waves 0 and 1 (waves w and w + 4 share a SIMD: 7, 7, 6, 6 per SIMD)
-        constexpr int NWI = nquads * 2 / 32;
-        static_assert(nquads * 2 % 32 == 0 && NWI % NW <= NW / 2, "tile quads must fill whole waves");
+        {
+            constexpr int RUN0 = TQH - 9;                                    // quads of a column's first run (the other three: 3)
+            static_assert(RUN0 == 3 || RUN0 == 4, "a tile column = four runs of 3 or 4 quads");
+            const int gs = wve & 1, run = wve >> 1;
+            const int ti0 = run ? RUN0 + 3 * (run - 1) : 0;
+            const int nq = min(run ? 3 : RUN0, H - e_I0 - ti0);               // (wave-uniform)
+            const int tj = l31e;
+            const int c4 = 16 * R + 8 * gs + 4 * lhe;                       // the lane's four channels within the slice
+            const f32x4* ee = y4 + ((gs * 2 + lhe) * 4) * Y1P + ti0 * PW + tj;
+            const f32x4* eo = ee + 1 * Y1P;
+            const f32x4* oe = ee + 2 * Y1P;
+            const f32x4* oo = ee + 3 * Y1P;
+            if (nq > 0) {
+                const f32x4 d4 = *reinterpret_cast<const f32x4*>(s_dco + c4), b4 = *reinterpret_cast<const f32x4*>(s_bias + c4);
+                f32x4 ra[2], rb[2], rc[2], rd[2], re[2];                    // filtered rows O(k), E(k), O(k + 1), E(k + 1), O(k + 2) of quad k
+                nb_up2_hrow(oe, oo, ra);
+                nb_up2_hrow(ee, eo, rb);
+                nb_up2_hrow(oe + PW, oo + PW, rc);
 #pragma unroll
-        for (int k = 0; k < NWI / NW; ++k) quad_item(wve + k * NW);
-        if constexpr (NWI % NW != 0) { if (wve < NWI % NW) quad_item(NWI / NW * NW + wve); }
+                for (int k = 0; k < RUN0; ++k) {
+                    if (k >= nq) break;
+                    const int ti = ti0 + k;
+                    f32x4 v[2][2];                        // [dy][px]
+                    float nzv[2][2];
+#pragma unroll
+                    for (int dy = 0; dy < 2; ++dy) {
+                        const f32x2 nz = *reinterpret_cast<const f32x2*>(s_noise + (2 * ti + dy) * (2 * TQW) + 2 * tj);
+                        // (the two noise values get registers of their own: see the note on v_pk_add_f32 op_sel in modconv3x3_up2_h3_kernel)
+                        nzv[dy][0] = nz[0]; nzv[dy][1] = nz[1];
+                        asm volatile("v_mov_b32 %0, %0" : "+v"(nzv[dy][0]));
+                        asm volatile("v_mov_b32 %0, %0" : "+v"(nzv[dy][1]));
+                    }
+                    nb_up2_hrow(ee + (k + 1) * PW, eo + (k + 1) * PW, rd);
+                    nb_up2_vout(ra, rb, rc, rd, d4, b4, nzv[0][0], nzv[0][1], p.alpha, clampv, v[0]);
+                    nb_up2_hrow(oe + (k + 2) * PW, oo + (k + 2) * PW, re);
+                    nb_up2_vout(rb, rc, rd, re, d4, b4, nzv[1][0], nzv[1][1], p.alpha, clampv, v[1]);
+                    store_quad(gs, ti, tj, c4, v);
+#pragma unroll
+                    for (int px = 0; px < 2; ++px) { ra[px] = rc[px]; rb[px] = rd[px]; rc[px] = re[px]; }
+                }
+            }
+        }
         if (p.tstamps) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); te_f += t_ - te0; }
     }
     NB_TSTAMP(4);
@@ -955,11 +957,13 @@ extern "C" void nb_debug_set_up2v_rows(int rows) { g_up2v_rows = rows; }
 
 // Tile height of a launch.  A full tile's K loop takes 16 block-times at both heights (4 position blocks per SIMD); 13 rows cover 8 %
 // more quads per tile, and a tile whose last rows lie below the image skips the blocks that only feed them (a SIMD's share of the
-// remaining blocks sets the loop's length).  What 13 rows cost per tile: 26 epilogue wave-iterations per round instead of 24, the
-// noise tile written behind the K loop, a cold prologue.  Estimate per launch = rounds of one workgroup per CU x mean tile time,
-// tile = 0.44 us per chunk and block-time of the critical SIMD + the rest of the tile (prologue, epilogue, store drain: 18.5 us at 12
-// rows, 19.7 at 13) -- both from the phase stamps (profiles/r07_phase_times.txt), rough: single launches of one shape differ by up
-// to ~7 % between visits, so the 2 % margin is a tie-breaker, not a noise bound; 13 rows where the estimate is >= 2 % lower.
+// remaining blocks sets the loop's length).  What 13 rows cost per tile: a 4-quad run instead of a 3-quad one on two waves of the
+// epilogue (SIMDs 0 and 1), the noise tile written behind the K loop, a cold prologue.  Estimate per launch = rounds of one workgroup
+// per CU x mean tile time, tile = 0.44 us per chunk and block-time of the critical SIMD + the rest of the tile (prologue, epilogue,
+// store drain: 18.5 us at 12 rows, 19.7 at 13) -- both from the phase stamps of the per-quad epilogue (profiles/r07_phase_times.txt),
+// rough: single launches of one shape differ by up to ~7 % between visits, so the 2 % margin is a tie-breaker, not a noise bound; 13
+// rows where the estimate is >= 2 % lower.  The column-run epilogue (round 8) takes ~2 us off the rest at 13 rows
+// (profiles/r08_phase_times.txt); 12-row stamps of it have not been taken, so the two constants stand as fitted: they move together.
 static int nb_up2v_rows(int nchunks, int n, int h, int w, int slices, long ncu) {
     auto est = [&](int tqh, double rest) {
         const int tiles_y = (h + tqh - 1) / tqh;
