@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _lock = threading.Lock()
 _lib = None
@@ -66,6 +66,7 @@ PROTOTYPES = {
     "nb_styles_noise_f32": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
     "nb_demod_coefs_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "nb_noise_f32": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
+    "nb_noise_seeded_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp]),
     "nb_norm_positions_f32": (C.c_int, [vp, C.c_int, vp, C.c_int, vp]),
     "nb_modconv3x3_f32": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int64, vp, vp,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp]),
@@ -193,7 +194,8 @@ class NbGeneratorLayerInfo(C.Structure):
 class NbGeneratorInputs(C.Structure):
     """``struct NbGeneratorInputs``."""
     _fields_ = [("z", vp), ("ws", vp), ("truncation_psi", C.c_float), ("truncation_cutoff", C.c_int32), ("geom", vp * 4),
-                ("positions", vp), ("noise_mode", C.c_int32), ("render_mode", C.c_int32), ("user_colors", vp), ("sfactor", vp)]
+                ("positions", vp), ("noise_mode", C.c_int32), ("render_mode", C.c_int32), ("user_colors", vp), ("sfactor", vp),
+                ("noise_seed", C.c_uint64), ("noise_offset", C.c_uint64), ("noise_state", vp)]
 
 
 class NbGeneratorOutputs(C.Structure):
@@ -241,7 +243,7 @@ NB_GEOM_PREP_WS_BYTES = 1040
 
 NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3
 NB_CONV_MODES = {"f32": 0, "h3": 1, "f8": 2, "f6": 3, "f16": 4}
-NB_NOISE_MODES = {"const": 0, "none": 1, "random": 2}
+NB_NOISE_MODES = {"const": 0, "none": 1, "random": 2, "seeded": 3}
 NB_RENDER_MODES = {"clear": 0, "full": 1}
 NB_GEOM_PREPROC = {None: 0, "none": 0, "-11inverse": 1, "inverse": 2}      # encoder.HipGeometryEncoder's preproc_type strings
 

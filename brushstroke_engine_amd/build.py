@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libneube_hip.so")
 SOURCES = ["nb_ops.hip", "nb_modconv.hip", "nb_modconv_h3.hip", "nb_modconv_up2v.hip", "nb_modconv_small.hip", "nb_grad.hip", "nb_canvas.hip", "nb_encoder.hip", "nb_calib.hip",
-           "nb_generator.hip", "nb_geomprep.hip"]
+           "nb_generator.hip", "nb_geomprep.hip", "nb_noise_seeded.hip"]
 HEADERS = ["nb_common.h", "nb_h3_common.h", "nb_torgb.h", os.path.join("..", "..", "include", "neube_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
@@ -30,9 +30,11 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-fn
 # nb_modconv_up2v.hip (round 4): their packed fp32 arithmetic is explicit (f32x4 / f32x2 vector types); SLP paired
 # the two scalar `x * gain` of the prologue into a swizzled v_pk_mul_f32 (tests/test_abi.py scans for any such form).
 # nb_geomprep.hip: byte-exact scalar fp32 per pixel; SLP paired the gray values of neighbouring pixels into packed instructions.
+# nb_noise_seeded.hip: scalar fp32 per pixel, two Box-Muller pairs per thread; SLP paired them (un-swizzled forms only when this was
+# written, but nothing in the kernel wants packed arithmetic).
 FILE_FLAGS = {"nb_modconv.hip": ["-fno-slp-vectorize"], "nb_ops.hip": ["-fno-slp-vectorize"],
               "nb_modconv_up2v.hip": ["-fno-slp-vectorize"], "nb_generator.hip": ["-fno-slp-vectorize"],
-              "nb_geomprep.hip": ["-fno-slp-vectorize"]}
+              "nb_geomprep.hip": ["-fno-slp-vectorize"], "nb_noise_seeded.hip": ["-fno-slp-vectorize"]}
 
 
 STAMP = LIB + ".stamp"

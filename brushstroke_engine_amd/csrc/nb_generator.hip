@@ -599,7 +599,7 @@ struct WalkSink {
 // bit gi of *handed for every feature it wrote into its consumer's operand tensor itself.
 using GeomHook = std::function<int(const NbPassPlan&, unsigned* handed)>;
 
-// One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant or no noise, no feature taps / blending),
+// One forward pass: SynthesisNetwork._prepare + _run_layers for render_triad (constant, seeded or no noise, no feature taps / blending),
 // following the pass's plan.  stage (validated by the caller) makes it one half of the painting engine's split: stop_res = the pass of
 // `_stop_after` (ends with block stop_res, whose last layer writes stage->features_out; no ToRGB), resume_res = the pass of `_resume`
 // (starts behind block resume_res from stage->features_in).
@@ -610,7 +610,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     const int nL = (int)specs.size(), R = cfg.R, w_dim = cfg.c.w_dim;
     const float clamp = cfg.c.conv_clamp < 0.f ? -1.f : cfg.c.conv_clamp;
     const float alpha = 0.2f, gain = g->act_gain;
-    const bool cnoise = in->noise_mode == NB_NOISE_CONST;
+    const bool cnoise = in->noise_mode == NB_NOISE_CONST, snoise = in->noise_mode == NB_NOISE_SEEDED;
     const int64_t* ipos = cnoise ? in->positions : nullptr;
     const int stop_res = stage ? stage->stop_res : 0, resume_res = stage ? stage->resume_res : 0;
     const NbGeneratorOutputs no_outputs{};
@@ -649,7 +649,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         GEN_TRY(nb_styles_noise_f32(g->table(inkernel_from < 0 ? nL : inkernel_from), n_tab, ws, cfg.num_ws, w_dim, nullptr, ipos, R, n, st));
     } else {
         GEN_TRY((plan.styles_fast ? nb_styles_fast_f32 : nb_styles_f32)(g->table(nL), n_tab, ws, cfg.num_ws, w_dim, n, st));
-        if (cnoise) {
+        if (cnoise || snoise) {
             // only the layers this pass runs: a head needs no noise image behind its last block, a tail none of the skipped blocks
             int lo = 0, hi = n_tab;
             for (int i = 0; i < nL; ++i) lo += resume_res && specs[i].block_res <= resume_res;
@@ -657,11 +657,16 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
                 hi = 0;
                 for (int i = 0; i < nL; ++i) hi += specs[i].block_res <= stop_res;
             }
-            if (inkernel_from >= 0) hi = std::min(hi, inkernel_from);
+            if (inkernel_from >= 0) hi = std::min(hi, inkernel_from);      // (constant noise with positions only)
             int max_res = 0;
             for (int i = lo; i < std::min(hi, nL); ++i) max_res = std::max(max_res, specs[i].block_res);
-            if (hi > lo && max_res > 0)
-                GEN_TRY(nb_noise_f32(g->table(nL) + lo, hi - lo, max_res, npos_k, npos_k ? nullptr : ipos, R, n, st));
+            if (hi > lo && max_res > 0) {
+                if (snoise)       // every layer's random image, per sample; the layer index stays absolute in a staged pass
+                    GEN_TRY(nb_noise_seeded_f32(g->table(nL) + lo, lo, hi - lo, max_res, in->noise_seed, in->noise_offset, in->noise_state,
+                                                n, st));
+                else
+                    GEN_TRY(nb_noise_f32(g->table(nL) + lo, hi - lo, max_res, npos_k, npos_k ? nullptr : ipos, R, n, st));
+            }
         }
     }
 
@@ -729,9 +734,9 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
             nsrc = NbNoiseSrc{d.noise_const_t, d.noise_lin, d.noise_strength, npos_k, npos_k ? nullptr : ipos, res, R};
             noise = (const float*)&nsrc;
             nstride = NB_NOISE_IN_KERNEL;
-        } else if (cnoise) {
+        } else if (cnoise || snoise) {
             noise = d.noise;
-            nstride = shared ? 0 : (int64_t)res * res;
+            nstride = (cnoise && shared) ? 0 : (int64_t)res * res;
         }
         const bool is_last = res == R;
         const bool head_last = stop_res && s.up == 1 && res == stop_res;      // the tapped layer: fp32 into the caller's buffer
@@ -1055,7 +1060,7 @@ int check_forward(NbGenerator* gen, const NbGeneratorInputs* in, int n, void* st
 }
 
 int check_modes_and_device(NbGenerator* gen, const NbGeneratorInputs* in, void* stream, const char* who) {
-    if (in->noise_mode != NB_NOISE_CONST && in->noise_mode != NB_NOISE_NONE) {
+    if (in->noise_mode != NB_NOISE_CONST && in->noise_mode != NB_NOISE_NONE && in->noise_mode != NB_NOISE_SEEDED) {
         nb_set_error("%s: noise_mode %d not supported (const and none are)", who, in->noise_mode);
         return in->noise_mode == NB_NOISE_RANDOM ? NB_EUNSUPPORTED : NB_EINVAL;
     }

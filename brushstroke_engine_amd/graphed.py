@@ -21,7 +21,8 @@ class GraphedTriadRender:
     """Capture ``Generator.render_triad`` for a fixed batch size; call it like a function."""
 
     def __init__(self, G: Generator, batch: int = 1, render_mode: str = "clear", use_ws: bool = False,
-                 use_positions: bool = True, want_f32: bool = False, warmup: int = 3, plan_slot: Optional[int] = None):
+                 use_positions: bool = True, want_f32: bool = False, warmup: int = 3, plan_slot: Optional[int] = None,
+                 noise_mode: str = "const"):
         cfg = G.cfg
         dev = G.synthesis.get_last_block().conv1.weight.device
         assert dev.type == "cuda"
@@ -34,6 +35,14 @@ class GraphedTriadRender:
         self.user_colors = torch.full([batch, 3, 3], float("nan"), dtype=torch.float32, device=dev)
         self._kw = dict(geom_feature=self.geom, positions=self.positions, render_mode=render_mode,
                         user_colors=self.user_colors, want_u8=True, want_f32=want_f32)
+        self.noise_state = None
+        if noise_mode == "seeded":
+            # [seed, offset] as a graph input: every replay draws the noise of the values it holds then (nb_noise_seeded_f32)
+            self.noise_state = torch.zeros([2], dtype=torch.int64, device=dev)
+            self._noise_host = [0, 0]
+            self._kw.update(noise_mode="seeded", noise_state=self.noise_state)
+        elif noise_mode != "const":
+            raise ValueError(f"GraphedTriadRender: noise_mode {noise_mode!r} (const and seeded can be captured)")
         if plan_slot is not None:
             # own workspace: graphs that replay concurrently on different streams must not share one (slot 0 is the
             # default of eager calls; the sub-batch streams of an eager split call use 1 .. sub_streams)
@@ -56,7 +65,7 @@ class GraphedTriadRender:
         return self.G.render_triad(z=self.z, **self._kw)
 
     def set_inputs(self, z=None, ws=None, geom_feature: Optional[List[torch.Tensor]] = None, positions=None,
-                   user_colors=None) -> None:
+                   user_colors=None, noise_seed=None, noise_offset=None) -> None:
         if z is not None:
             self.z.copy_(z)
         if ws is not None:
@@ -68,6 +77,14 @@ class GraphedTriadRender:
             self.positions.copy_(positions)
         if user_colors is not None:
             self.user_colors.copy_(user_colors)
+        if noise_seed is not None or noise_offset is not None:
+            if self.noise_state is None:
+                raise ValueError("noise_seed / noise_offset need noise_mode='seeded'")
+            for k, v in enumerate((noise_seed, noise_offset)):
+                if v is not None:
+                    v = int(v) & ((1 << 64) - 1)
+                    self._noise_host[k] = v - (1 << 64) if v >= 1 << 63 else v      # the uint64's bits as int64
+            self.noise_state.copy_(torch.tensor(self._noise_host, dtype=torch.int64))
 
     def replay(self):
         self.graph.replay()
@@ -76,3 +93,6 @@ class GraphedTriadRender:
     def __call__(self, **inputs):
         self.set_inputs(**inputs)
         return self.replay()
+
+
+GraphedTriad = GraphedTriadRender

@@ -17,6 +17,7 @@ from . import _lib
 from .config import GeneratorConfig, LayerSpec
 
 _p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+_U64 = (1 << 64) - 1
 
 
 def native_config(cfg: GeneratorConfig) -> "_lib.NbGeneratorConfig":
@@ -169,12 +170,13 @@ class NativeGenerator:
 
     def forward_into(self, outputs: dict, n: int, z=None, ws=None, geom_feature: Sequence = (), positions=None, noise_mode="const",
                      render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0, truncation_cutoff=None, geom=None,
-                     stage=None):
+                     stage=None, noise_seed=0, noise_offset=0, noise_state=None):
         """Enqueue one forward on the current stream into caller-allocated ``outputs`` (keys rgba_u8 / rgba / img / uvs / colors;
         missing = not wanted).  Inputs must already be device tensors of the right dtype and shape (nothing is converted here):
         the form for graph capture.  ``geom``: stroke patches [n, 1, R, R] fp32 for the attached encoder, instead of
         ``geom_feature``.  ``stage``: an ``_lib.NbGeneratorStage`` for one half of a split pass
-        (nb_generator_forward_staged; :meth:`head` / :meth:`tail` build it)."""
+        (nb_generator_forward_staged; :meth:`head` / :meth:`tail` build it).  ``noise_mode="seeded"``: sample k draws the noise of
+        (``noise_seed``, ``noise_offset`` + k), or of the two values in ``noise_state`` (int64[2] device tensor) when given."""
         if geom is not None and len(geom_feature):
             raise ValueError("pass either geom (stroke patches) or geom_feature, not both")
         ins = _lib.NbGeneratorInputs()
@@ -189,6 +191,8 @@ class NativeGenerator:
             raise RuntimeError(f"Unknown render mode for TriadGanPaintEngine: {render_mode}")
         ins.render_mode = _lib.NB_RENDER_MODES[render_mode]
         ins.user_colors, ins.sfactor = _p(user_colors), _p(sfactor)
+        ins.noise_seed, ins.noise_offset = int(noise_seed) & _U64, int(noise_offset) & _U64
+        ins.noise_state = _p(noise_state)
         outs = _lib.NbGeneratorOutputs()
         for k in ("rgba_u8", "rgba", "img", "uvs", "colors"):
             setattr(outs, k, _p(outputs.get(k)))
@@ -204,7 +208,8 @@ class NativeGenerator:
                            "generator_forward_geom")
 
     def render_triad(self, z=None, ws=None, geom_feature=None, positions=None, render_mode="clear", user_colors=None, want_u8=True,
-                     want_f32=False, sfactor=None, noise_mode="const", truncation_psi=1.0, truncation_cutoff=None, geom=None):
+                     want_f32=False, sfactor=None, noise_mode="const", truncation_psi=1.0, truncation_cutoff=None, geom=None,
+                     noise_seed=0, noise_offset=0, noise_state=None):
         """Generator.render_triad through the C entry: (rgba_u8 [N,R,R,4] | None, rgba [N,4,R,R] | None, {uvs, colors, img}).
         ``geom``: stroke patches [N, 1, R, R] (1 = background) for the attached encoder (:meth:`attach_encoder`), instead of the
         encoded ``geom_feature``."""
@@ -245,7 +250,8 @@ class NativeGenerator:
         if want_f32:
             outs["rgba"] = torch.empty([n, 4, r, r], dtype=torch.float32, device=dev)
         self.forward_into(outs, n, z=z, ws=ws, geom_feature=geom, positions=pos, noise_mode=noise_mode, render_mode=render_mode,
-                          user_colors=user, sfactor=sfac, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, geom=patches)
+                          user_colors=user, sfactor=sfac, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, geom=patches,
+                          noise_seed=noise_seed, noise_offset=noise_offset, noise_state=noise_state)
         # the inputs converted here are read by work enqueued on the current stream: keep them alive for it
         cur = torch.cuda.current_stream(dev)
         for t in [z, ws, pos, user, sfac, patches] + geom:
@@ -255,25 +261,27 @@ class NativeGenerator:
 
     # ---- staged passes: the generator split around the feature-canvas blend (painting.PaintingHelper._schedule) ----
     def head(self, n: int, stop_res: int, features_out, z=None, ws=None, geom_feature: Sequence = (), geom=None, positions=None,
-             noise_mode="const", truncation_psi=1.0, truncation_cutoff=None):
+             noise_mode="const", truncation_psi=1.0, truncation_cutoff=None, noise_seed=0, noise_offset=0, noise_state=None):
         """Enqueue the pass up to block ``stop_res`` (``forward_pre_mapped(_stop_after=stop_res)``): the block's fp32 output, before
         blending, goes into ``features_out`` [n, channels(stop_res), stop_res, stop_res].  Device tensors of the right dtype and
         shape, as :meth:`forward_into` takes them."""
         stage = _lib.NbGeneratorStage(int(stop_res), 0, _p(features_out), None)
         self.forward_into({}, n, z=z, ws=ws, geom_feature=geom_feature, positions=positions, noise_mode=noise_mode,
-                          truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, geom=geom, stage=stage)
+                          truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, geom=geom, stage=stage,
+                          noise_seed=noise_seed, noise_offset=noise_offset, noise_state=noise_state)
         return features_out
 
     def tail(self, n: int, resume_res: int, features_in, outputs: dict, z=None, ws=None, geom_feature: Sequence = (), geom=None,
              positions=None, noise_mode="const", render_mode="clear", user_colors=None, sfactor=None, truncation_psi=1.0,
-             truncation_cutoff=None):
+             truncation_cutoff=None, noise_seed=0, noise_offset=0, noise_state=None):
         """Enqueue the pass behind block ``resume_res`` (``render_triad(_resume=(resume_res, features_in))``) into the caller's
         ``outputs`` (keys as :meth:`forward_into`).  Only the geometry features at resolutions >= ``resume_res`` are read
         (``geom_feature`` entries below may be None)."""
         stage = _lib.NbGeneratorStage(0, int(resume_res), None, _p(features_in))
         self.forward_into(outputs, n, z=z, ws=ws, geom_feature=geom_feature, positions=positions, noise_mode=noise_mode,
                           render_mode=render_mode, user_colors=user_colors, sfactor=sfactor, truncation_psi=truncation_psi,
-                          truncation_cutoff=truncation_cutoff, geom=geom, stage=stage)
+                          truncation_cutoff=truncation_cutoff, geom=geom, stage=stage, noise_seed=noise_seed,
+                          noise_offset=noise_offset, noise_state=noise_state)
         return outputs
 
 

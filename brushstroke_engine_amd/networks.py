@@ -253,6 +253,21 @@ class _KernelPlan:
         self.geom = [types.SimpleNamespace(**{k: getattr(gp, k) for k, _ in gp._fields_}) for gp in raw.geom[:raw.num_geom]]
 
 
+_U64 = (1 << 64) - 1
+
+
+def _seeded_kwargs(noise_seed, noise_offset, noise_state) -> dict:
+    """The public seeded-noise keywords (``noise_seed=``, ``noise_offset=0``, ``noise_state=``) as the synthesis pass's private ones."""
+    kw = {}
+    if noise_seed is not None:
+        kw["_noise_seed"] = (noise_seed, noise_offset)
+    elif noise_offset:
+        raise ValueError("noise_offset needs noise_seed")
+    if noise_state is not None:
+        kw["_noise_state"] = noise_state
+    return kw
+
+
 def _res_mask(resolutions) -> int:
     """Block resolutions -> NbPlanOptions bit mask (bit log2(res))."""
     return sum({1 << (int(r).bit_length() - 1) for r in resolutions if r})
@@ -283,8 +298,14 @@ class _PassOptions:
     prepare_only: bool = False
     prepared: Optional[dict] = None
     mark: Optional[tuple] = None
+    # noise_mode "seeded" (this build's reproducible form of "random": nb_noise_seeded_f32, include/neube_hip.h): sample k of the
+    # batch draws the noise of (seed, offset + k).  `_noise_seed=(seed, offset)`, or `_noise_state` = an int64[2] device tensor
+    # holding the two (a captured graph draws fresh noise by overwriting it before a replay); exactly one of them
+    noise_seed: Optional[tuple] = None
+    noise_state: Optional[torch.Tensor] = None
 
     _KEYS = {"noise_mode": "noise_mode", "norm_noise_positions": "norm_noise_positions", "_positions": "positions",
+             "_noise_seed": "noise_seed", "_noise_state": "noise_state",
              "_extra_outputs": "extra", "_stop_after": "stop_after", "_resume": "resume", "_plan_slot": "plan_slot",
              "_reuse_styles": "reuse_styles", "_prepare_only": "prepare_only", "_prepared": "prepared", "_mark": "mark"}
 
@@ -296,8 +317,15 @@ class _PassOptions:
         o = cls(**{field: kw.pop(key) for key, field in cls._KEYS.items() if key in kw})
         if kw:
             raise TypeError(f"unexpected synthesis kwargs: {sorted(kw)}")
-        if o.noise_mode not in ("random", "const", "none"):
+        if o.noise_mode not in ("random", "const", "none", "seeded"):
             raise AssertionError(f"noise_mode {o.noise_mode!r}")
+        if o.noise_mode == "seeded":
+            if (o.noise_seed is None) == (o.noise_state is None):
+                raise ValueError("noise_mode 'seeded' needs exactly one of a seed (noise_seed / noise_offset) and noise_state")
+            if o.noise_seed is not None:
+                o.noise_seed = (int(o.noise_seed[0]) & _U64, int(o.noise_seed[1]) & _U64)
+        elif o.noise_seed is not None or o.noise_state is not None:
+            raise ValueError(f"a noise seed / noise_state needs noise_mode 'seeded', not {o.noise_mode!r}")
         return o
 
 
@@ -570,6 +598,8 @@ class SynthesisNetwork(torch.nn.Module):
         if opts.prepared is not None:
             return                                  # styles, coefficients and noise images are in the workspace slot already
         if opts.reuse_styles:
+            if noise_mode == "seeded":
+                raise RuntimeError("_reuse_styles: a seeded pass writes its own noise images")
             if resume is None or (inkernel_from is None and noise_mode == "const") or table is not plan.table:
                 raise RuntimeError("_reuse_styles needs a resumed pass whose layers compute their noise themselves")
             if any(i_ < inkernel_from for i_, sp in enumerate(cfg.layers) if sp.block_res > resume[0]) and noise_mode == "const":
@@ -583,16 +613,27 @@ class SynthesisNetwork(torch.nn.Module):
             return
         styles_fn = lib.nb_styles_fast_f32 if ps.kplan.styles_fast else lib.nb_styles_f32
         _lib.check(styles_fn(_p(plan.table), plan.n_layers, _p(ps.ws), self.num_ws, self.w_dim, n, stream), "styles")
-        if noise_mode == "const":
+        if noise_mode in ("const", "seeded"):
             # only the layers this pass runs (the tiled-canvas schedule splits the generator at R/2: the head pass
             # needs no 256x256 noise images, the tail pass nothing but those); layers are ordered by resolution
             lo_ = 0 if resume is None else sum(1 for sp in cfg.layers if sp.block_res <= resume[0])
             hi_ = plan.n_layers if stop_after is None else sum(1 for sp in cfg.layers if sp.block_res <= stop_after)
             # layers on the large split-f16 kernels compute their shifted noise themselves (NbNoiseSrc): the noise
             # launch stops at the first of them (layers are ordered by resolution, eligibility grows with it)
-            if inkernel_from is not None:
+            if inkernel_from is not None:           # (constant noise with positions only)
                 hi_ = min(hi_, inkernel_from)
-            if hi_ > lo_ and cfg.layers[lo_:hi_]:       # (a pass resumed behind the last block runs no layer)
+            if noise_mode == "seeded":
+                # every layer's random image in one launch (no torch.randn, no allocation); the layer index stays absolute
+                if hi_ > lo_ and cfg.layers[lo_:hi_]:
+                    state = opts.noise_state
+                    if state is not None and (state.device != ps.device or state.dtype != torch.int64 or tuple(state.shape) != (2,)
+                                              or not state.is_contiguous()):
+                        raise ValueError("noise_state: an int64 tensor [seed, offset] on the generator's device")
+                    seed, offset = (0, 0) if state is not None else opts.noise_seed
+                    _lib.check(lib.nb_noise_seeded_f32(table.data_ptr() + lo_ * ctypes.sizeof(_lib.NbLayerDesc), lo_, hi_ - lo_,
+                                                       max(sp.block_res for sp in cfg.layers[lo_:hi_]), seed, offset, _p(state), n,
+                                                       stream), "noise_seeded")
+            elif hi_ > lo_ and cfg.layers[lo_:hi_]:       # (a pass resumed behind the last block runs no layer)
                 _lib.check(lib.nb_noise_f32(table.data_ptr() + lo_ * ctypes.sizeof(_lib.NbLayerDesc), hi_ - lo_,
                                             max(sp.block_res for sp in cfg.layers[lo_:hi_]), _p(npos), _p(ipos),
                                             self.img_resolution, n, stream), "noise")
@@ -728,6 +769,8 @@ class SynthesisNetwork(torch.nn.Module):
         elif noise_mode == "const":
             noise_ptr = plan.noise[i].data_ptr()
             nstride = 0 if ps.shared else s.block_res * s.block_res
+        elif noise_mode == "seeded":
+            noise_ptr, nstride = plan.noise[i].data_ptr(), s.block_res * s.block_res
         elif noise_mode == "random":
             rnd = torch.randn([n, s.block_res, s.block_res], device=device) * layer.noise_strength
             ps.keep_alive.append(rnd)
@@ -1038,7 +1081,11 @@ class Generator(torch.nn.Module):
         return Generator(cfg, random_state_dict(cfg, seed)).to(device)
 
     def forward_pre_mapped(self, ws, geom_feature, positions=None, return_debug_data=False, return_features=None,
-                           blended_features=None, noise_buffers=None, **synthesis_kwargs):
+                           blended_features=None, noise_buffers=None, noise_seed=None, noise_offset=0, noise_state=None,
+                           **synthesis_kwargs):
+        # noise_mode="seeded" (this build's reproducible 'random'): sample k draws the noise of (noise_seed, noise_offset + k), or of
+        # the two values in the int64[2] device tensor noise_state
+        synthesis_kwargs.update(_seeded_kwargs(noise_seed, noise_offset, noise_state))
         # networks_modified.py:351-353 normalises positions here; this build hands the integer positions to
         # nb_noise_f32, which does the same (positions % R)/(R-1) in correctly rounded fp32 (see neube_hip.h)
         n = ws.shape[0]
@@ -1089,6 +1136,7 @@ class Generator(torch.nn.Module):
         extra = kw.pop("_extra_outputs", None)
         resume = kw.pop("_resume", None)
         npos = kw.pop("norm_noise_positions", None)
+        nseed, nstate = kw.pop("_noise_seed", None), kw.pop("_noise_state", None)      # seeded noise: sample k of the WHOLE batch
         kw_join = kw.pop("_join", True)
         if self._side_streams is None or self._side_streams[0].device != dev:
             self._side_streams = [torch.cuda.Stream(device=dev) for _ in range(self.sub_streams)]
@@ -1109,6 +1157,11 @@ class Generator(torch.nn.Module):
             if lazy_geom is not None and torch.is_tensor(lazy_geom.geom) and lazy_geom.geom.is_cuda:
                 lazy_geom.geom.record_stream(st)
             with torch.cuda.stream(st):
+                if nseed is not None:
+                    kw["_noise_seed"] = (nseed[0], int(nseed[1]) + a)
+                if nstate is not None:
+                    nstate.record_stream(st)
+                    kw["_noise_state"] = torch.stack([nstate[0], nstate[1] + a])
                 res = self.synthesis(ws[a:b], lazy_geom.sliced(a, b) if lazy_geom is not None else [g[a:b] for g in geom_feature],
                                      pos_encoding=None,
                                      return_debug_data=return_debug_data, return_features=return_features, **kw,
@@ -1124,16 +1177,17 @@ class Generator(torch.nn.Module):
 
     def forward(self, z, c, geom_feature, positions=None, noise_buffers=None, truncation_psi=1, truncation_cutoff=None,
                 return_debug_data=False, return_features=None, blended_features=None, style_mixing_prob=0,
-                **synthesis_kwargs):
+                noise_seed=None, noise_offset=0, noise_state=None, **synthesis_kwargs):
         ws = self.mapping(z, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
         if style_mixing_prob > 0:
             ws = mix_styles(self.mapping, ws, z, c, style_mixing_prob, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
         return self.forward_pre_mapped(ws, geom_feature, positions=positions, return_debug_data=return_debug_data,
                                        return_features=return_features, blended_features=blended_features,
-                                       noise_buffers=noise_buffers, **synthesis_kwargs)
+                                       noise_buffers=noise_buffers, noise_seed=noise_seed, noise_offset=noise_offset,
+                                       noise_state=noise_state, **synthesis_kwargs)
 
     def render_triad(self, z=None, ws=None, geom_feature=None, positions=None, render_mode="clear", user_colors=None,
-                     want_u8=True, want_f32=False, sfactor=None, join=True, **kw):
+                     want_u8=True, want_f32=False, sfactor=None, join=True, noise_seed=None, noise_offset=0, noise_state=None, **kw):
         """Generator + the paint engine's compositing (brush.py:763-792) fused into the ToRGB launch.
         Returns (rgba_u8 [N,R,R,4] | None, rgba_f32 [N,4,R,R] | None, debug dict with uvs/colors).
         ``join=False`` (throughput loops): when the batch runs as sub-batches on side streams, returns a callable that
@@ -1141,6 +1195,7 @@ class Generator(torch.nn.Module):
         extra = {"rgba_u8": want_u8, "rgba": want_f32, "render_mode": render_mode, "user_colors": user_colors,
                  "sfactor": sfactor}
         kw.setdefault("noise_mode", "const")
+        kw.update(noise_seed=noise_seed, noise_offset=noise_offset, noise_state=noise_state)
         if ws is None:
             res = self.forward(z, None, geom_feature, positions=positions, return_debug_data=True,
                                _extra_outputs=extra, _join=join, **kw)

@@ -197,6 +197,28 @@ int nb_demod_coefs_f32(const float* styles, const float* wsq, float* dcoefs, int
 int nb_noise_f32(const NbLayerDesc* layers_dev, int n_layers, int max_res, const float* norm_pos,
                  const int64_t* positions, int img_resolution, int n, void* stream);
 
+/* Seeded random noise of all layers in one launch: SynthesisLayer's noise_mode 'random' (training/networks.py:369-370:
+ * torch.randn([n, 1, res, res]) * noise_strength) with a counter-based generator in place of torch's global one, so that the
+ * draw is a pure function of (seed, sample, layer, pixel): the same sample gets the same noise at any batch size, on any rank,
+ * from Python or C, and in every replay of a captured graph.  Positions play no part, as in the reference's random mode.
+ * For table row i (layer l = first_layer + i: the index in the generator's layer list, absolute even when a table + lo is
+ * passed), sample k < n and pixel quad q (pixels 4q .. 4q+3 of the row-major res * res image):
+ *     s = offset + k                                                  (uint64, wraps)
+ *     (x0, x1, x2, x3) = Philox4x32-10(counter = (q, l, lo32(s), hi32(s)), key = (lo32(seed), hi32(seed)))
+ *         (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds)
+ *     pair(a, b): u1 = ((a >> 8) + 1) * 2^-24 in (0, 1], u2 = (b >> 8) * 2^-24 in [0, 1)   (both exact in fp32)
+ *                 r = sqrtf(-2 logf(u1)); (z_even, z_odd) = (r cospif(2 u2), r sinpif(2 u2))   (accurate library functions)
+ *     pixels 4q, 4q+1 = pair(x0, x1); pixels 4q+2, 4q+3 = pair(x2, x3)
+ *     noise_out[k, pixel] = z * noise_strength[0]       (one fp32 multiply; noise_strength == NULL: z itself)
+ * So sample k at offset o is sample 0 at offset o + k.  Rows whose noise_out is NULL are skipped (the ToRGB row); only res,
+ * noise_out and noise_strength of a row are read.  res * res need not be a multiple of 4.  state_dev: NULL, or a device pointer
+ * to {seed, offset}; then the kernel reads the two from there and ignores the by-value arguments (a captured graph draws fresh
+ * noise by writing 16 bytes before a replay).  Enqueue only.  max_res = largest res in the table (it sizes the grid; the result
+ * does not depend on it), at most 32768. */
+#define NB_NOISE_SEEDED 3
+int nb_noise_seeded_f32(const NbLayerDesc* layers_dev, int first_layer, int n_layers, int max_res, uint64_t seed, uint64_t offset,
+                        const uint64_t* state_dev, int n, void* stream);
+
 /* The first step of that arithmetic on its own: positions [n,2] int64 -> norm_pos_out [n,2] float32 = ((p mod R) / (R - 1)), the values
  * nb_noise_f32 derives internally (networks.py:371-374; same function, same bits).  For callers that hand NbNoiseSrc to the split-f16
  * convolutions: those evaluate the normalisation at the top of every tile, and from `positions` that is four 64-bit modulo operations
@@ -634,7 +656,8 @@ typedef struct NbGeneratorLayerInfo { /* config.LayerSpec */
 #define NB_CONV_F16 4
 #define NB_NOISE_CONST  0             /* noise_mode */
 #define NB_NOISE_NONE   1
-#define NB_NOISE_RANDOM 2             /* -> NB_EUNSUPPORTED */
+#define NB_NOISE_RANDOM 2             /* -> NB_EUNSUPPORTED (torch's global generator has no counterpart here) */
+/*      NB_NOISE_SEEDED 3                reproducible random noise: nb_noise_seeded_f32 (defined there) */
 #define NB_RENDER_CLEAR 0             /* render_mode: alpha = u + v / 1 (nb_torgb_triad_f32) */
 #define NB_RENDER_FULL  1
 
@@ -662,10 +685,16 @@ typedef struct NbGeneratorInputs {
     int32_t truncation_cutoff;        /* < 0 = every ws */
     const float* geom[4];             /* geometry features [n, geom_channels[k], res_k, res_k] fp32, one per feature */
     const int64_t* positions;         /* [n, 2] (y, x) patch positions, or NULL (no positional noise shift) */
-    int32_t noise_mode;               /* NB_NOISE_CONST / NB_NOISE_NONE */
+    int32_t noise_mode;               /* NB_NOISE_CONST / NB_NOISE_NONE / NB_NOISE_SEEDED */
     int32_t render_mode;              /* NB_RENDER_CLEAR / NB_RENDER_FULL */
     const float* user_colors;         /* [n, 3, 3] or NULL; NaN entries = the style's own colour */
     const float* sfactor;             /* [n] or NULL */
+    /* NB_NOISE_SEEDED: every layer that runs gets nb_noise_seeded_f32's image of (noise_seed, noise_offset + sample index, its
+     * absolute layer index), written by one launch in front of the layers (whole, geometry and staged passes alike; positions are
+     * ignored).  noise_state: NULL, or a device pointer to {seed, offset} that replaces the two by-value fields -- the form for a
+     * captured graph.  Other modes ignore the three. */
+    uint64_t noise_seed, noise_offset;
+    const uint64_t* noise_state;
 } NbGeneratorInputs;
 
 typedef struct NbGeneratorOutputs {   /* device pointers; NULL = not wanted */
