@@ -152,7 +152,10 @@ def test_f8_tiled_canvas_matches_reference():
 def test_up2_tile_heights_agree(fmt, ci, co, h, w):
     """The up=2 split-f16 kernel has three tile heights (12 quad rows for throughput, 8 where those would end in a mostly
     empty round of workgroups, 5 for under-filled launches such as batch 1).  Both walk the same per-pixel arithmetic, so fp32 and hand-off outputs must be bit-identical; 24 rows do
-    not divide by 5 (overhanging last tile)."""
+    not divide by 5 (overhanging last tile).
+    The cases 8 x 8 and 16 x 16 cannot tell the forms apart: nb_up2_h3_select sends w == 8 and w == 16 to the 8-wide / 16-wide
+    instantiation whatever the hooks say, so there the five launches are one kernel compared with itself (they check that it is
+    deterministic).  Those two forms, and every tile height, are held to float64 by tests/test_hip_conv_forms_f64.py."""
     from brushstroke_engine_amd import _lib, ops
     rs = np.random.RandomState(ci + h + fmt)
     n = 2
@@ -204,7 +207,11 @@ def test_up2_tile_heights_agree(fmt, ci, co, h, w):
 @pytest.mark.parametrize("ci,co,h,w", [(128, 128, 32, 64), (64, 64, 48, 32), (48, 64, 32, 32), (16, 128, 16, 32), (40, 64, 32, 32)])
 def test_up1_rows_per_wave_agree(fmt, ci, co, h, w):
     """The 8-wave up=1 split-f16 kernel runs with 2 (throughput) or 1 (under-filled launches, batch 1) pixel rows per
-    wave; same per-pixel arithmetic, so fp32 and hand-off outputs must be bit-identical."""
+    wave; same per-pixel arithmetic, so fp32 and hand-off outputs must be bit-identical.
+    With H2 operands (fmt 0) the cases 32 x 32 and 16 x 32 cannot tell the forms apart: nb_up1_h3_impl sends H2 launches on images
+    of at most 32 x 32 pixels to modconv3x3_up1_h3s_kernel whatever the hooks say, so there every "form" is that one kernel compared
+    with itself.  Each form (with nb_debug_set_up1_small(0) where needed) and h3s are held to float64 by
+    tests/test_hip_conv_forms_f64.py."""
     from brushstroke_engine_amd import _lib, ops
     if fmt and ci % 16:
         pytest.skip("f8 operands need whole 16-channel chunks (an odd number of channel groups is an H2 case: the last chunk's missing group "

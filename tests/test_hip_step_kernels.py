@@ -398,8 +398,10 @@ def _torgb_run(lib, x, st, stride, w, b, cb, clamp, uc, sf, mode, n, c, hw, dev,
     return o, u8
 
 
-def _torgb_ref(x, st, w, b, cb, clamp, uc, sf, mode, c):
+def _torgb_ref(x, st, w, b, cb, clamp, uc, sf, mode, c, x_err=0.0):
     """float64 ToRGBColorTriadLayer arithmetic (OracleGenerator.torgb after its affine) + triad_composite, with bounds.
+    x_err (default 0: x is the kernel's own input) = bound of the error of every x the kernel sees (a fused producer's output
+    against the float64 x given here); it enters the logits as x_err * sum_c |w_c s_c| and is carried on from there.
     logits: c terms x * (w * s) (2 roundings each; fmaf accumulation in 8 partial sums, then 7 adds) + bias ->
     E = (c + 10) U (sum|x w s| + |b|); the clamp is 1-Lipschitz.  softmax: du_k = u_k (dl_k - sum_j u_j dl_j), so
     |du_k| <= 2 E_max u_k (1 - u_k), plus expf / 1/x / products: 16 U.  img_ch = sum_k u_k col_k: sum |du_k| |col_k| + 12 U sum
@@ -414,7 +416,7 @@ def _torgb_ref(x, st, w, b, cb, clamp, uc, sf, mode, c):
     pre = torch.einsum("noc,nch->noh", wm, xd)
     A = torch.einsum("noc,nch->noh", wm.abs(), xd.abs()) + b.double().abs()[None, :, None]
     logits = orc.bias_act(pre, b.double(), clamp=clamp if clamp >= 0 else None)
-    E = (c + 10) * U * A
+    E = (c + 10) * U * A + x_err * wm.abs().sum(dim=2)[:, :, None]
     Emax = E.max(dim=1, keepdim=True).values
     uvs = torch.softmax(logits, dim=1)
     tol_u = 2 * Emax * uvs * (1 - uvs) + 16 * U
