@@ -550,14 +550,17 @@ int nb_stitching_grid(int h, int w, int patch_width, int overlap_margin, int* nr
 
 /* Stem: 1 -> 64 channels, 7x7, reflect padding 3.  x fp32 [n,1,h,w] (h % 16 == 0, w % 32 == 0), w50 [64][50] =
  * folded weights [c_out][ky*7+kx] padded with one zero, y_h2 = H2 [n,8,2,h,w,8].  preproc (autoenc/base.py:30-52):
- * 0 none, 1 '-11inverse' (1-x)*2-1, 2 'inverse' 1-x.  Exact fp32 products (v_mfma_f32_32x32x2_f32). */
+ * 0 none, 1 '-11inverse' (1-x)*2-1, 2 'inverse' 1-x.  Split-f16 products (three v_mfma_f32_32x32x16_f16 per K step over the
+ * hi / lo f16 halves of image and weights: fp32-grade, within 2e-6 of the largest pre-bias output of float64). */
 int nb_enc_stem7x7_f32_h2(const float* x, const float* w50, const float* bias, void* y_h2, int n, int h, int w,
                           int preproc, float slope, void* stream);
 
 /* 3x3 conv, stride 1 or 2, reflect padding 1, split-f16 products.  x_h2: H2 [n, c_in, h_in, w_in]; w_h3: hi/lo f16
  * [ceil(c_in/16)][3][3][2][2][ceil128(c_out)][8]; exactly one of y_f32 (fp32 NCHW [n,c_out,h_in/stride,w_in/stride])
- * and y_h2 (H2, c_out % 8 == 0) is non-NULL.  Output must be a multiple of 16 wide (rows % 16 == 0) or a multiple of 32 wide
- * (rows % 8 == 0). */
+ * and y_h2 (H2, c_out % 8 == 0) is non-NULL.  Output sizes: a multiple of 32 wide with rows % 8 == 0 (8 x 32 tiles), any other
+ * multiple of 16 wide with rows % 16 == 0 (16 x 16 tiles: 16, 48, 80 ...), or -- with c_in % 16 == 0 -- a power of two >= 4 wide with
+ * any number of rows (the 32-position split-K tiles: rows that do not fill the last tile are masked).  Where both forms fit and c_in >= 32,
+ * under-filled launches (<= 48 large-tile workgroups) and layers with c_out <= 32 take the split-K tiles. */
 int nb_enc_conv3x3_h3(const void* x_h2, int c_in, const void* w_h3, const float* bias, float* y_f32, void* y_h2, int n,
                       int h_in, int w_in, int c_out, int stride, float slope, void* stream);
 
@@ -565,7 +568,9 @@ int nb_enc_conv3x3_h3(const void* x_h2, int c_in, const void* w_h3, const float*
  * geometry features as extra input channels, networks_modified.py:218-219 `torch.cat`): the result times
  * oscale[n * oscale_stride + co] (the consumer's styles of those channels; NULL = 1) goes into channel groups
  * cg0 .. cg0 + c_out/8 - 1 of y_h2 [n][c8_total][2][h][w][8]; out_fmt 0 = H2 (hi/lo f16), 1 = "f8" (hi f16 + fp8
- * correction operands: c_out % 16 == 0, cg0 even).  Removes the fp32 round trip + nb_pack_h2*_part_f32 pass. */
+ * correction operands: c_out % 16 == 0, cg0 even).  Removes the fp32 round trip + nb_pack_h2*_part_f32 pass.  Needs an output size
+ * the 8 x 32 or 16 x 16 tiles take (the split-K tiles have no hand-off), c8_total >= cg0 + c_out/8 and oscale_stride >= c_out;
+ * anything else is NB_EINVAL with nothing written.  Words of y_h2 outside those channel groups are not touched. */
 int nb_enc_conv3x3_h3_handoff(const void* x_h2, int c_in, const void* w_h3, const float* bias, void* y_h2,
                               const float* oscale, int oscale_stride, int c8_total, int cg0, int out_fmt,
                               int n, int h_in, int w_in, int c_out, int stride, float slope, void* stream);
@@ -599,7 +604,8 @@ int nb_enc_stem_conv3x3_f8(const float* x, const float* w50, const float* bias0,
 /* Stride-2 3x3 correlation WITHOUT padding on the same kernel -- the strided half of conv2d_resample's down-sampling branch
  * (conv2d_resample.py:96-113) and the input gradient of its up-sampling branch (:124-147), which cuDNN runs for the reference:
  * x H2 [n][c8][2][2ho+1][2wo+1][8], weights as above, y fp32 [n][c_out][ho][wo] = oscale[n][co] * (bias[co] + sum_{ci,a,b}
- * x[n,ci,2i+a,2j+b] w[co,ci,a,b]); oscale may be NULL.  Output sizes: wo % 32 == 0 and ho % 8 == 0, or wo == 16 and ho % 16 == 0. */
+ * x[n,ci,2i+a,2j+b] w[co,ci,a,b]); oscale may be NULL.  Output sizes: wo % 32 == 0 and ho % 8 == 0, or wo % 16 == 0 and ho % 16 == 0
+ * (the large tiles only: the split-K tiles of nb_enc_conv3x3_h3 have no unpadded form). */
 int nb_conv3x3_s2_valid_h3(const void* x_h2, int c_in, const void* w_h3, const float* bias, const float* oscale, int oscale_stride,
                            float* y_f32, int n, int h_in, int w_in, int c_out, void* stream);
 int nb_enc_upsample2x_h2_ex(const float* x, void* y_h2, int out_fmt, int n, int c, int h, int w, void* stream);
