@@ -16,9 +16,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libneube_hip.so")
-SOURCES = ["nb_ops.hip", "nb_modconv.hip", "nb_modconv_h3.hip", "nb_modconv_up2v.hip", "nb_modconv_small.hip", "nb_grad.hip", "nb_canvas.hip", "nb_encoder.hip", "nb_calib.hip",
-           "nb_generator.hip", "nb_geomprep.hip", "nb_noise_seeded.hip"]
-HEADERS = ["nb_common.h", "nb_h3_common.h", "nb_torgb.h", os.path.join("..", "..", "include", "neube_hip.h")]
+# (the four files that take longest to compile come first: the pool of four starts with them)
+SOURCES = ["nb_modconv_up1_h3.hip", "nb_modconv_up2_h3.hip", "nb_modconv_up2v.hip", "nb_encoder.hip", "nb_ops.hip", "nb_modconv.hip", "nb_pack_h2.hip",
+           "nb_modconv_small.hip", "nb_grad.hip", "nb_canvas.hip", "nb_calib.hip", "nb_generator.hip", "nb_geomprep.hip", "nb_noise_seeded.hip"]
+HEADERS = ["nb_common.h", "nb_h3_common.h", "nb_h3_launch.h", "nb_torgb.h", os.path.join("..", "..", "include", "neube_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall",

@@ -12,7 +12,7 @@
 //                        seven input rows in LDS and every B fragment is one aligned ds_read_b128.  Split-f16 products (3
 //                        v_mfma_f32_32x32x16_f16 per K step, fp32-grade) instead of the exact-fp32 MFMA of rounds 1-2, which runs
 //                        at a sixteenth of the rate and was half of the launch: 96 instead of 200 four-times-longer MFMAs per wave.
-//   enc_conv3x3_h3_kernel  3x3, stride 1 or 2, split-f16 products (see nb_modconv_h3.hip for the arithmetic and
+//   enc_conv3x3_h3_kernel  3x3, stride 1 or 2, split-f16 products (see nb_modconv_up1_h3.hip for the arithmetic and
 //                        the H2 activation format).  K loop = (16-channel chunk, tap row); per step the activation
 //                        rows that tap row needs are gathered by LDS-DMA with per-lane source addresses -- for
 //                        stride 2 the even and odd input columns land in two planes, so every MFMA B fragment is a
@@ -40,7 +40,7 @@ __device__ __forceinline__ float nb_lrelu(float v, float slope) { return v < 0.f
 // ------------------------------------------------------------------------------------------------
 // stem: 1 -> 64 channels, 7x7, reflect padding 3; fp32 [n,1,h,w] -> H2 [n,8,2,h,w,8]
 // ------------------------------------------------------------------------------------------------
-// four values -> four e4m3 bytes, saturated to the format's range (the same conversion as nb_pk4_fp8 of nb_modconv_h3.hip)
+// four values -> four e4m3 bytes, saturated to the format's range (the same conversion as nb_pk4_fp8 of nb_h3_common.h)
 __device__ __forceinline__ unsigned nb_enc_pk4_fp8(float a, float b, float c, float d) {
     auto cl = [](float v) { return fminf(fmaxf(v, -448.f), 448.f); };
     int w = 0;
@@ -49,7 +49,7 @@ __device__ __forceinline__ unsigned nb_enc_pk4_fp8(float a, float b, float c, fl
     return (unsigned)w;
 }
 
-// ... in a wave whose MODE.FP16_OVFL is set the conversion itself saturates (nb_pk4_fp8_sat of nb_modconv_h3.hip): the stem's
+// ... in a wave whose MODE.FP16_OVFL is set the conversion itself saturates (nb_pk4_fp8_sat of nb_h3_common.h): the stem's
 // epilogue is bound by its vector instructions, 4 of ~15 per value were these clamps
 __device__ __forceinline__ unsigned nb_enc_pk4_fp8_sat(float a, float b, float c, float d) {
     int w = 0;
@@ -213,7 +213,7 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 
-// F8: the input activations and the weights carry their corrections as fp8 (the "f8" operand format of nb_modconv_h3.hip:
+// F8: the input activations and the weights carry their corrections as fp8 (the "f8" operand format of nb_h3_common.h:
 // lo slot of an even channel group = fp8(xl 2^9) of the 16-channel chunk, of the odd group = fp8(x/4); weights fp8(w) /
 // fp8(wl 2^11)); per tap one f16 MFMA for the main product and, per PAIR of taps, one block-scaled K=64 fp8 MFMA for both
 // correction products (the third tap of a step pairs with the third tap of the next step): 768 instead of 1152 matrix
@@ -1030,7 +1030,7 @@ __global__ __launch_bounds__(512) void enc_conv3x3_h3_kernel(const EncConvParams
                     }
                     *reinterpret_cast<h4*>(sh + pix * CP + col) = vh;
                     if (p.out_f8) {
-                        // lo image as bytes: per 16-channel chunk 16 x fp8(xl 2^9) then 16 x fp8(v/4) (see nb_modconv_h3.hip)
+                        // lo image as bytes: per 16-channel chunk 16 x fp8(xl 2^9) then 16 x fp8(v/4) (see nb_h3_common.h)
                         unsigned char* sb = reinterpret_cast<unsigned char*>(sl) + (size_t)pix * (CP * 2) + (col >> 4) * 32 + (col & 15);
                         *reinterpret_cast<unsigned*>(sb) = nb_enc_pk4_fp8(xl[0] * 512.f, xl[1] * 512.f, xl[2] * 512.f, xl[3] * 512.f);
                         *reinterpret_cast<unsigned*>(sb + 16) = nb_enc_pk4_fp8(vv[0] * 0.25f, vv[1] * 0.25f, vv[2] * 0.25f, vv[3] * 0.25f);

@@ -1,5 +1,6 @@
 // Shared device helpers of the split-f16 ("h3" / "f8") convolution kernels: vector types, LDS-DMA, counted waits, fp8 packing,
-// lane-half exchange, the up=2 kernels' parameter block.  Included by nb_modconv_h3.hip and nb_modconv_up2v.hip.
+// lane-half exchange, the up=2 kernels' parameter block.  Included by nb_modconv_up1_h3.hip, nb_modconv_up2_h3.hip,
+// nb_modconv_up2v.hip, nb_pack_h2.hip and nb_encoder.hip.
 #pragma once
 #include "nb_common.h"
 #include <cstdlib>
@@ -13,7 +14,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define NB_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define NB_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
 
 #define NB_TSTAMP(k)                                                                                         \
     do {                                                                                                     \

@@ -370,7 +370,7 @@ __host__ __device__ constexpr int nb_up2_stage_floats(int nbp, int kc) { return 
 #define NB_UP2_STAGES 3
 #define NB_STY_MAX 1024
 
-// H2OUT: write the output in the split-f16 "H2" activation format of nb_modconv_h3.hip ([N][C/8][hi,lo][H][W][8] f16,
+// H2OUT: write the output in the split-f16 "H2" activation format of nb_modconv_up1_h3.hip ([N][C/8][hi,lo][H][W][8] f16,
 // multiplied by out_scale = the consuming layer's styles) instead of fp32 NCHW.
 template <int NBP, int KC, bool H2OUT>
 __global__ __launch_bounds__(256) void modconv3x3_up2_kernel(const ModconvParams p) {

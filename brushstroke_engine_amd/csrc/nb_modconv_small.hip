@@ -1,11 +1,11 @@
 // Modulated 3x3 convolution (up = 1) for SMALL images on the f16 matrix cores of gfx950: the <= 64x64 layers of the
-// generator (b4 ... b64 conv1), which the large-tile split-f16 kernels of nb_modconv_h3.hip cannot fill the chip with and
+// generator (b4 ... b64 conv1), which the large-tile split-f16 kernels of nb_modconv_up1_h3.hip cannot fill the chip with and
 // which the fp32-MFMA kernels of nb_modconv.hip run at the fp32 matrix rate (1/16 of f16) -- at batch 1 their launches
 // are half of the interactive step, at batch 32 a sixth.
 //
 // Same math as everywhere (training/networks.py:30-88, :362-391):
 //     y = clamp(lrelu(conv(x * s[n,c]) * d[n,o] + noise + bias[o]) * gain)
-// in the "scale activations, shared weights" form with the split-f16 products of nb_modconv_h3.hip
+// in the "scale activations, shared weights" form with the split-f16 products of nb_modconv_up1_h3.hip
 //     x w  ~=  xh wh + xh wl + xl wh      (xh = f16(x s), xl = f16(x s - xh); same for w; error ~2^-22 relative).
 //
 // Workgroup = 4 waves = one tile of 32 c_out x 32 output positions, the four waves SPLIT K: wave w owns the 16-channel

@@ -21,21 +21,8 @@
 // of 32.  K loop: 16-channel chunks x 3 tap rows; the weights of one (chunk, tap row) form a 4-deep LDS ring,
 // the activation halo tile of a chunk is double buffered; counted vmcnt + raw s_barrier keep 2 sub-chunks of
 // LDS-DMA in flight behind the MFMAs.
-#include "nb_h3_common.h"
+#include "nb_h3_launch.h"
 #include "nb_torgb.h"
-
-// `noise` / `noise_stride_n` of the entry points -> kernel fields: a [n or 1][H][W] tensor, or (NB_NOISE_IN_KERNEL) a host
-// NbNoiseSrc describing how the kernel computes the noise itself
-static int nb_noise_src_setup(const float* noise, int64_t stride_n, int ho, int wo, const float** k_noise, long long* k_stride, NbNoiseSrcDev* k_src) {
-    *k_src = NbNoiseSrcDev{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (stride_n != NB_NOISE_IN_KERNEL) { *k_noise = noise; *k_stride = stride_n; return NB_OK; }
-    const NbNoiseSrc* s = reinterpret_cast<const NbNoiseSrc*>(noise);
-    if (!s || !s->noise_const_t || !s->noise_lin || !s->noise_strength || ((s->norm_pos != nullptr) == (s->positions != nullptr))) return NB_EINVAL;
-    if (s->res != ho || s->res != wo || (s->positions && s->img_resolution < 2)) return NB_EINVAL;
-    *k_src = NbNoiseSrcDev{s->noise_const_t, s->noise_lin, s->noise_strength, s->norm_pos, (const long long*)s->positions, s->res, s->img_resolution};
-    *k_noise = nullptr; *k_stride = 0;
-    return NB_OK;
-}
 
 struct H3Params {
     const _Float16* x;      // H2 [n][c8][2][H][W][8], already multiplied by this layer's styles
@@ -63,11 +50,10 @@ struct H3Params {
     TorgbParams tg;
 };
 
-static unsigned long long* g_tstamps = nullptr;
-static int g_tstamps_cap = 0;
+unsigned long long* g_tstamps = nullptr;
+int g_tstamps_cap = 0;
 // Debug hook (not part of the product ABI): phase timestamps [workgroup][8] of the next h3 launches, s_memrealtime ticks
 extern "C" void nb_debug_set_timestamps(void* buf, int capacity_workgroups) { g_tstamps = (unsigned long long*)buf; g_tstamps_cap = capacity_workgroups; }
-
 
 // Activation of the split-f16 kernels: lrelu(g (a d + noise + bias)) clamped, with the gain g > 0 folded into the three
 // addends (lrelu(g t) = g lrelu(t)).  Every output path of a kernel -- fp32, H2, f8 -- evaluates exactly this expression
@@ -77,8 +63,6 @@ __device__ __forceinline__ float nb_h3_act(float a, float dg, float nbg, float a
     // lrelu = max(t, alpha t) for 0 <= alpha <= 1 (the launchers check); clampv = +inf for "no clamp"
     return __builtin_amdgcn_fmed3f(__builtin_amdgcn_fmed3f(t, t * alpha, __builtin_inff()), -clampv, clampv);
 }
-
-
 
 // (the hand-off epilogue of the up=1 kernels, nb_up1_handoff_epilogue, lives in nb_h3_common.h: the geometry encoder's conv kernel uses it too)
 
@@ -130,7 +114,7 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
     // [sample][tile][c_out slice] (p.items of them, p.items_x per sample), and the NEXT tile's prologue -- its halo tile and first three
     // weight sub-chunks, ~4 us of LDS-DMA round trip -- is issued BEFORE this tile's epilogue, which works straight from the
     // accumulators (hand-off / fused ToRGB outputs) and leaves the staging LDS alone.
-    // XCD-aware order (as in the up=2 kernel below): hardware workgroup ids go round-robin to the 8 XCDs, each with its own L2;
+    // XCD-aware order (as in the up=2 kernels): hardware workgroup ids go round-robin to the 8 XCDs, each with its own L2;
     // renumbered, an XCD works on a contiguous run of a sample's row-major tile list -- whole tile rows -- so that the halo columns
     // and rows neighbouring tiles share are L2 hits instead of second HBM reads (gridDim.x is a multiple of 8 whenever the per-sample
     // list is, so a workgroup's items keep to its XCD)
@@ -346,6 +330,7 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
         //            behind the last fp6 MFMA the lo slots of step t+1
         // Measured (profiles/r05_f6_ab.txt): not faster than the f8 loop -- neither loop is bound by the matrix pipe.
 #define NB_SB __builtin_amdgcn_sched_barrier(0)
+#define NB_Q(v, q, src) { const i32x4 t_ = __builtin_bit_cast(i32x4, (src)); v[4 * (q)] = t_[0]; v[4 * (q) + 1] = t_[1]; v[4 * (q) + 2] = t_[2]; v[4 * (q) + 3] = t_[3]; }
         __shared__ __attribute__((aligned(16))) h8 s_zero6[1];
         if (tid == 0) s_zero6[0] = h8{};
         __builtin_amdgcn_s_barrier();
@@ -476,7 +461,6 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
         // the last step's tap 2 and its corrections
         nb_static_for<0, NM>([&](auto k_) { constexpr int k = decltype(k_)::value; mf_f16(ah2, bh2)(std::integral_constant<int, k / NBW>{}, std::integral_constant<int, k % NBW>{}); NB_SB; });
         nb_static_for<0, NM>([&](auto k_) { constexpr int k = decltype(k_)::value; mf_fp6(al2, sa2, bl2, sb2)(std::integral_constant<int, k / NBW>{}, std::integral_constant<int, k % NBW>{}); NB_SB; });
-#undef NB_SB
     } else if constexpr (F8 && V2) {
         // ---- f8 operands, software-pipelined over the barrier ------------------------------------------------------
         // Step t = (chunk c, tap row ky) multiplies, per accumulator tile and in this order: tap 2 of step t-1 (f16), on even t
@@ -488,8 +472,6 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
         //            behind the last fp8 MFMA the lo halves of step t+1 (their tuples were its operands)
         // so no step opens with a burst of sixteen reads behind a barrier that both waves of a SIMD reach together.
         // All compile-time: the loop body is two chunks = six steps (tap row and the parity that selects the tuple quad).
-#define NB_SB __builtin_amdgcn_sched_barrier(0)
-#define NB_Q(v, q, src) { const i32x4 t_ = __builtin_bit_cast(i32x4, (src)); v[4 * (q)] = t_[0]; v[4 * (q) + 1] = t_[1]; v[4 * (q) + 2] = t_[2]; v[4 * (q) + 3] = t_[3]; }
         const int sa = lh ? 116 : 127, sb = lh ? 129 : 118;
         h8 ah0[MB], ah1[MB], ah2[MB], bh0[NBW], bh1[NBW], bh2[NBW];
         i32x8 al01[MB], bl01[NBW], al2[MB], bl2[NBW];
@@ -714,8 +696,6 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
         }
         nb_static_for<0, NM>([&](auto k_) { constexpr int k = decltype(k_)::value; mf_fp8(al2, bl2)(std::integral_constant<int, k / NBW>{}, std::integral_constant<int, k % NBW>{}); NB_SB; });
         }
-#undef NB_Q
-#undef NB_SB
     } else if constexpr (V2) {
         // ---- H2 operands (the `h3` arithmetic: hi x hi, hi x lo, lo x hi per tap), software-pipelined over the barrier like the
         //      f8 loop above.  Per accumulator tile the nine products of a step arrive in the order of the loop below (tap by tap:
@@ -724,7 +704,6 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
         //            one accumulator)            fillers: the step's LDS-DMA pieces, its tap-2 fragments
         //   wait (counted) + barrier: every wave has read ALL of stage t; stage t+1 has landed
         //   part B:  tap 2 (three groups)         fillers: the sixteen fragments of taps 0 and 1 of step t+1
-#define NB_SB __builtin_amdgcn_sched_barrier(0)
         h8 ah[3][MB], al[3][MB], bh[3][NBW], bl[3][NBW];           // [tap][block]
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -805,7 +784,6 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
         nb_static_for<0, 2 * NF>([&](auto j_) { rd(j_, I1{}, wring, xbuf, 0); });
         for (int c = 0; c < NC; ++c) { step(I0{}, 3 * c, c); step(I1{}, 3 * c + 1, c); step(I2{}, 3 * c + 2, c); }
         NB_SB;
-#undef NB_SB
     } else if constexpr (F8) {
         // ---- f8 operands: explicitly ordered, software-pipelined step -------------------------------------------
         // The compiler, left alone, sinks every fragment read to just before its first use and waits with lgkmcnt(0)
@@ -818,8 +796,6 @@ __global__ __launch_bounds__(512) void modconv3x3_up1_h3_kernel(const H3Params p
         // The third tap of a row has no partner within its step, so its corrections ride with the third tap of the NEXT step
         // in one K = 64 fp8 instruction (quad 0 = even step, quad 1 = odd step): 7 fp8 instructions per two steps instead of
         // 8, 768 instead of 896 matrix cycles per step and tile row.
-#define NB_SB __builtin_amdgcn_sched_barrier(0)
-#define NB_Q(v, q, src) { const i32x4 t_ = __builtin_bit_cast(i32x4, (src)); v[4 * (q)] = t_[0]; v[4 * (q) + 1] = t_[1]; v[4 * (q) + 2] = t_[2]; v[4 * (q) + 3] = t_[3]; }
         const int sa = lh ? 116 : 127, sb = lh ? 129 : 118;
         h8 ah0[MB], ah1[MB], ah2[MB], bh0[NBW], bh1[NBW], bh2[NBW];
         i32x8 al01[MB], bl01[NBW], al2[MB], bl2[NBW];          // fp8 operand tuples: (tap 0 | tap 1), (tap 2 of an even step | of the odd step after it)
@@ -1397,20 +1373,12 @@ static int launch_h3(H3Params p, int n, hipStream_t st) {
     }
     // persistent workgroups: one per CU (fewer items than CUs: one each), the next tile's prologue issued ahead of the current tile's
     // epilogue; g_up1_persist == 0 (test hook): one workgroup per item, as until round 5
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        ncu = v;
-    }
-    const long want = (long)ncu * g_persist_wgs_per_cu;                 // (workgroups per CU: see NB_PERSIST_WGS_PER_CU)
+    const long want = (long)nb_num_cus() * g_persist_wgs_per_cu;                 // (workgroups per CU: see NB_PERSIST_WGS_PER_CU)
     dim3 grid(PERSIST && p.items > want ? (unsigned)want : (unsigned)p.items);
     hipLaunchKernelGGL((modconv3x3_up1_h3_kernel<MW, F8, NBW, V2, F6, PP, HO, PERSIST>), grid, dim3(512), lds, st, p);
     NB_CHECK_LAUNCH("modconv3x3_up1_h3");
     return NB_OK;
 }
-
-extern "C" const float* nb_zero_page_ptr(void);
 
 static int g_force_up1_v2 = -1;
 // developer / test hook: -1 = automatic (on), 0 / 1 = the round-3 / the software-pipelined K loop of the f8 up=1 kernel
@@ -1428,47 +1396,31 @@ static int g_force_up1_small = -1;
 // developer / test hook: -1 = automatic (images <= 32 x 32), 0 / 1 = never / always the 4-wave two-workgroups-per-CU form of the H2 up=1 kernel
 extern "C" void nb_debug_set_up1_small(int mode) { g_force_up1_small = mode; }
 
-static int nb_up1_h3_impl(const void* x_h2, int c_in, const void* w_h3, const float* dcoefs, const float* noise,
-                          int64_t noise_stride_n, const float* bias, float* y, void* y_h2, const float* next_styles,
-                          int next_stride, int c_next, int n, int h, int w, int c_out, float alpha, float gain, float clamp,
-                          void* stream, const TorgbParams* tg = nullptr, int in_fmt = 0, int out_fmt = 0) {
+// workgroups of a full-height launch of the 8-wave kernel: 128 c_out x 8 rows of 32 pixels above 64 channels, else 64 x 16 rows
+static long long nb_up1_h3_wgs(int n, int h, int w, int c_out) {
+    const int mw = c_out > 64 ? 2 : 1;
+    return (long long)n * (w / 32) * (h / (16 / mw)) * ((c_out + 64 * mw - 1) / (64 * mw));
+}
+
+static int nb_up1_h3_impl(const H3ConvArgs& a, void* stream, const TorgbParams* tg = nullptr, int in_fmt = 0) {
+    const int n = a.n, h = a.h, w = a.w, c_out = a.c_out, out_fmt = a.out_fmt;
     const bool f8 = in_fmt != 0, f6 = in_fmt == 2;          // (the f6 form is a variant of the f8 loop: same containers, same staging)
     const bool hi_only = in_fmt == 3;                       // f8 containers, correction products skipped (conv_mode "f16": where the ping-pong loop runs)
-    NB_REQUIRE(out_fmt == 0 || ((out_fmt == 1 || out_fmt == 2) && y_h2 && c_out % 16 == 0 && c_next % 16 == 0),
+    NB_REQUIRE(out_fmt == 0 || ((out_fmt == 1 || out_fmt == 2) && a.y_h2 && c_out % 16 == 0 && a.c_next % 16 == 0),
                "modconv3x3_up1_h3: f8 / f6 output needs an H2 destination and c_out, c_next %% 16 == 0");
-    NB_REQUIRE(x_h2 && w_h3 && dcoefs && bias && (tg ? !y_h2 : ((y != nullptr) != (y_h2 != nullptr))), "modconv3x3_up1_h3: null pointer");
-    NB_REQUIRE(!f8 || c_in % 16 == 0, "modconv3x3_up1_h3: the f8 operand format needs c_in %% 16 == 0 (got %d)", c_in);
-    NB_REQUIRE(!y_h2 || (next_styles && c_out % 8 == 0 && c_next >= c_out && next_stride >= c_out && (uintptr_t)y_h2 % 16 == 0),
-               "modconv3x3_up1_h3: H2 output needs the consumer's styles, c_out %% 8 == 0 and c_next >= c_out");
-    NB_REQUIRE(n > 0 && n <= 65535 && c_in > 0 && c_out > 0, "modconv3x3_up1_h3: bad sizes");
-    NB_REQUIRE(alpha >= 0.f && alpha <= 1.f && gain > 0.f, "modconv3x3_up1_h3: leaky-ReLU slope must lie in [0, 1] and the gain be positive (got %g, %g)", alpha, gain);
-    NB_REQUIRE(w % 32 == 0 && h % 16 == 0, "modconv3x3_up1_h3: needs w %% 32 == 0 and h %% 16 == 0 (got %dx%d)", h, w);
-    NB_REQUIRE(((uintptr_t)x_h2 | (uintptr_t)w_h3 | (uintptr_t)y) % 16 == 0, "modconv3x3_up1_h3: pointers must be 16-byte aligned");
+    NB_REQUIRE(a.x_h2 && a.w_h3 && a.dcoefs && a.bias && (tg ? !a.y_h2 : ((a.y != nullptr) != (a.y_h2 != nullptr))), "modconv3x3_up1_h3: null pointer");
+    NB_REQUIRE(!f8 || a.c_in % 16 == 0, "modconv3x3_up1_h3: the f8 operand format needs c_in %% 16 == 0 (got %d)", a.c_in);
     H3Params p;
-    p.x = (const _Float16*)x_h2; p.wts = (const _Float16*)w_h3; p.dcoefs = dcoefs; p.noise = noise; p.bias = bias; p.y = y;
-    p.zeros = nb_zero_page_ptr();
-    NB_REQUIRE(p.zeros, "modconv3x3_up1_h3: could not allocate the zero page");
-    p.noise_stride_n = noise_stride_n;
-    NB_REQUIRE(nb_noise_src_setup(noise, noise_stride_n, h, w, &p.noise, &p.noise_stride_n, &p.nsrc) == NB_OK, "modconv3x3_up1_h3: bad NbNoiseSrc (needs the "
-               "transposed constant, the grid row, the strength, exactly one of norm_pos / positions, and res = the %dx%d output)", h, w);
-    p.c8 = (c_in + 7) / 8; p.nchunks = (c_in + 15) / 16; p.c_out = c_out; p.co_ld = (c_out + 63) / 64 * 64; p.h = h; p.w = w;
-    p.dbg = g_nb_debug_flags; p.stagger_ticks = g_nb_stagger_ticks;            // (developer hooks: nb_debug_set_flags / nb_debug_set_stagger)
-    p.alpha = alpha; p.gain = gain; p.clamp = clamp;
-    p.yh2 = (_Float16*)y_h2; p.next_styles = next_styles; p.next_stride = next_stride; p.c8_next = (c_next + 7) / 8;
-    p.out_f8 = out_fmt;
+    if (const int rc = nb_h3_launch_setup(p, "modconv3x3_up1_h3", a, 1, w % 32 == 0 && h % 16 == 0, "w % 32 == 0 and h % 16 == 0", true)) return rc;
     p.tg = TorgbParams{};
     if (tg) p.tg = *tg;
-    p.tstamps = nullptr;
-    if (g_tstamps) {
-        const long long wgs = (long long)(w / 32) * (h / (c_out > 64 ? 8 : 16)) * ((c_out + (c_out > 64 ? 127 : 63)) / (c_out > 64 ? 128 : 64)) * n;
-        if (wgs <= g_tstamps_cap) p.tstamps = g_tstamps;
-    }
+    const long long wgs_full = nb_up1_h3_wgs(n, h, w, c_out);
+    p.tstamps = g_tstamps && wgs_full <= g_tstamps_cap ? g_tstamps : nullptr;
     // the 4-wave / 2-workgroups-per-CU form wins on small images (fewer, larger workgroups leave CUs idle there); on the
     // large layers both forms run at the same rate -- the chip is power-limited in these loops, not latency-limited
     { const bool small = g_force_up1_small >= 0 ? g_force_up1_small != 0 : (h * w <= 32 * 32);
       if (small && !f8 && (!tg || c_out <= 64)) return launch_h3s(p, n, (hipStream_t)stream); }
     // half-height tiles when the full ones leave the chip mostly idle (batch 1); g_force_nbw: test hook
-    const long wgs_full = (long)n * (w / 32) * (h / (c_out > 64 ? 8 : 16)) * ((c_out + (c_out > 64 ? 127 : 63)) / (c_out > 64 ? 128 : 64));
     const bool half = g_force_nbw ? g_force_nbw == 1 : wgs_full < 160;
     hipStream_t st = (hipStream_t)stream;
     // the software-pipelined K loop (V2; both operand formats) unless switched off (test hook nb_debug_set_up1_v2)
@@ -1479,29 +1431,39 @@ static int nb_up1_h3_impl(const void* x_h2, int c_in, const void* w_h3, const fl
     // Persistent workgroups: automatic = NO (see the kernel's PERSIST); nb_debug_set_up1_persistent(1) = always -- the tests and
     // tools/stress_persistent.py keep that instantiation honest.  Half-height launches (< 160 workgroups) have nothing to walk: loop-less always.
     const bool persist = g_up1_persist > 0;
-#define NB_H3_GO(MW, F8, NBW, V2, F6, PP, HO) \
-    (persist ? launch_h3<MW, F8, NBW, V2, F6, PP, HO, true>(p, n, st) : launch_h3<MW, F8, NBW, V2, F6, PP, HO, false>(p, n, st))
-#define NB_H3_GO1(MW, F8, NBW, V2, F6) launch_h3<MW, F8, NBW, V2, F6, false, false, false>(p, n, st)
-    if (f6) {                                               // (the software-pipelined loop only)
-        if (half) return c_out > 64 ? NB_H3_GO1(2, true, 1, true, true) : NB_H3_GO1(1, true, 1, true, true);
-        return c_out > 64 ? NB_H3_GO(2, true, 2, true, true, false, false) : NB_H3_GO(1, true, 2, true, true, false, false);
-    }
-    if (half) {
-        if (f8 && v2) return c_out > 64 ? NB_H3_GO1(2, true, 1, true, false) : NB_H3_GO1(1, true, 1, true, false);
-        if (f8) return c_out > 64 ? NB_H3_GO1(2, true, 1, false, false) : NB_H3_GO1(1, true, 1, false, false);
-        if (v2) return c_out > 64 ? NB_H3_GO1(2, false, 1, true, false) : NB_H3_GO1(1, false, 1, true, false);
-        return c_out > 64 ? NB_H3_GO1(2, false, 1, false, false) : NB_H3_GO1(1, false, 1, false, false);
-    }
-    // the ping-pong form of that loop (full-height tiles): nb_debug_set_up1_pp
+    // the ping-pong form of the f8 loop (full-height tiles): nb_debug_set_up1_pp
     const bool pp = (g_force_up1_pp >= 0 ? g_force_up1_pp : NB_UP1_PP_DEFAULT) != 0;
-    if (f8 && v2 && pp && hi_only) return c_out > 64 ? NB_H3_GO(2, true, 2, true, false, true, true) : NB_H3_GO(1, true, 2, true, false, true, true);
-    if (f8 && v2 && pp) return c_out > 64 ? NB_H3_GO(2, true, 2, true, false, true, false) : NB_H3_GO(1, true, 2, true, false, true, false);
-    if (f8 && v2) return c_out > 64 ? NB_H3_GO(2, true, 2, true, false, false, false) : NB_H3_GO(1, true, 2, true, false, false, false);
-    if (f8) return c_out > 64 ? NB_H3_GO(2, true, 2, false, false, false, false) : NB_H3_GO(1, true, 2, false, false, false, false);
-    if (v2) return c_out > 64 ? NB_H3_GO(2, false, 2, true, false, false, false) : NB_H3_GO(1, false, 2, true, false, false, false);
-    return c_out > 64 ? NB_H3_GO(2, false, 2, false, false, false, false) : NB_H3_GO(1, false, 2, false, false, false, false);
-#undef NB_H3_GO
-#undef NB_H3_GO1
+    using T = std::true_type; using F = std::false_type;
+    using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+    auto go1 = [&](auto mw_, auto nbw_, auto f8_, auto v2_, auto f6_, auto pp_, auto ho_) {
+        constexpr int MW_ = decltype(mw_)::value, NBW_ = decltype(nbw_)::value;
+        constexpr bool F8_ = decltype(f8_)::value, V2_ = decltype(v2_)::value, F6_ = decltype(f6_)::value, PP_ = decltype(pp_)::value, HO_ = decltype(ho_)::value;
+        if constexpr (NBW_ == 2) {
+            if (persist) return launch_h3<MW_, F8_, NBW_, V2_, F6_, PP_, HO_, true>(p, n, st);
+        }
+        return launch_h3<MW_, F8_, NBW_, V2_, F6_, PP_, HO_, false>(p, n, st);
+    };
+    auto go = [&](auto nbw_, auto f8_, auto v2_, auto f6_, auto pp_, auto ho_) {
+        return c_out > 64 ? go1(I2{}, nbw_, f8_, v2_, f6_, pp_, ho_) : go1(I1{}, nbw_, f8_, v2_, f6_, pp_, ho_);
+    };
+    auto go_rows = [&](auto f8_, auto v2_, auto f6_) { return half ? go(I1{}, f8_, v2_, f6_, F{}, F{}) : go(I2{}, f8_, v2_, f6_, F{}, F{}); };
+    if (f6) return go_rows(T{}, T{}, T{});                  // (the software-pipelined loop only)
+    if (!half && f8 && v2 && pp) return hi_only ? go(I2{}, T{}, T{}, F{}, T{}, T{}) : go(I2{}, T{}, T{}, F{}, T{}, F{});
+    if (f8) return v2 ? go_rows(T{}, T{}, F{}) : go_rows(T{}, F{}, F{});
+    return v2 ? go_rows(F{}, T{}, F{}) : go_rows(F{}, F{}, F{});
+}
+
+// NbTorgbArgs of an entry point -> the fused epilogue's TorgbParams (x stays null: it reads the accumulators).  `name` = the entry's
+// message prefix.  (nb_torgb_triad_f32 of nb_ops.hip takes its arguments one by one, not as NbTorgbArgs: it fills its own.)
+static int nb_up1_torgb_params(const char* name, const NbTorgbArgs* t, int c_out, int h, int w, TorgbParams* tg) {
+    NB_REQUIRE(c_out <= 128, "%s: the fused ToRGB needs all channels in one workgroup (c_out <= 128)", name);
+    NB_REQUIRE(t->styles_stride_n >= c_out + 9, "torgb_triad: styles rows must hold 9 color scalars + c styles");
+    NB_REQUIRE(t->render_mode == 0 || t->render_mode == 1, "Unknown render mode for TriadGanPaintEngine: %d", t->render_mode);
+    tg->x = nullptr; tg->styles = t->styles; tg->w = t->w; tg->bias = t->bias; tg->color_bias = t->color_bias;
+    tg->logits = t->logits; tg->uvs = t->uvs; tg->img = t->img; tg->colors_out = t->colors_out; tg->user_colors = t->user_colors;
+    tg->sfactor = t->sfactor; tg->rgba_f32 = t->rgba_f32; tg->rgba_u8 = t->rgba_u8;
+    tg->styles_stride_n = t->styles_stride_n; tg->c = c_out; tg->hw = h * w; tg->render_mode = t->render_mode; tg->clamp = t->clamp;
+    return NB_OK;
 }
 
 extern "C" int nb_modconv3x3_up1_h3_ex(const void* x, int c_in, const void* wts, const float* dcoefs, const float* noise,
@@ -1511,1041 +1473,32 @@ extern "C" int nb_modconv3x3_up1_h3_ex(const void* x, int c_in, const void* wts,
                                       void* stream) {
     NB_REQUIRE(in_fmt >= 0 && in_fmt <= 3, "modconv3x3_up1_h3: operand format must be 0 (H2), 1 (f8), 2 (f6) or 3 (f8 containers, hi x hi products only)");
     if (!t)
-        return nb_up1_h3_impl(x, c_in, wts, dcoefs, noise, noise_stride_n, bias, y_f32, y_h2, next_styles, next_stride, c_next,
-                              n, h, w, c_out, alpha, gain, clamp, stream, nullptr, in_fmt, out_fmt);
+        return nb_up1_h3_impl({x, c_in, wts, dcoefs, noise, noise_stride_n, bias, y_f32, y_h2, next_styles, next_stride, c_next, n, h, w, c_out, alpha, gain, clamp, out_fmt},
+                              stream, nullptr, in_fmt);
     NB_REQUIRE(t->styles && t->w && t->bias && t->color_bias && !y_h2, "modconv3x3_up1_h3_ex: bad ToRGB arguments");
-    NB_REQUIRE(c_out <= 128, "modconv3x3_up1_h3_ex: the fused ToRGB needs all channels in one workgroup (c_out <= 128)");
-    NB_REQUIRE(t->styles_stride_n >= c_out + 9, "torgb_triad: styles rows must hold 9 color scalars + c styles");
-    NB_REQUIRE(t->render_mode == 0 || t->render_mode == 1, "Unknown render mode for TriadGanPaintEngine: %d", t->render_mode);
     TorgbParams tg;
-    tg.x = nullptr; tg.styles = t->styles; tg.w = t->w; tg.bias = t->bias; tg.color_bias = t->color_bias;
-    tg.logits = t->logits; tg.uvs = t->uvs; tg.img = t->img; tg.colors_out = t->colors_out; tg.user_colors = t->user_colors;
-    tg.sfactor = t->sfactor; tg.rgba_f32 = t->rgba_f32; tg.rgba_u8 = t->rgba_u8;
-    tg.styles_stride_n = t->styles_stride_n; tg.c = c_out; tg.hw = h * w; tg.render_mode = t->render_mode; tg.clamp = t->clamp;
-    return nb_up1_h3_impl(x, c_in, wts, dcoefs, noise, noise_stride_n, bias, y_f32, nullptr, nullptr, 0, 0, n, h, w, c_out,
-                          alpha, gain, clamp, stream, &tg, in_fmt, 0);
+    if (const int rc = nb_up1_torgb_params("modconv3x3_up1_h3_ex", t, c_out, h, w, &tg)) return rc;
+    return nb_up1_h3_impl({x, c_in, wts, dcoefs, noise, noise_stride_n, bias, y_f32, nullptr, nullptr, 0, 0, n, h, w, c_out, alpha, gain, clamp, 0}, stream, &tg, in_fmt);
 }
 
 extern "C" int nb_modconv3x3_up1_h3(const void* x_h2, int c_in, const void* w_h3, const float* dcoefs, const float* noise,
                                     int64_t noise_stride_n, const float* bias, float* y, int n, int h, int w, int c_out,
                                     float alpha, float gain, float clamp, void* stream) {
-    return nb_up1_h3_impl(x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, y, nullptr, nullptr, 0, 0, n, h, w, c_out,
-                          alpha, gain, clamp, stream);
+    return nb_up1_h3_impl({x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, y, nullptr, nullptr, 0, 0, n, h, w, c_out, alpha, gain, clamp, 0}, stream);
 }
 
 extern "C" int nb_modconv3x3_up1_h3_torgb(const void* x_h2, int c_in, const void* w_h3, const float* dcoefs, const float* noise,
                                           int64_t noise_stride_n, const float* bias, float* y, int n, int h, int w, int c_out,
                                           float alpha, float gain, float clamp, const NbTorgbArgs* t, void* stream) {
     NB_REQUIRE(t && t->styles && t->w && t->bias && t->color_bias, "modconv3x3_up1_h3_torgb: null pointer");
-    NB_REQUIRE(c_out <= 128, "modconv3x3_up1_h3_torgb: the fused ToRGB needs all channels in one workgroup (c_out <= 128)");
-    NB_REQUIRE(t->styles_stride_n >= c_out + 9, "torgb_triad: styles rows must hold 9 color scalars + c styles");
-    NB_REQUIRE(t->render_mode == 0 || t->render_mode == 1, "Unknown render mode for TriadGanPaintEngine: %d", t->render_mode);
     TorgbParams tg;
-    tg.x = nullptr; tg.styles = t->styles; tg.w = t->w; tg.bias = t->bias; tg.color_bias = t->color_bias;
-    tg.logits = t->logits; tg.uvs = t->uvs; tg.img = t->img; tg.colors_out = t->colors_out; tg.user_colors = t->user_colors;
-    tg.sfactor = t->sfactor; tg.rgba_f32 = t->rgba_f32; tg.rgba_u8 = t->rgba_u8;
-    tg.styles_stride_n = t->styles_stride_n; tg.c = c_out; tg.hw = h * w; tg.render_mode = t->render_mode; tg.clamp = t->clamp;
-    return nb_up1_h3_impl(x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, y, nullptr, nullptr, 0, 0, n, h, w, c_out,
-                          alpha, gain, clamp, stream, &tg);
+    if (const int rc = nb_up1_torgb_params("modconv3x3_up1_h3_torgb", t, c_out, h, w, &tg)) return rc;
+    return nb_up1_h3_impl({x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, y, nullptr, nullptr, 0, 0, n, h, w, c_out, alpha, gain, clamp, 0}, stream, &tg);
 }
 
 extern "C" int nb_modconv3x3_up1_h3_h2(const void* x_h2, int c_in, const void* w_h3, const float* dcoefs, const float* noise,
                                        int64_t noise_stride_n, const float* bias, const float* next_styles, int next_stride,
                                        void* y_h2, int c_next, int n, int h, int w, int c_out, float alpha, float gain,
                                        float clamp, void* stream) {
-    return nb_up1_h3_impl(x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, nullptr, y_h2, next_styles, next_stride,
-                          c_next, n, h, w, c_out, alpha, gain, clamp, stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// up = 2 on the f16 matrix cores: the 4-phase transposed convolution + fused polyphase FIR of
-// nb_modconv.hip (same math, same quad grid: see the comment block there), with split-f16 products.
-//
-// Workgroup = 8 waves, one 12 x 32 quad tile (14 x 34 = 476 halo'd positions = 15 MFMA column blocks of 32, two
-// per wave) x 32 c_out.  All four phases share the staged halo tile (9 taps per staged byte), so every wave
-// carries 2 blocks x 4 phases x 16 = 128 accumulator registers; the A/B fragments are streamed per tap.
-// (12 rows do not divide the image height: the last tile row overhangs and is masked.)  Input H2 (pre-modulated), weights [chunk][tap 9][cg 2][hi/lo 2][c_out_ld][8], output fp32 NCHW.
-// ------------------------------------------------------------------------------------------------
-#ifndef NB_H3_TQH
-#define NB_H3_TQH 12
-#endif
-#define NB_H3_TQH_SMALL 5       // tile height of the under-filled (batch-1) launches
-#define NB_H3_TQH_MID 8         // 10 x 34 = 340 positions = 11 blocks (3 / 3 / 3 / 2 per SIMD): for launches whose 12-row tiles end in a mostly empty round of workgroups
-#define NB_H3_STAGES 3          // LDS-DMA stages of the up=2 kernel (planes at their exact size: 3 x 52 032 B for the 12-row tile)
-
-// TQH = quad rows per tile: NB_H3_TQH (12) for throughput; 5 (7 x 34 = 238 positions = 8 column blocks, one per wave)
-// when the large tiles would leave most of the chip idle - the batch-1 / interactive configuration.
-// OUTM = output mode: 0 = fp32 NCHW, 1 = the consumer's H2 tensor, 2 = the consumer's tensor in the "f8" operand format.
-// TQW_ = quad columns per tile: 32, or 16 for 16-wide inputs (b32.conv0 at large batch: 8 x 16 tiles = 10 x 18 = 180
-// positions = 6 blocks, one per wave).
-// (Tried and dropped, DESIGN.md 6: a one-wave-per-SIMD form with 256 accumulators per wave and a hand-ordered K loop, and two
-//  4-wave workgroups per CU on 5-row tiles -- neither was faster.)
-// NW_ / NST_ = waves per workgroup / LDS-DMA stages: 8 / 3 (one workgroup per CU), or 4 / 2 on 12 x 16 tiles (14 x 18 = 252
-// positions = 8 column blocks, two per wave; 2 x 36.7 KB of staging) so that TWO workgroups share a CU and one's prologue
-// (first-chunk DMA latency) and epilogue (LDS round trip, FIR, conversions, stores: a quarter to a third of a workgroup's
-// life, no matrix work) run under the other's K loop.
-template <bool F8, int TQH, int OUTM = 0, int TQW_ = 32, int NW_ = 8, int NST_ = NB_H3_STAGES>
-__global__ __launch_bounds__(NW_ * 64, 2) void modconv3x3_up2_h3_kernel(const H3Up2Params p) {
-    NB_TSTAMP(0);
-    if constexpr (OUTM == 2) nb_set_fp16_ovfl();
-    nb_stagger(p.stagger_ticks, 256);
-    constexpr int NW = NW_, NT = NW_ * 64, TQW = TQW_, PH = TQH + 2, PW = TQW + 2, NPOS = PH * PW;     // 476
-    constexpr int NBLK = (NPOS + 31) / 32;            // 15 position blocks
-    constexpr int NBJ = (NBLK + NW - 1) / NW;         // blocks per wave (2)
-    constexpr int XR = TQH + 3, XS = TQW + 3;         // halo tile 15 x 35 input pixels
-    // planes are packed at their exact size (the last 1-KiB DMA piece of a plane is partial: lanes past the plane do not
-    // copy), which is what lets THREE stages of the 12-row tile fit the 160 KiB of LDS
-    constexpr int SLOTS = XR * XS, PP = (SLOTS + 63) / 64, XPL = SLOTS;         // 525 slots -> 9 pieces
-    constexpr int NXP = 4 * PP, NXPW = (NXP + NW - 1) / NW;                     // 36 -> 5 per wave
-    constexpr int WSLOTS = 36 * 32, NWP = WSLOTS / 64, NWPW = (NWP + NW - 1) / NW;   // 18 -> 3 per wave
-    // LDS-DMA pieces a wave issues per chunk: the 36 activation + 18 weight pieces are ONE list dealt round-robin to the waves
-    // (7 each, 2 re-copies; dealt per kind it was 5 + 3 = 8 each with 10 re-copies -- and a piece is a KiB through the CU's
-    // vector-memory path whether anybody needs it or not)
-    constexpr int NPC = (NXP + NWP + NW - 1) / NW;
-    constexpr int STAGE = 4 * XPL + WSLOTS;           // 16-byte slots per stage
-    constexpr int NST = NST_;                         // 3 (2: the two-workgroups-per-CU form)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_h3[];
-    h8* ring = reinterpret_cast<h8*>(smem_h3);        // [NST][ x: 4 planes x XPL | w: 36 rows x 32 ]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lh = lane >> 5, l31 = lane & 31;
-    const int H = p.h, W = p.w;
-    int b = blockIdx.x;
-    // XCD-aware order: consecutive workgroup ids go round-robin to the 8 XCDs (each with its own L2), so the c_out
-    // slices of one input tile -- which re-read the same activations -- are renumbered to share an XCD
-    // (the XCD's share of the tile list rotates with the sample: the cheap tiles of a ragged last tile row -- see the K loop's
-    //  copies below -- would otherwise all sit on the last XCDs, which then idle while the others finish)
-    if (gridDim.x % 8 == 0 && !(p.dbg & 8)) b = (((b & 7) + blockIdx.y) & 7) * (gridDim.x >> 3) + (b >> 3);
-    const int slice = b % p.slices; b /= p.slices;
-    const int tile_x = b % p.tiles_x; const int tile_y = b / p.tiles_x;
-    const int n = blockIdx.y;
-    const int I0 = tile_y * TQH, J0 = tile_x * TQW;
-    const int co0 = slice * 32;
-    const size_t HW8 = (size_t)H * W * 8;
-    const _Float16* xn = p.x + (size_t)n * p.c8 * 2 * HW8;
-    const int nblk = wv < NBLK - (NBJ - 1) * NW ? NBJ : NBJ - 1;      // blocks wv, wv+8 (< 15)
-
-    // epilogue operands fetched under the prologue DMA: demodulation / bias per channel and the tile's noise
-    __shared__ __attribute__((aligned(16))) float s_dco[32], s_bias[32], s_nst[32];
-    __shared__ __attribute__((aligned(16))) float s_noise[2 * TQH * 2 * TQW];
-    if (tid < 32) {
-        const int co = co0 + tid;
-        // the activation gain is folded into the three addends: lrelu(g t) = g lrelu(t) for g > 0 (the launcher checks)
-        float dg = co < p.c_out ? p.dcoefs[(size_t)n * p.c_out + co] * p.gain : 0.f;
-        float bv = co < p.c_out ? p.bias[co] : 0.f;
-        // (the two `* gain` must not meet in one packed instruction: the SLP vectoriser pairs them as v_pk_mul_f32 with the gain
-        //  broadcast through op_sel:[1,0] in some instantiations -- a swizzled packed form, see NB_NO_PACKED_F32 in nb_common.h)
-        asm volatile("" : "+v"(dg), "+v"(bv));
-        s_dco[tid] = dg;
-        s_bias[tid] = bv * p.gain;
-        s_nst[tid] = (p.yh2 && co < p.c_out) ? p.next_styles[(size_t)n * p.next_stride + co] : 0.f;
-    }
-    // LDS-DMA descriptors of this wave's pieces.  Activation piece i: plane xpl (= cg_local*2 + hi/lo), 64 slots from
-    // `part`; xsp = element offset of the lane's source slot inside a plane (-1: outside the image -> zero page),
-    // xok = the lane's slot belongs to the plane (the last piece of a plane is partial)
-    int xsp[NXPW], xpl[NXPW], xdst[NXPW];
-    bool xok[NXPW];
-#pragma unroll
-    for (int i = 0; i < NXPW; ++i) {
-        int q = i * NW + wv;
-        q = q < NXP ? q : NXP - 1;
-        const int pl = q / PP, part = q - pl * PP;
-        const int e = part * 64 + lane;
-        xpl[i] = pl;
-        xdst[i] = pl * XPL + part * 64;
-        xsp[i] = -1;
-        xok[i] = e < SLOTS;
-        if (e < SLOTS) {
-            const int r = e / XS, c = e - r * XS;
-            const int gy = I0 - 1 + r, gx = J0 - 1 + c;
-            if (gy >= 0 && gy < H && gx >= 0 && gx < W) xsp[i] = (gy * W + gx) * 8;
-        }
-    }
-    // piece k of chunk c into stage st: k < NXPW activations, else weights
-    auto issue_piece = [&](auto kk, int c, h8* st) {
-        constexpr int k = decltype(kk)::value;
-        // list position u = k NW + wv: activation piece u (descriptor k of this wave) if u < NXP, else weight piece u - NXP
-        constexpr bool ALLX = k * NW + NW - 1 < NXP, ALLW = k * NW >= NXP;
-        const _Float16* xsrc = reinterpret_cast<const _Float16*>(p.zeros);
-        h8* xd = st;
-        bool xo = false;
-        if constexpr (!ALLW) {
-            const int cg = 2 * c + (xpl[k] >> 1);
-            if (xsp[k] >= 0 && cg < p.c8) xsrc = xn + (size_t)(4 * c + xpl[k]) * HW8 + xsp[k];
-            xd = st + xdst[k]; xo = xok[k];
-        }
-        if constexpr (ALLX) {
-            if (xo) nb_lds_dma16(xsrc, xd);
-        } else {
-            int q = k * NW + wv - NXP;
-            q = q < 0 ? 0 : (q < NWP ? q : NWP - 1);
-            const int e = q * 64 + lane;
-            const int row = e >> 5, j = e & 31;           // row = tap*4 + cg*2 + hl
-            const _Float16* wsrc = p.wts + (((size_t)c * 36 + row) * p.co_ld + co0 + j) * 8;
-            h8* wd = st + 4 * XPL + q * 64;
-            if constexpr (ALLW) {
-                nb_lds_dma16(wsrc, wd);
-            } else {                                      // the round where the list changes kind: a wave issues ONE of the two (the
-                const bool isx = k * NW + wv < NXP;       // other has no lane enabled, and such an instruction does not exist for vmcnt)
-                if (isx && xo) nb_lds_dma16(xsrc, xd);
-                if (!isx) nb_lds_dma16(wsrc, wd);
-            }
-        }
-    };
-    auto issue = [&](int c, h8* st) { nb_static_for<0, NPC>([&](auto k) { issue_piece(k, c, st); }); };
-    // the pieces of one chunk spread over S points of the MFMA stream: point s issues pieces [s NPC / S, (s+1) NPC / S)
-    auto issue_at = [&](auto ss, auto SS, int c, h8* st) {
-        constexpr int s_ = decltype(ss)::value, S_ = decltype(SS)::value;
-        nb_static_for<s_ * NPC / S_, (s_ + 1) * NPC / S_>([&](auto k) { issue_piece(k, c, st); });
-    };
-
-    // B-fragment base slots: position (r, c) of block (wv + 8j); X(r, c) = slot r*XS + c of plane (lh*2 + hl)
-    int boff[NBJ];
-#pragma unroll
-    for (int j = 0; j < NBJ; ++j) {
-        int pidx = (wv + NW * j) * 32 + l31;
-        pidx = pidx < NPOS ? pidx : NPOS - 1;
-        const int r = pidx / PW, c = pidx - r * PW;
-        boff[j] = lh * 2 * XPL + r * XS + c;
-    }
-    const int aoff = 4 * XPL + lh * 2 * 32 + l31;     // + tap*128 + hl*32
-
-    f32x16 acc[NBJ][4];
-#pragma unroll
-    for (int j = 0; j < NBJ; ++j)
-#pragma unroll
-        for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][ph][r] = 0.f;
-
-    // ---- K loop: 16-channel chunks through a THREE-stage LDS ring.  Chunk c is read from stage c % 3 while the LDS-DMA
-    //      pieces of chunk c+2 are issued one or two at a time BETWEEN the chunk's MFMA groups (a piece costs the issuing
-    //      wave ~60 cycles among MFMAs, 100-185 in a burst next to the fragment reads -- and after a barrier both waves of a
-    //      SIMD would burst at the same moment, with nobody feeding the matrix pipe: that burst was a third of the K loop
-    //      of the 2-stage form).  One wait + barrier per chunk: vmcnt(NPC) = everything but the pieces just issued, i.e.
-    //      chunk c+1 (issued a whole chunk ago) has landed; the barrier also frees stage (c-1) % 3 = (c+2) % 3 for the
-    //      next chunk's pieces.  The last two chunks issue nothing (own copies of the body: no branch inside it). ----
-    const int NC = p.nchunks;
-    static_assert(NST == 3 || NST == 2, "ring indices below are written for three (or two) stages");
-    issue(0, ring);
-    // the tile's noise values (epilogue operand), computed or fetched while chunk 0 is on its way: with the in-kernel noise
-    // (NbNoiseSrc) that is ~150 VALU instructions per thread, which cost 1 us of prologue when they ran ahead of the first DMA
-    for (int e = tid; e < 2 * TQH * 2 * TQW; e += NT) {
-        const int r = e / (2 * TQW), c = e - r * (2 * TQW);
-        const int oy = 2 * I0 + r, ox = 2 * J0 + c;
-        float v = (p.noise && oy < 2 * H) ? p.noise[(size_t)n * p.noise_stride_n + (size_t)oy * (2 * W) + ox] : 0.f;
-        if (p.nsrc.const_t && oy < 2 * H) {
-            float np0, np1, wx0, wx1, wy0, wy1;
-            int sx0, sy0;
-            nb_noise_np(p.nsrc, n, np0, np1);
-            nb_noise_axis(p.nsrc, oy, np0, sx0, wx0, wx1);
-            nb_noise_axis(p.nsrc, ox, np1, sy0, wy0, wy1);
-            v = nb_noise_value(p.nsrc, p.nsrc.strength[0], sx0, wx0, wx1, sy0, wy0, wy1);
-        }
-        s_noise[e] = v * p.gain;
-    }
-
-    if (NC > 1 && NST == 3) {
-        issue(1, ring + STAGE);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC) : "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    NB_TSTAMP(1);
-    // tap (a,b) row-major -> (slot offset of its input pixel, output phase): x11 = X(r,c), x10 = X(r,c+1),
-    // x01 = X(r+1,c), x00 = X(r+1,c+1).  Only four distinct offsets occur, so the taps are walked grouped by offset:
-    // one pair of B fragments (hi, lo) per block serves up to four taps, and the A fragments of the next tap (and the
-    // B fragments of the next group) are fetched under the six MFMAs of the current tap.
-    constexpr int kOrd[9] = {4, 5, 7, 8, 3, 6, 1, 2, 0};
-    constexpr int kDel[9] = {0, 0, 0, 0, 1, 1, XS, XS, XS + 1};          // slot offset, in walk order
-    constexpr int kGrp[9] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
-    constexpr int kPha[9] = {3, 2, 1, 0, 2, 0, 1, 0, 0};                 // kTapPhase[kOrd[i]]
-    unsigned long long t_dma = 0, t_bar = 0;
-    const unsigned long long t_loop0 = p.tstamps ? __builtin_amdgcn_s_memtime() : 0;
-    // one chunk: reads from `st`; DMA = issue the pieces of chunk cn into `sn` between the MFMA groups
-    // (Measured, round 3 -- an ablation build without the in-loop pieces, and one that also drops the barrier: the pieces cost
-    //  ~480 of a chunk's ~3 550 cycles wherever they sit in the chunk, also with the two waves of a SIMD issuing theirs at
-    //  different points; the barrier costs nothing; the loop without DMA still needs ~3 050 cycles for 2 432 cycles of MFMA.
-    //  A variant with masked out-of-image lanes and pre-zeroed halo slots saved registers but is WRONG: a piece whose lanes
-    //  are all masked is skipped, and the counted vmcnt waits below rely on every wave issuing exactly NPC pieces per chunk.)
-    auto chunk = [&](auto dma_, auto nbe_, const h8* st, int cn, h8* sn) {
-        constexpr bool DMA = decltype(dma_)::value;
-        constexpr int NBE = decltype(nbe_)::value & 3;      // column blocks this wave multiplies (a wave whose second block does not exist skips its MFMAs and reads)
-        // ... and how many of them take all four phases.  The LAST block of a full tile lies wholly in the last halo row
-        // (positions 448 .. 475 of the 14 x 34), which the FIR reads in the odd-row phases only (oe, oo: rows ti .. ti+2 of a quad;
-        // ee, eo: ti, ti+1): its six even-row taps and their fragment reads are left out (nbe_ & 4).
-        constexpr int NB01 = (decltype(nbe_)::value & 4) ? NBE - 1 : NBE;
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (F8) {
-            // "f8" operands (see modconv3x3_up1_h3_kernel): one f16 MFMA per tap for the main product, and the two
-            // correction products of a PAIR of taps that feed the same output phase on one block-scaled fp8 MFMA:
-            //   phase 0 (ee): taps (8,6) and (2,0)   phase 1 (eo): (7,1)   phase 2 (oe): (5,3)   phase 3 (oo): 4 alone
-            // walked so that the B fragments of input offsets 0 and 1 are loaded once and those of XS / XS+1 replace them.
-            const int sa = lh ? 116 : 127, sb = lh ? 129 : 118;
-            const h8 z8 = {};
-            h8 b0h[NBJ] = {}, b0l[NBJ] = {}, b1h[NBJ] = {}, b1l[NBJ] = {}, b2h[NBJ] = {}, b2l[NBJ] = {};
-            h8 a1h = {}, a1l = {}, a2h = {}, a2l = {}, n1h = {}, n1l = {}, n2h = {}, n2l = {};
-            using S4 = std::integral_constant<int, 4>;
-#ifdef NB_ABL_NOREAD      // developer ablation (tools/build_variant.sh; timing only, wrong results): no fragment reads
-#define NB_RD(dst, src) asm volatile("" : "+v"(dst))
-#else
-#define NB_RD(dst, src) dst = (src)
-#endif
-#define NB_LDA(tap, hi, lo) { NB_RD(hi, st[aoff + (tap) * 128]); NB_RD(lo, st[aoff + (tap) * 128 + 32]); }
-#define NB_LDB(del, hi, lo) { _Pragma("unroll") for (int j = 0; j < NB01; ++j) { NB_RD(hi[j], st[boff[j] + (del)]); NB_RD(lo[j], st[boff[j] + XPL + (del)]); } }
-#define NB_PAIR(ph, ah_a, al_a, bha, bla, ah_b, al_b, bhb, blb)                                                                   \
-            { _Pragma("unroll") for (int j = 0; j < ((ph) >= 2 ? NBE : NB01); ++j) {                                               \
-                f32x16& a_ = acc[j][ph];                                                                                           \
-                a_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_a, bha[j], a_, 0, 0, 0);                                            \
-                a_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_b, bhb[j], a_, 0, 0, 0);                                            \
-                a_ = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(nb_cat8(al_a, al_b), nb_cat8(bla[j], blb[j]), a_, 0, 0, 0, sa, 0, sb); } }
-#ifdef NB_ABL_NODMA       // developer ablation: no LDS-DMA inside the K loop (the chunks read what the prologue staged)
-#define NB_DMA(slot) {}
-#else
-#define NB_DMA(slot) { if constexpr (DMA) { __builtin_amdgcn_sched_barrier(0); issue_at(std::integral_constant<int, slot>{}, S4{}, cn, sn); __builtin_amdgcn_sched_barrier(0); } }
-#endif
-            // Program order = issue order (a scheduling fence after every group): left to itself the scheduler sinks each
-            // fragment read to just before its first use (register pressure), and every MFMA group then starts with an
-            // exposed `s_waitcnt lgkmcnt(0)`.  With the reads of the NEXT group issued before the current group's MFMAs the
-            // compiler's own wait bookkeeping emits counted waits (lgkmcnt(4), (2), (8), ...) and the reads return under
-            // 256 cycles of matrix work.
-#define NB_FENCE() __builtin_amdgcn_sched_barrier(0)
-            // first group's operands in the order its MFMAs take them (the counted waits then release the first MFMA after
-            // three reads, not after all sixteen), then the second group's A fragments
-            NB_RD(a1h, st[aoff + 8 * 128]);
-#pragma unroll
-            for (int j = 0; j < NBE; ++j) NB_RD(b0h[j], st[boff[j]]);
-            NB_RD(a2h, st[aoff + 6 * 128]);
-#pragma unroll
-            for (int j = 0; j < NBE; ++j) NB_RD(b1h[j], st[boff[j] + 1]);
-            NB_RD(a1l, st[aoff + 8 * 128 + 32]); NB_RD(a2l, st[aoff + 6 * 128 + 32]);
-#pragma unroll
-            for (int j = 0; j < NBE; ++j) { NB_RD(b0l[j], st[boff[j] + XPL]); NB_RD(b1l[j], st[boff[j] + XPL + 1]); }
-            NB_LDA(5, n1h, n1l); NB_LDA(3, n2h, n2l);                             // (for the second group)
-            NB_FENCE();
-            NB_PAIR(0, a1h, a1l, b0h, b0l, a2h, a2l, b1h, b1l);                   // taps 8, 6
-            NB_FENCE();
-            NB_DMA(0);
-            NB_LDA(4, a1h, a1l);                                                  // (for the third group)
-            NB_FENCE();
-            NB_PAIR(2, n1h, n1l, b0h, b0l, n2h, n2l, b1h, b1l);                   // taps 5, 3
-            NB_FENCE();
-            NB_DMA(1);
-            NB_LDB(XS, b1h, b1l); NB_LDA(7, n1h, n1l); NB_LDA(1, n2h, n2l);       // (for the fourth group)
-            NB_FENCE();
-#pragma unroll
-            for (int j = 0; j < NBE; ++j) {                                       // tap 4 alone
-                f32x16& a_ = acc[j][3];
-                a_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, b0h[j], a_, 0, 0, 0);
-                a_ = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(nb_cat8(a1l, z8), nb_cat8(b0l[j], z8), a_, 0, 0, 0, sa, 0, sb);
-            }
-            NB_FENCE();
-            NB_DMA(2);
-            NB_LDB(XS + 1, b2h, b2l); NB_LDA(2, a1h, a1l); NB_LDA(0, a2h, a2l);   // (for the fifth group)
-            NB_FENCE();
-            NB_PAIR(1, n1h, n1l, b0h, b0l, n2h, n2l, b1h, b1l);                   // taps 7, 1
-            NB_FENCE();
-            NB_DMA(3);
-            NB_PAIR(0, a1h, a1l, b1h, b1l, a2h, a2l, b2h, b2l);                   // taps 2, 0
-#undef NB_FENCE
-#undef NB_LDA
-#undef NB_LDB
-#undef NB_PAIR
-#undef NB_DMA
-        } else {
-            h8 ah[2], al[2], bh[2][NBJ], bl[2][NBJ];
-            ah[0] = st[aoff + kOrd[0] * 128]; al[0] = st[aoff + kOrd[0] * 128 + 32];
-#pragma unroll
-            for (int j = 0; j < NBE; ++j) { bh[0][j] = st[boff[j] + kDel[0]]; bl[0][j] = st[boff[j] + XPL + kDel[0]]; }
-            nb_static_for<0, 9>([&](auto ii) {
-                constexpr int i = decltype(ii)::value;
-                constexpr int ca = i & 1, cb = kGrp[i] & 1;
-                constexpr int NBT = kPha[i] >= 2 ? NBE : NB01;            // blocks that take this tap
-                constexpr int NBF = kGrp[i + 1 < 9 ? i + 1 : i] >= 2 ? NB01 : NBE;      // blocks that need the next offset group's B fragments (groups 2, 3 = taps 1, 2, 0: even-row phases only)
-                f32x16& a0 = acc[0][kPha[i]];
-                if constexpr (NBT > 0) a0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bh[cb][0], a0, 0, 0, 0);
-                constexpr int nfetch = i + 1 < 9 ? (kGrp[i + 1 < 9 ? i + 1 : i] != kGrp[i] ? 2 + 2 * NBF : 2) : 0;
-                if constexpr (i + 1 < 9) {
-                    ah[ca ^ 1] = st[aoff + kOrd[i + 1] * 128]; al[ca ^ 1] = st[aoff + kOrd[i + 1] * 128 + 32];
-                    if constexpr (kGrp[i + 1] != kGrp[i]) {
-#pragma unroll
-                        for (int j = 0; j < NBF; ++j) {
-                            bh[cb ^ 1][j] = st[boff[j] + kDel[i + 1]]; bl[cb ^ 1][j] = st[boff[j] + XPL + kDel[i + 1]];
-                        }
-                    }
-                }
-                if constexpr (NBT > 0) {
-                    a0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bl[cb][0], a0, 0, 0, 0);
-                    a0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ca], bh[cb][0], a0, 0, 0, 0);
-                }
-#pragma unroll
-                for (int j = 1; j < NBT; ++j) {
-                    f32x16& aj = acc[j][kPha[i]];
-                    aj = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bh[cb][j], aj, 0, 0, 0);
-                    aj = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bl[cb][j], aj, 0, 0, 0);
-                    aj = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ca], bh[cb][j], aj, 0, 0, 0);
-                }
-                // next tap's fragment reads go out BEFORE this tap's six MFMAs (their registers are free: the previous tap
-                // has issued), which gives the LDS the whole tap to answer
-                if constexpr (nfetch > 0) __builtin_amdgcn_sched_group_barrier(0x100, nfetch, 0);
-                if constexpr (NBT > 0) __builtin_amdgcn_sched_group_barrier(0x008, 3 * NBT, 0);
-                // this chunk's share of the next-but-one chunk's LDS-DMA pieces, behind the tap's MFMAs (taps 0..7)
-                if constexpr (DMA && i < 8) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    issue_at(ii, std::integral_constant<int, 8>{}, cn, sn);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            });
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto kloop = [&](auto nbe) {
-    int c = 0;
-    int s_cur = 0;                                    // stage of chunk c
-    if constexpr (NST == 2) {
-        // two stages: chunk c+1 lands in the other stage while chunk c is multiplied; the wait at the end of a chunk is for
-        // pieces issued during it -- exposed latency that the co-resident workgroup's matrix work covers
-        for (; c + 1 < NC; ++c) {
-            chunk(std::true_type{}, nbe, ring + s_cur * STAGE, c + 1, ring + (s_cur ^ 1) * STAGE);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            s_cur ^= 1;
-        }
-    }
-    for (; NST == 3 && c + 2 < NC; ++c) {
-        const int s_nn = s_cur == 0 ? 2 : s_cur - 1;  // (c + 2) % 3
-        chunk(std::true_type{}, nbe, ring + s_cur * STAGE, c + 2, ring + s_nn * STAGE);
-        // chunk c+1 has landed (the pieces of c+2 may stay in flight); everybody is done reading chunk c
-        // (no timestamp reads in here: the branches around them split the loop body into several basic blocks, and the
-        //  compiler then sinks MFMAs past the wait and the barrier)
-#ifdef NB_ABL_NODMA
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC) : "memory");
-#endif
-#ifndef NB_ABL_NOBARRIER
-        __builtin_amdgcn_s_barrier();
-#endif
-        s_cur = s_cur == 2 ? 0 : s_cur + 1;
-    }
-    for (; c < NC; ++c) {
-        chunk(std::false_type{}, nbe, ring + s_cur * STAGE, 0, nullptr);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        s_cur = s_cur == NST - 1 ? 0 : s_cur + 1;
-    }
-    };
-    // (copies of the loop per number of column blocks a wave really has to multiply: blocks that do not exist -- the 16th of the
-    //  15-block tile -- or lie wholly below the image -- the last tile row of a height that 12 does not divide -- cost no MFMAs and
-    //  no fragment reads; the DMA pieces and barriers are the same in every copy.  Their accumulators stay zero; nothing that is
-    //  stored reads them.)
-    const int nvalid_blk = (min(TQH, H - I0) + 2) * PW;                  // positions of the rows that feed stored pixels ...
-    int nbe_w = 0;                                                       // ... and this wave's blocks that hold any of them
-#pragma unroll
-    for (int j = 0; j < NBJ; ++j) nbe_w += (wv + NW * j) * 32 < nvalid_blk && j < nblk;
-    // the wave whose last multiplied block is the tile's last one, when that block holds nothing but the last halo row
-    constexpr bool LASTROW_BLK = (NBLK - 1) * 32 >= (PH - 1) * PW;
-    const bool half_last = LASTROW_BLK && !(p.dbg & 16) && wv == (NBLK - 1) % NW && nbe_w == (NBLK - 1) / NW + 1;
-    if constexpr (NBJ > 1) {
-        if (nbe_w == 2) { if (half_last) kloop(std::integral_constant<int, 2 | 4>{}); else kloop(std::integral_constant<int, 2>{}); }
-        else if (nbe_w == 1) { if (half_last) kloop(std::integral_constant<int, 1 | 4>{}); else kloop(std::integral_constant<int, 1>{}); }
-        else kloop(std::integral_constant<int, 0>{});
-    } else {
-        if (nbe_w == 1) { if (half_last) kloop(std::integral_constant<int, 1 | 4>{}); else kloop(std::integral_constant<int, 1>{}); }
-        else kloop(std::integral_constant<int, 0>{});
-    }
-    if (p.tstamps && tid == 0) {
-        unsigned long long* ts = p.tstamps + (size_t)(blockIdx.x + blockIdx.y * gridDim.x) * 8;
-        ts[6] = t_dma; ts[7] = t_bar | ((__builtin_amdgcn_s_memtime() - t_loop0) << 32);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // drain before the staging LDS is reused
-    __builtin_amdgcn_s_barrier();
-
-    NB_TSTAMP(2);
-    if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) p.y[0] = 0.f; return; }      // ablation: main loop only
-    // ---- epilogue: 2 rounds of 16 c_out.  Accumulator register rho <-> c_out row (rho&3) + 8(rho>>2) + 4*lh, so the four
-    //      registers rho = 4g..4g+3 of a lane are four CONSECUTIVE channels: they go to LDS as one 16-byte slot
-    //      y4[g&1][lh][phase][position].  Then one item = one quad (2 x 2 output pixels) x those 4 channels: 25 slot reads,
-    //      the separable polyphase FIR with every instruction packed over channel pairs (no lane-half shuffles), activation,
-    //      hi/lo split and fp8 conversion in registers.  Lanes l and l+32 hold the two channel halves of the same quad and
-    //      trade rows with v_permlane32_swap, after which a lane owns 8 channels of one output row of the quad = whole
-    //      16-byte H2 slots (8-byte halves of the f8 slots) that go straight to global memory: no staging buffer, no
-    //      transposition stage, 4 barriers instead of 12. ----
-    const int Wo = 2 * W, Ho = 2 * H;
-    constexpr int nquads = TQH * TQW;
-    constexpr int Y1P = NBLK * 32;                    // slots per (g, lh, phase) plane
-    f32x4* y4 = reinterpret_cast<f32x4*>(smem_h3);
-    const float clampv = p.clamp >= 0.f ? p.clamp : __builtin_inff();     // (no clamp: med3 against +-inf)
-    unsigned long long te_w = 0, te_f = 0, te0 = 0;   // debug: cycles in (phase write + sync), (items)
-#pragma unroll
-    for (int R = 0; R < 2; ++R) {
-        if (p.tstamps) te0 = __builtin_amdgcn_s_memtime();
-        // LDS-only barriers: __syncthreads() would also wait (vmcnt(0)) for the previous round's global stores to retire
-        if (R) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // the previous round's reads are done
-#pragma unroll
-        for (int gs = 0; gs < 2; ++gs) {
-            const int r0 = (2 * R + gs) * 4;
-#pragma unroll
-            for (int j = 0; j < NBJ; ++j) {
-                if (j < nblk) {
-                    const int pidx = (wv + NW * j) * 32 + l31;
-#pragma unroll
-                    for (int ph = 0; ph < 4; ++ph)
-                        y4[((gs * 2 + lh) * 4 + ph) * Y1P + pidx] = f32x4{acc[j][ph][r0], acc[j][ph][r0 + 1], acc[j][ph][r0 + 2], acc[j][ph][r0 + 3]};
-                }
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (p.tstamps) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); te_w += t_ - te0; te0 = t_; }
-        auto quad_item = [&](const int wi) {
-            const int hq = wi * 32 + l31;             // (g, quad); lane half = channel half
-            const int gs = hq / nquads, qd = hq - gs * nquads;
-            const int ti = qd / TQW, tj = qd - ti * TQW;
-            if (I0 + ti >= H) return;                 // quad row below the image (ragged last tile row): nothing of it is stored
-            const int c4 = 8 * (2 * R + gs) + 4 * lh; // the lane's four channels within the slice
-            const f32x4* ee = y4 + ((gs * 2 + lh) * 4) * Y1P + ti * PW + tj;
-            const f32x4* eo = ee + 1 * Y1P;
-            const f32x4* oe = ee + 2 * Y1P;
-            const f32x4* oo = ee + 3 * Y1P;
-            // horizontal pass first (nb_up2_hrow, nb_h3_common.h): the quad's five pre-filter rows O(ti), E(ti), O(ti + 1), E(ti + 1),
-            // O(ti + 2) at its two output columns; then one vertical FIR per output row (nb_up2_vout) -- the per-output order of
-            // modconv3x3_up2v_kernel, which shares the filtered rows along a column run of quads
-            f32x4 hr[5][2];
-#pragma unroll
-            for (int m = 0; m < 5; ++m) {
-                if (m & 1) nb_up2_hrow(ee + (m >> 1) * PW, eo + (m >> 1) * PW, hr[m]);
-                else nb_up2_hrow(oe + (m >> 1) * PW, oo + (m >> 1) * PW, hr[m]);
-            }
-            const f32x4 d4 = *reinterpret_cast<const f32x4*>(s_dco + c4), b4 = *reinterpret_cast<const f32x4*>(s_bias + c4);
-            const int qi = I0 + ti, qj = J0 + tj;
-            f32x4 v[2][2];                            // [dy][px]
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy) {
-                const f32x2 nz = *reinterpret_cast<const f32x2*>(s_noise + (2 * ti + dy) * (2 * TQW) + 2 * tj);
-                // The two noise values get registers of their own.  Left in the loaded pair, the compiler adds the second one
-                // as `v_pk_add_f32 d, bias, v[pair] op_sel:[0,1]` (low result reads the pair's HIGH dword), and that
-                // instruction returned, for 8-16 lanes of the upper half-wave and run-to-run differently, the sum with the
-                // pair's LOW dword in its low result (measured: tools/determinism_up2.py; waits forced to zero and s_nops
-                // did not change it, this did).
-                float nz0 = nz[0], nz1 = nz[1];
-                asm volatile("v_mov_b32 %0, %0" : "+v"(nz0));
-                asm volatile("v_mov_b32 %0, %0" : "+v"(nz1));
-                nb_up2_vout(hr[dy], hr[dy + 1], hr[dy + 2], hr[dy + 3], d4, b4, nz0, nz1, p.alpha, clampv, v[dy]);
-            }
-            if constexpr (OUTM == 0) {
-                if (qi < H && !(p.dbg & 1)) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int co = co0 + c4 + i;
-                        if (co < p.c_out) {
-                            float* dst = p.y + ((size_t)n * p.c_out + co) * ((size_t)Ho * Wo) + (size_t)(2 * qi) * Wo + 2 * qj;
-                            *reinterpret_cast<f32x2*>(dst) = f32x2{v[0][0][i], v[0][1][i]};
-                            *reinterpret_cast<f32x2*>(dst + Wo) = f32x2{v[1][0][i], v[1][1][i]};
-                        }
-                    }
-                }
-            } else {
-                const f32x4 ns4 = *reinterpret_cast<const f32x4*>(s_nst + c4);
-                unsigned hi[2][2][2], lo[2][2][2];    // [dy][px][dword]: hi = 4 x f16; lo = H2: 4 x f16 residual, f8: {fp8(xl 2^9) x 4, fp8(v/4) x 4}
-#pragma unroll
-                for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                    for (int px = 0; px < 2; ++px) {
-                        f32x4 w = v[dy][px] * ns4;
-                        const h2 h01 = __builtin_convertvector(f32x2{w[0], w[1]}, h2), h23 = __builtin_convertvector(f32x2{w[2], w[3]}, h2);
-                        // residual w - f16(w) as a mixed-precision fma (reads the f16 half directly)
-                        const f32x4 xl = {nb_sub_f16(w[0], h01, false), nb_sub_f16(w[1], h01, true), nb_sub_f16(w[2], h23, false), nb_sub_f16(w[3], h23, true)};
-                        hi[dy][px][0] = __builtin_bit_cast(unsigned, h01); hi[dy][px][1] = __builtin_bit_cast(unsigned, h23);
-                        if constexpr (OUTM == 1) {
-                            const h2 l01 = __builtin_convertvector(f32x2{xl[0], xl[1]}, h2), l23 = __builtin_convertvector(f32x2{xl[2], xl[3]}, h2);
-                            lo[dy][px][0] = __builtin_bit_cast(unsigned, l01); lo[dy][px][1] = __builtin_bit_cast(unsigned, l23);
-                        } else {
-                            // (conversions saturate: FP16_OVFL is set for this kernel)
-                            // (x 2^9 and x 2^-2 inside the conversions: nb_pk4_fp8_sat_scaled)
-                            lo[dy][px][0] = nb_pk4_fp8_sat_scaled(xl[0], xl[1], xl[2], xl[3], 0x1p-9f);
-                            lo[dy][px][1] = nb_pk4_fp8_sat_scaled(w[0], w[1], w[2], w[3], 4.f);
-                        }
-                    }
-                // lanes l (channels 0-3 of the group) and l+32 (channels 4-7) trade rows: afterwards a lane holds output row
-                // dy = lh of the quad with all 8 channels -- a = channels 0-3, b = channels 4-7
-                unsigned ha[2][2], hb[2][2], la[2][2], lb[2][2];     // [px][dword]
-#pragma unroll
-                for (int px = 0; px < 2; ++px)
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        ha[px][k] = hi[0][px][k]; hb[px][k] = hi[1][px][k]; la[px][k] = lo[0][px][k]; lb[px][k] = lo[1][px][k];
-                        nb_swap32(ha[px][k], hb[px][k]);
-                        nb_swap32(la[px][k], lb[px][k]);
-                    }
-                const int cg = co0 / 8 + 2 * R + gs;
-                const int oy = 2 * qi + lh, ox = 2 * qj;
-                if (qi < H && cg * 8 < p.c_out && !(p.dbg & 1)) {
-                    const size_t OHW8 = (size_t)Ho * Wo * 8;
-                    _Float16* yn = p.yh2 + ((size_t)n * p.c8_next + cg) * 2 * OHW8;
-                    const size_t opix8 = ((size_t)oy * Wo + ox) * 8;
-#pragma unroll
-                    for (int px = 0; px < 2; ++px) {
-                        *reinterpret_cast<u32x4*>(yn + opix8 + px * 8) = u32x4{ha[px][0], ha[px][1], hb[px][0], hb[px][1]};
-                        if constexpr (OUTM == 1) {
-                            *reinterpret_cast<u32x4*>(yn + OHW8 + opix8 + px * 8) = u32x4{la[px][0], la[px][1], lb[px][0], lb[px][1]};
-                        } else {
-                            // the 16-channel chunk's two lo slots: (even group, lo) = fp8(xl 2^9) of its 16 channels, (odd group,
-                            // lo) = fp8(v/4); this group's 8 channels are bytes 8 (cg & 1) .. + 7 of both
-                            _Float16* lo_xl = p.yh2 + ((size_t)n * p.c8_next + (cg & ~1)) * 2 * OHW8 + OHW8 + opix8 + px * 8 + (cg & 1) * 4;
-                            *reinterpret_cast<u32x2*>(lo_xl) = u32x2{la[px][0], lb[px][0]};
-                            *reinterpret_cast<u32x2*>(lo_xl + 2 * OHW8) = u32x2{la[px][1], lb[px][1]};
-                        }
-                    }
-                }
-            }
-        };
-        constexpr int NWI = nquads * 2 / 32;          // wave-iterations of 32 quads x both channel halves per round
-        static_assert(nquads * 2 % 32 == 0, "tile quads must fill whole waves");
-        if constexpr (NWI % NW == 0) {
-#pragma unroll
-            for (int k = 0; k < NWI / NW; ++k) quad_item(wv + k * NW);
-        } else {
-            for (int wi = wv; wi < NWI; wi += NW) quad_item(wi);
-        }
-        if (p.tstamps) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); te_f += t_ - te0; }
-    }
-    const unsigned long long te_s = 0;
-    NB_TSTAMP(4);
-    if (p.tstamps) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        NB_TSTAMP(5);
-        if (threadIdx.x == 0) p.tstamps[(size_t)(blockIdx.x + blockIdx.y * gridDim.x) * 8 + 3] = (te_w & 0x1fffff) | ((te_f & 0x1fffff) << 21) | ((te_s & 0x1fffff) << 42);
-    }
-}
-
-static int g_force_tqh = -1;
-// developer / test hook: 0 = automatic tile choice, NB_H3_TQH, NB_H3_TQH_MID or NB_H3_TQH_SMALL = force that tile height
-extern "C" void nb_debug_set_up2_tile(int tqh) { g_force_tqh = tqh; }
-// the 8-wave form with the software-pipelined K loop (nb_modconv_up2v.hip)
-bool nb_up2v_eligible(int in_fmt, int c_in, int h, int w);
-int nb_up2v_launch(H3Up2Params p, int n, int in_fmt, void* stream, unsigned long long* tstamps, int tstamps_cap, bool auto_rows);
-#ifndef NB_UP2V_AUTO
-#define NB_UP2V_AUTO 1          // 1: f8 launches on the 12-row throughput tiles run on the software-pipelined kernel
-#endif
-static int g_force_v2 = -1;
-// developer / test hook: -1 = automatic, 0 = never, 1 = wherever the shape allows (f8 operands, w % 32 == 0; always 12-row tiles)
-extern "C" void nb_debug_set_up2_v2(int mode) { g_force_v2 = mode; }
-static int g_force_pair = -1;
-// developer / test hook: -1 = automatic, 0 / 1 = never / always the two-workgroups-per-CU form (4 waves, 12 x 16 tiles, 2 stages)
-extern "C" void nb_debug_set_up2_pair(int mode) { g_force_pair = mode; }
-template <int TQH, int TQW, bool F8, int OUTM, int NW, int NST>
-static int nb_up2_h3_launch1(const H3Up2Params& p, int n, size_t lds, void* stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)modconv3x3_up2_h3_kernel<F8, TQH, OUTM, TQW, NW, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    dim3 grid(p.tiles_x * p.tiles_y * p.slices, n);
-    hipLaunchKernelGGL((modconv3x3_up2_h3_kernel<F8, TQH, OUTM, TQW, NW, NST>), grid, dim3(NW * 64), lds, (hipStream_t)stream, p);
-    NB_CHECK_LAUNCH("modconv3x3_up2_h3");
-    return NB_OK;
-}
-
-template <int TQH, int TQW = 32, int NW = 8, int NST = NB_H3_STAGES>
-static int nb_up2_h3_launch(H3Up2Params p, int n, int in_fmt, void* stream) {
-    p.tiles_x = p.w / TQW;
-    p.tiles_y = (p.h + TQH - 1) / TQH;
-    p.tstamps = (g_tstamps && (long long)p.tiles_x * p.tiles_y * p.slices * n <= g_tstamps_cap) ? g_tstamps : nullptr;
-    constexpr int XPL = (TQH + 3) * (TQW + 3);
-    constexpr int NBLK_ = ((TQH + 2) * (TQW + 2) + 31) / 32;
-    constexpr size_t lds_stage = (size_t)NST * (4 * XPL + 36 * 32) * 16;
-    static_assert(NBLK_ <= 2 * NW, "two column blocks per wave at most");
-    constexpr size_t lds_epi = (size_t)16 * NBLK_ * 32 * 16;       // epilogue: [2 groups][2 halves][4 phases][positions] x 4 channels fp32
-    const size_t lds = lds_stage > lds_epi ? lds_stage : lds_epi;
-    const int outm = p.yh2 ? (p.out_f8 ? 2 : 1) : 0;
-    if constexpr (NW == 4) {      // the two-per-CU form exists for H2 operands only (its f8 form spills 1-3 registers: not with counted waits)
-        NB_REQUIRE(!in_fmt, "modconv3x3_up2_h3: the two-workgroups-per-CU form takes H2 operands only");
-        return outm == 2 ? nb_up2_h3_launch1<TQH, TQW, false, 2, NW, NST>(p, n, lds, stream) : outm == 1 ? nb_up2_h3_launch1<TQH, TQW, false, 1, NW, NST>(p, n, lds, stream)
-                                                                                               : nb_up2_h3_launch1<TQH, TQW, false, 0, NW, NST>(p, n, lds, stream);
-    } else
-    if (in_fmt)
-        return outm == 2 ? nb_up2_h3_launch1<TQH, TQW, true, 2, NW, NST>(p, n, lds, stream) : outm == 1 ? nb_up2_h3_launch1<TQH, TQW, true, 1, NW, NST>(p, n, lds, stream)
-                                                                                              : nb_up2_h3_launch1<TQH, TQW, true, 0, NW, NST>(p, n, lds, stream);
-    return outm == 2 ? nb_up2_h3_launch1<TQH, TQW, false, 2, NW, NST>(p, n, lds, stream) : outm == 1 ? nb_up2_h3_launch1<TQH, TQW, false, 1, NW, NST>(p, n, lds, stream)
-                                                                                           : nb_up2_h3_launch1<TQH, TQW, false, 0, NW, NST>(p, n, lds, stream);
-}
-
-// which kernel a split-f16 up=2 launch runs on (the debug hooks apply; UP2_WIDE: the one-wave-per-SIMD form of round 4, removed in round 6)
-enum Up2Form { UP2_BIG = 0, UP2_MID, UP2_SMALL, UP2_W16, UP2_PAIR, UP2_WIDE, UP2_V2, UP2_W8 };
-static Up2Form nb_up2_h3_select(int in_fmt, int c_in, int c_out, int n, int h, int w) {
-    const int tiles_x = w / 32, slices = (c_out + 31) / 32;
-    if (w == 16) return UP2_W16;                      // 16-wide inputs: 8 x 16 quad tiles
-    if (w == 8) return UP2_W8;                        // 8 x 8 inputs: the whole image is one 8 x 8 quad tile (4 position blocks)
-    // tile height: the 12-row tiles unless they leave the chip mostly idle (batch-1 / interactive), then 5-row tiles
-    const int force_tqh = g_force_tqh >= 0 ? g_force_tqh : 0;
-    const long wgs_big = (long)n * tiles_x * ((h + NB_H3_TQH - 1) / NB_H3_TQH) * slices;
-    const bool small_tiles = force_tqh ? force_tqh == NB_H3_TQH_SMALL : wgs_big < 160;
-    // 8-row tiles when the 12-row tiles' last round of workgroups would leave most of the chip idle.  Estimate = rounds of 256
-    // workgroups x cost of one (critical SIMD's position blocks 4 / 3, + prologue and epilogue ~ quads): b64.conv0 at batch 32
-    // (32 input rows) is 384 workgroups = 1.5 rounds of 12-row tiles, but 512 = 2 full rounds of 8-row tiles at 0.73 the cost.
-    bool mid_tiles = force_tqh == NB_H3_TQH_MID;
-    if (!force_tqh && !small_tiles) {
-        constexpr long ncu = 256;                     // MI355X (one workgroup of this kernel per CU)
-        const long wgs_mid = (long)n * tiles_x * ((h + NB_H3_TQH_MID - 1) / NB_H3_TQH_MID) * slices;
-        const double est_big = (double)((wgs_big + ncu - 1) / ncu) * 5.4, est_mid = (double)((wgs_mid + ncu - 1) / ncu) * 3.93;
-        mid_tiles = est_mid < 0.9 * est_big;
-    }
-    // two 4-wave workgroups per CU on 12 x 16 tiles (see the kernel's NW_ / NST_) when that launch fills the chip as well
-    const bool pair = !in_fmt && g_force_pair > 0;          // (opt-in through nb_debug_set_up2_pair: not faster than one 8-wave workgroup per CU)
-    if (pair) return UP2_PAIR;
-    // the 12-row throughput tiles of an f8 launch: the kernel with the software-pipelined K loop (same tile, same results)
-    const int force_v2 = g_force_v2;
-    if (force_v2 != 0 && nb_up2v_eligible(in_fmt, c_in, h, w) &&
-        (force_v2 > 0 ? force_tqh == 0 || force_tqh == NB_H3_TQH : (NB_UP2V_AUTO && !mid_tiles && !small_tiles && (force_tqh == 0 || force_tqh == NB_H3_TQH))))
-        return UP2_V2;
-    if (mid_tiles) return UP2_MID;
-    return small_tiles ? UP2_SMALL : UP2_BIG;
-}
-
-static int nb_up2_h3_impl(const void* x_h2, int c_in, const void* w_h3, const float* dcoefs, const float* noise,
-                          int64_t noise_stride_n, const float* bias, float* y, void* y_h2, const float* next_styles,
-                          int next_stride, int c_next, int n, int h, int w, int c_out, float alpha, float gain, float clamp,
-                          void* stream, int in_fmt = 0, int out_fmt = 0) {
-    NB_REQUIRE(in_fmt >= 0 && in_fmt <= 3 && (out_fmt == 0 || out_fmt == 1), "modconv3x3_up2_h3: input operand format must be 0 (H2), 1 (f8), 2 (f6) or 3 (f8, hi only), "
-               "output format 0 or 1 (the up=2 epilogue does not write the f6 format)");
-    NB_REQUIRE(in_fmt == 0 || c_in % 16 == 0, "modconv3x3_up2_h3: the f8 / f6 operand formats need c_in %% 16 == 0 (got %d)", c_in);
-    NB_REQUIRE(out_fmt == 0 || (y_h2 && c_out % 16 == 0 && c_next % 16 == 0), "modconv3x3_up2_h3: f8 output needs an H2 destination and c_out, c_next %% 16 == 0");
-    NB_REQUIRE(x_h2 && w_h3 && dcoefs && bias && ((y != nullptr) != (y_h2 != nullptr)), "modconv3x3_up2_h3: null pointer");
-    NB_REQUIRE(!y_h2 || (next_styles && c_out % 8 == 0 && c_next >= c_out && next_stride >= c_out && (uintptr_t)y_h2 % 16 == 0),
-               "modconv3x3_up2_h3: H2 output needs the consumer's styles, c_out %% 8 == 0 and c_next >= c_out");
-    NB_REQUIRE(n > 0 && n <= 65535 && c_in > 0 && c_out > 0, "modconv3x3_up2_h3: bad sizes");
-    NB_REQUIRE((w % 32 == 0 || w == 16 || w == 8) && h >= 8, "modconv3x3_up2_h3: needs w %% 32 == 0, w == 16 or w == 8 (got %dx%d)", h, w);
-    NB_REQUIRE(alpha >= 0.f && alpha <= 1.f && gain > 0.f, "modconv3x3_up2_h3: leaky-ReLU slope must lie in [0, 1] and the gain be positive (got %g, %g)", alpha, gain);
-    NB_REQUIRE(((uintptr_t)x_h2 | (uintptr_t)w_h3 | (uintptr_t)y) % 16 == 0, "modconv3x3_up2_h3: pointers must be 16-byte aligned");
-    H3Up2Params p;
-    p.x = (const _Float16*)x_h2; p.wts = (const _Float16*)w_h3; p.dcoefs = dcoefs; p.noise = noise; p.bias = bias; p.y = y;
-    p.zeros = nb_zero_page_ptr();
-    NB_REQUIRE(p.zeros, "modconv3x3_up2_h3: could not allocate the zero page");
-    p.noise_stride_n = noise_stride_n;
-    NB_REQUIRE(nb_noise_src_setup(noise, noise_stride_n, 2 * h, 2 * w, &p.noise, &p.noise_stride_n, &p.nsrc) == NB_OK, "modconv3x3_up2_h3: bad NbNoiseSrc (needs the "
-               "transposed constant, the grid row, the strength, exactly one of norm_pos / positions, and res = the %dx%d output)", 2 * h, 2 * w);
-    p.c8 = (c_in + 7) / 8; p.nchunks = (c_in + 15) / 16; p.c_out = c_out; p.co_ld = (c_out + 63) / 64 * 64; p.h = h; p.w = w;
-    p.dbg = g_nb_debug_flags; p.stagger_ticks = g_nb_stagger_ticks;            // (developer hooks: nb_debug_set_flags / nb_debug_set_stagger)
-    p.alpha = alpha; p.gain = gain; p.clamp = clamp;
-    p.tiles_x = w / 32; p.slices = (c_out + 31) / 32;
-    p.yh2 = (_Float16*)y_h2; p.next_styles = next_styles; p.next_stride = next_stride; p.c8_next = (c_next + 7) / 8;
-    p.out_f8 = out_fmt;
-    const Up2Form form = nb_up2_h3_select(in_fmt, c_in, c_out, n, h, w);
-    NB_REQUIRE(in_fmt != 2 || form == UP2_V2, "modconv3x3_up2_h3: f6 operands are taken by the 12-row software-pipelined kernel only (this launch: %dx%d, batch %d)", h, w, n);
-    switch (form) {
-        case UP2_W16: return nb_up2_h3_launch<8, 16>(p, n, in_fmt, stream);
-        case UP2_W8: return nb_up2_h3_launch<8, 8>(p, n, in_fmt, stream);
-        case UP2_PAIR: return nb_up2_h3_launch<NB_H3_TQH, 16, 4, 2>(p, n, in_fmt, stream);
-        case UP2_V2: return nb_up2v_launch(p, n, in_fmt, stream, g_tstamps, g_tstamps_cap, g_force_v2 < 0);      // (forced: 12-row tiles)
-        case UP2_MID: return nb_up2_h3_launch<NB_H3_TQH_MID>(p, n, in_fmt, stream);
-        case UP2_SMALL: return nb_up2_h3_launch<NB_H3_TQH_SMALL>(p, n, in_fmt, stream);
-        default: return nb_up2_h3_launch<NB_H3_TQH>(p, n, in_fmt, stream);
-    }
-}
-
-extern "C" int nb_modconv3x3_up2_h3_variant(int in_fmt, int c_in, int c_out, int n, int h, int w, char* buf, int buflen) {
-    NB_REQUIRE(buf && buflen > 0, "modconv3x3_up2_h3_variant: bad buffer");
-    NB_REQUIRE(in_fmt >= 0 && in_fmt <= 3 && n > 0 && c_in > 0 && c_out > 0 && h >= 8 && (w % 32 == 0 || w == 16 || w == 8), "modconv3x3_up2_h3_variant: bad shape");
-    static const char* const names[] = {"modconv3x3_up2_h3_kernel", "modconv3x3_up2_h3_kernel", "modconv3x3_up2_h3_kernel", "modconv3x3_up2_h3_kernel",
-                                        "modconv3x3_up2_h3_kernel", "modconv3x3_up2_h3_kernel", "modconv3x3_up2v_kernel", "modconv3x3_up2_h3_kernel"};
-    snprintf(buf, buflen, "%s", names[nb_up2_h3_select(in_fmt, c_in, c_out, n, h, w)]);
-    return NB_OK;
-}
-
-extern "C" int nb_modconv3x3_up2_h3(const void* x_h2, int c_in, const void* w_h3, const float* dcoefs, const float* noise,
-                                    int64_t noise_stride_n, const float* bias, float* y, int n, int h, int w, int c_out,
-                                    float alpha, float gain, float clamp, void* stream) {
-    return nb_up2_h3_impl(x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, y, nullptr, nullptr, 0, 0, n, h, w, c_out,
-                          alpha, gain, clamp, stream);
-}
-
-extern "C" int nb_modconv3x3_up2_h3_ex(const void* x, int c_in, const void* wts, const float* dcoefs, const float* noise,
-                                      int64_t noise_stride_n, const float* bias, float* y_f32, void* y_h2,
-                                      const float* next_styles, int next_stride, int c_next, int in_fmt, int out_fmt, int n,
-                                      int h, int w, int c_out, float alpha, float gain, float clamp, void* stream) {
-    return nb_up2_h3_impl(x, c_in, wts, dcoefs, noise, noise_stride_n, bias, y_f32, y_h2, next_styles, next_stride, c_next,
-                          n, h, w, c_out, alpha, gain, clamp, stream, in_fmt, out_fmt);
-}
-
-extern "C" int nb_modconv3x3_up2_h3_h2(const void* x_h2, int c_in, const void* w_h3, const float* dcoefs, const float* noise,
-                                       int64_t noise_stride_n, const float* bias, const float* next_styles, int next_stride,
-                                       void* y_h2, int c_next, int n, int h, int w, int c_out, float alpha, float gain,
-                                       float clamp, void* stream) {
-    return nb_up2_h3_impl(x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, nullptr, y_h2, next_styles, next_stride,
-                          c_next, n, h, w, c_out, alpha, gain, clamp, stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp32 NCHW -> H2 packing (optionally x two concatenated inputs, x per-(n,c) scale = the consumer's styles)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pack_h2_kernel(const float* __restrict__ x1, int c1, const float* __restrict__ x2, int c2,
-                                                      const float* __restrict__ scale, _Float16* __restrict__ out, int c8, int hw) {
-    const int n = blockIdx.z, cg = blockIdx.y;
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= hw) return;
-    const int c_in = c1 + c2;
-    h8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ch = cg * 8 + j;
-        float v = 0.f;
-        if (ch < c_in) {
-            v = ch < c1 ? x1[((size_t)n * c1 + ch) * hw + pix] : x2[((size_t)n * c2 + (ch - c1)) * hw + pix];
-            if (scale) v *= scale[(size_t)n * c_in + ch];
-        }
-        const _Float16 hh = (_Float16)v;
-        hi[j] = hh;
-        lo[j] = (_Float16)(v - (float)hh);
-    }
-    h8* o = reinterpret_cast<h8*>(out) + ((size_t)(n * c8 + cg) * 2) * hw + pix;
-    o[0] = hi;
-    o[hw] = lo;
-}
-
-extern "C" int nb_pack_h2_f32(const float* x1, int c1, const float* x2, int c2, const float* scale, void* out_h2, int n,
-                              int hw, void* stream) {
-    NB_REQUIRE(x1 && out_h2 && c1 > 0 && c2 >= 0 && (c2 == 0 || x2) && n > 0 && n <= 65535 && hw > 0, "pack_h2: bad arguments");
-    const int c8 = (c1 + c2 + 7) / 8;
-    dim3 grid((hw + 255) / 256, c8, n);
-    hipLaunchKernelGGL(pack_h2_kernel, grid, dim3(256), 0, (hipStream_t)stream, x1, c1, x2, c2, scale, (_Float16*)out_h2, c8, hw);
-    NB_CHECK_LAUNCH("pack_h2");
-    return NB_OK;
-}
-
-// fp32 NCHW (x1 ++ x2) * scale -> the "f8" activation format (see modconv3x3_up1_h3_kernel): per 16-channel chunk the
-// f16 high halves of both channel groups, fp8(xl * 2^9) and fp8(x / 4)
-__global__ __launch_bounds__(256) void pack_h2f8_kernel(const float* __restrict__ x1, int c1, const float* __restrict__ x2, int c2,
-                                                        const float* __restrict__ scale, _Float16* __restrict__ out, int c8, int hw) {
-    const int n = blockIdx.z, chunk = blockIdx.y;
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= hw) return;
-    const int c_in = c1 + c2;
-    float v[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int ch = chunk * 16 + j;
-        float t = 0.f;
-        if (ch < c_in) {
-            t = ch < c1 ? x1[((size_t)n * c1 + ch) * hw + pix] : x2[((size_t)n * c2 + (ch - c1)) * hw + pix];
-            if (scale) t *= scale[(size_t)n * c_in + ch];
-        }
-        v[j] = t;
-    }
-    h8 hi0, hi1;
-    float xl[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const _Float16 hh = (_Float16)v[j];
-        if (j < 8) hi0[j & 7] = hh; else hi1[j & 7] = hh;
-        xl[j] = (v[j] - (float)hh) * 512.f;
-    }
-    i32x4 l8, h8v;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        l8[q] = (int)nb_pk4_fp8(xl[4 * q], xl[4 * q + 1], xl[4 * q + 2], xl[4 * q + 3]);
-        h8v[q] = (int)nb_pk4_fp8(v[4 * q] * 0.25f, v[4 * q + 1] * 0.25f, v[4 * q + 2] * 0.25f, v[4 * q + 3] * 0.25f);
-    }
-    h8* o = reinterpret_cast<h8*>(out) + ((size_t)(n * c8 + 2 * chunk) * 2) * hw + pix;
-    o[0] = hi0;
-    o[hw] = __builtin_bit_cast(h8, l8);
-    o[2 * (size_t)hw] = hi1;
-    o[3 * (size_t)hw] = __builtin_bit_cast(h8, h8v);
-}
-
-extern "C" int nb_pack_h2f8_f32(const float* x1, int c1, const float* x2, int c2, const float* scale, void* out, int n, int hw,
-                                void* stream) {
-    NB_REQUIRE(x1 && out && c1 > 0 && c2 >= 0 && (c2 == 0 || x2) && n > 0 && n <= 65535 && hw > 0, "pack_h2f8: bad arguments");
-    NB_REQUIRE((c1 + c2) % 16 == 0, "pack_h2f8: the f8 operand format needs a multiple of 16 channels (got %d)", c1 + c2);
-    const int c8 = (c1 + c2) / 8;
-    dim3 grid((hw + 255) / 256, c8 / 2, n);
-    hipLaunchKernelGGL(pack_h2f8_kernel, grid, dim3(256), 0, (hipStream_t)stream, x1, c1, x2, c2, scale, (_Float16*)out, c8, hw);
-    NB_CHECK_LAUNCH("pack_h2f8");
-    return NB_OK;
-}
-
-// fp32 NCHW (x1 ++ x2) * scale -> the "f6" activation format (nb_h3_common.h): per 16-channel chunk the f16 high halves of both channel
-// groups and, in the two lo slots, 32 e2m3 fields (xl 2^11 / S, x / S interleaved) + the chunk's scale byte.  With cg0 / c8_total:
-// into channel groups cg0.. of a tensor with c8_total groups (the geometry features behind a producer that wrote its own groups).
-__global__ __launch_bounds__(256) void pack_h2f6_kernel(const float* __restrict__ x1, int c1, const float* __restrict__ x2, int c2,
-                                                        const float* __restrict__ scale, int scale_stride, _Float16* __restrict__ out,
-                                                        int c8_total, int cg0, int hw) {
-    const int n = blockIdx.z, chunk = blockIdx.y;
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= hw) return;
-    const int c_in = c1 + c2;
-    float v[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int ch = chunk * 16 + j;
-        float t = 0.f;
-        if (ch < c_in) {
-            t = ch < c1 ? x1[((size_t)n * c1 + ch) * hw + pix] : x2[((size_t)n * c2 + (ch - c1)) * hw + pix];
-            if (scale) t *= scale[(size_t)n * scale_stride + ch];
-        }
-        v[j] = t;
-    }
-    h8 hi0, hi1;
-    i32x4 l0, l1;
-    nb_f6_encode16(v, hi0, hi1, l0, l1);
-    h8* o = reinterpret_cast<h8*>(out) + ((size_t)(n * c8_total + cg0 + 2 * chunk) * 2) * hw + pix;
-    o[0] = hi0;
-    o[hw] = __builtin_bit_cast(h8, l0);
-    o[2 * (size_t)hw] = hi1;
-    o[3 * (size_t)hw] = __builtin_bit_cast(h8, l1);
-}
-
-extern "C" int nb_pack_h2f6_f32(const float* x1, int c1, const float* x2, int c2, const float* scale, void* out, int n, int hw,
-                                void* stream) {
-    NB_REQUIRE(x1 && out && c1 > 0 && c2 >= 0 && (c2 == 0 || x2) && n > 0 && n <= 65535 && hw > 0, "pack_h2f6: bad arguments");
-    NB_REQUIRE((c1 + c2) % 16 == 0, "pack_h2f6: the f6 operand format needs a multiple of 16 channels (got %d)", c1 + c2);
-    const int c8 = (c1 + c2) / 8;
-    dim3 grid((hw + 255) / 256, c8 / 2, n);
-    hipLaunchKernelGGL(pack_h2f6_kernel, grid, dim3(256), 0, (hipStream_t)stream, x1, c1, x2, c2, scale, c1 + c2, (_Float16*)out, c8, 0, hw);
-    NB_CHECK_LAUNCH("pack_h2f6");
-    return NB_OK;
-}
-
-extern "C" int nb_pack_h2f6_part_f32(const float* x, int c, const float* scale, int scale_stride, void* out, int c8_total,
-                                     int cg0, int n, int hw, void* stream) {
-    NB_REQUIRE(x && out && c > 0 && c % 16 == 0 && cg0 % 2 == 0 && n > 0 && n <= 65535 && hw > 0 && cg0 >= 0 && cg0 + c / 8 <= c8_total,
-               "pack_h2f6_part: bad arguments (whole 16-channel chunks only)");
-    dim3 grid((hw + 255) / 256, c / 16, n);
-    hipLaunchKernelGGL(pack_h2f6_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, c, (const float*)nullptr, 0, scale, scale_stride, (_Float16*)out,
-                       c8_total, cg0, hw);
-    NB_CHECK_LAUNCH("pack_h2f6_part");
-    return NB_OK;
-}
-
-// Pack c channels of an fp32 NCHW tensor into channel groups cg0.. of an H2 tensor with c8_total groups (the geometry
-// features that the consumer concatenates behind a producer that wrote its own groups directly)
-__global__ __launch_bounds__(256) void pack_h2_part_kernel(const float* __restrict__ x, int c, const float* __restrict__ scale,
-                                                           int scale_stride, _Float16* __restrict__ out, int c8_total, int cg0, int hw) {
-    const int n = blockIdx.z, cgl = blockIdx.y;
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= hw) return;
-    h8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ch = cgl * 8 + j;
-        float v = 0.f;
-        if (ch < c) {
-            v = x[((size_t)n * c + ch) * hw + pix];
-            if (scale) v *= scale[(size_t)n * scale_stride + ch];
-        }
-        const _Float16 hh = (_Float16)v;
-        hi[j] = hh;
-        lo[j] = (_Float16)(v - (float)hh);
-    }
-    h8* o = reinterpret_cast<h8*>(out) + ((size_t)(n * c8_total + cg0 + cgl) * 2) * hw + pix;
-    o[0] = hi;
-    o[hw] = lo;
-}
-
-__global__ __launch_bounds__(256) void pack_h2f8_part_kernel(const float* __restrict__ x, int c, const float* __restrict__ scale,
-                                                             int scale_stride, _Float16* __restrict__ out, int c8_total, int cg0, int hw) {
-    const int n = blockIdx.z, chunk = blockIdx.y;
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= hw) return;
-    float v[16], xl[16];
-    h8 hi0, hi1;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int ch = chunk * 16 + j;
-        float t = 0.f;
-        if (ch < c) {
-            t = x[((size_t)n * c + ch) * hw + pix];
-            if (scale) t *= scale[(size_t)n * scale_stride + ch];
-        }
-        const _Float16 hh = (_Float16)t;
-        if (j < 8) hi0[j & 7] = hh; else hi1[j & 7] = hh;
-        v[j] = t; xl[j] = (t - (float)hh) * 512.f;
-    }
-    i32x4 l8, h8v;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        l8[q] = (int)nb_pk4_fp8(xl[4 * q], xl[4 * q + 1], xl[4 * q + 2], xl[4 * q + 3]);
-        h8v[q] = (int)nb_pk4_fp8(v[4 * q] * 0.25f, v[4 * q + 1] * 0.25f, v[4 * q + 2] * 0.25f, v[4 * q + 3] * 0.25f);
-    }
-    h8* o = reinterpret_cast<h8*>(out) + ((size_t)(n * c8_total + cg0 + 2 * chunk) * 2) * hw + pix;
-    o[0] = hi0;
-    o[hw] = __builtin_bit_cast(h8, l8);
-    o[2 * (size_t)hw] = hi1;
-    o[3 * (size_t)hw] = __builtin_bit_cast(h8, h8v);
-}
-
-extern "C" int nb_pack_h2f8_part_f32(const float* x, int c, const float* scale, int scale_stride, void* out, int c8_total,
-                                     int cg0, int n, int hw, void* stream) {
-    NB_REQUIRE(x && out && c > 0 && c % 16 == 0 && cg0 % 2 == 0 && n > 0 && n <= 65535 && hw > 0 && cg0 >= 0 && cg0 + c / 8 <= c8_total,
-               "pack_h2f8_part: bad arguments (whole 16-channel chunks only)");
-    dim3 grid((hw + 255) / 256, c / 16, n);
-    hipLaunchKernelGGL(pack_h2f8_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, c, scale, scale_stride, (_Float16*)out, c8_total, cg0, hw);
-    NB_CHECK_LAUNCH("pack_h2f8_part");
-    return NB_OK;
-}
-
-extern "C" int nb_pack_h2_part_f32(const float* x, int c, const float* scale, int scale_stride, void* out_h2, int c8_total,
-                                   int cg0, int n, int hw, void* stream) {
-    NB_REQUIRE(x && out_h2 && c > 0 && n > 0 && n <= 65535 && hw > 0 && cg0 >= 0 && cg0 + (c + 7) / 8 <= c8_total, "pack_h2_part: bad arguments");
-    dim3 grid((hw + 255) / 256, (c + 7) / 8, n);
-    hipLaunchKernelGGL(pack_h2_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, c, scale, scale_stride, (_Float16*)out_h2, c8_total, cg0, hw);
-    NB_CHECK_LAUNCH("pack_h2_part");
-    return NB_OK;
-}
-
-// Device-side weight packing (same layout as the host helper below): one thread per (chunk, tap, cg, co) writes the hi and lo
-// slots of its 8 channels (zero padding included)
-// tf != 0: w is the weight of the convolution whose INPUT gradient is being computed, [c_in][c_out][3][3] in this call's terms; the
-// packed weight is its transpose with the taps reversed (the transposed convolution's kernel) -- no flipped copy in between.
-__global__ __launch_bounds__(256) void pack_conv_weight_h3_kernel(const float* __restrict__ w, int c_out, int c_in, int co_ld, int nch,
-                                                                  h8* __restrict__ out, int tf) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;             // ((chunk * 9 + tap) * 2 + cg) * co_ld + co
-    if (idx >= nch * 18 * co_ld) return;
-    const int co = idx % co_ld;
-    int r = idx / co_ld;
-    const int cg = r & 1; r >>= 1;
-    const int tap = r % 9, ch = r / 9;
-    h8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ci = ch * 16 + cg * 8 + j;
-        const float v = (co < c_out && ci < c_in) ? (tf ? w[((size_t)ci * c_out + co) * 9 + 8 - tap] : w[((size_t)co * c_in + ci) * 9 + tap]) : 0.f;
-        const _Float16 hh = (_Float16)v;
-        hi[j] = hh;
-        lo[j] = (_Float16)(v - (float)hh);
-    }
-    const size_t base = ((((size_t)ch * 9 + tap) * 2 + cg) * 2) * co_ld;
-    out[base + co] = hi;
-    out[base + co_ld + co] = lo;
-}
-
-extern "C" int nb_pack_conv_weight_h3_dev(const float* w, int c_out, int c_in, int co_align, int transpose_flip, void* out, void* stream) {
-    NB_REQUIRE(w && out && c_out > 0 && c_in > 0 && (uintptr_t)out % 16 == 0 && (co_align == 64 || co_align == 128), "pack_conv_weight_h3_dev: bad arguments");
-    const int nch = (c_in + 15) / 16, co_ld = (c_out + co_align - 1) / co_align * co_align;
-    const int total = nch * 18 * co_ld;
-    hipLaunchKernelGGL(pack_conv_weight_h3_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, c_out, c_in, co_ld, nch,
-                       (h8*)out, transpose_flip);
-    NB_CHECK_LAUNCH("pack_conv_weight_h3_dev");
-    return NB_OK;
-}
-
-// Host-side weight packing: W[c_out][c_in][3][3] fp32 -> hi/lo f16 [ceil16(c_in)/16][3][3][2][2][ceil64(c_out)][8]
-extern "C" int nb_pack_conv_weight_h3(const float* w, int c_out, int c_in, void* out) {
-    NB_REQUIRE(w && out && c_out > 0 && c_in > 0, "pack_conv_weight_h3: bad arguments");
-    const int nch = (c_in + 15) / 16, co_ld = (c_out + 63) / 64 * 64;
-    _Float16* o = (_Float16*)out;
-    const size_t total = (size_t)nch * 9 * 4 * co_ld * 8;
-    for (size_t i = 0; i < total; ++i) o[i] = (_Float16)0.f;
-    for (int co = 0; co < c_out; ++co)
-        for (int ci = 0; ci < c_in; ++ci)
-            for (int t = 0; t < 9; ++t) {
-                const float v = w[((size_t)co * c_in + ci) * 9 + t];
-                const _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                const int ch = ci / 16, cg = (ci % 16) / 8, j = ci % 8;
-                const size_t base = ((((size_t)ch * 9 + t) * 2 + cg) * 2) * co_ld;
-                o[(base + co) * 8 + j] = hi;
-                o[(base + co_ld + co) * 8 + j] = lo;
-            }
-    return NB_OK;
+    return nb_up1_h3_impl({x_h2, c_in, w_h3, dcoefs, noise, noise_stride_n, bias, nullptr, y_h2, next_styles, next_stride, c_next, n, h, w, c_out, alpha, gain, clamp, 0}, stream);
 }

@@ -2,7 +2,7 @@
 //
 // Same math, same tile (12 x 32 quads x 32 c_out, two position blocks and all four output phases per wave = 128 accumulator
 // registers, two waves per SIMD), same three-stage LDS ring and the same phase slots, stores and per-output arithmetic
-// (nb_up2_hrow / nb_up2_vout, nb_h3_common.h) as modconv3x3_up2_h3_kernel (nb_modconv_h3.hip): bit-identical results.  Its epilogue
+// (nb_up2_hrow / nb_up2_vout, nb_h3_common.h) as modconv3x3_up2_h3_kernel (nb_modconv_up2_h3.hip): bit-identical results.  Its epilogue
 // items are column runs of quads that share the horizontally filtered rows (round 8).  What differs besides is the K loop, which is the
 // one measured on the one-wave-per-SIMD kernel of round 4 (nb_modconv_up2w.hip, removed in round 6 -- docs/perf_history.md: 97 % of its cycles were matrix work):
 //   * one basic block per chunk: LDS-DMA pieces are issued from statements that set their lane mask themselves (an `if` around a
@@ -14,7 +14,7 @@
 //     instead of in bursts between the groups, a scheduling fence after every statement: program order is issue order;
 //   * the two 16-byte halves of a block-scaled fp8 operand are read straight into one 8-register tuple (no v_mov assembling).
 // Round 7: 13-row tiles as well (Up2vTile below: 16 full position blocks, two per wave), chosen per launch shape (nb_up2v_rows).
-#include "nb_h3_common.h"
+#include "nb_h3_launch.h"
 
 #ifdef NB_ABL6_NOMFMA
 #define NB_ABL6_F16 false
@@ -910,23 +910,12 @@ __global__ __launch_bounds__(NT, 2) void modconv3x3_up2v_kernel(const H3Up2Param
     } while (0)
 }
 
-extern int g_persist_wgs_per_cu;
 #ifndef NB_UP2V_PERSIST_DEFAULT
 #define NB_UP2V_PERSIST_DEFAULT 1          // (one stream: persistent 0.664-0.668 ms per step, round 5's kernel 0.667-0.672, the loop-less instantiation 0.679-0.686; three streams: equal)
 #endif
 static int g_up2v_persist = -1;
 // developer / test hook: -1 / 1 = persistent workgroups (one per CU, next tile's first chunk prefetched under the epilogue), 0 = one workgroup per tile
 extern "C" void nb_debug_set_up2v_persistent(int mode) { g_up2v_persist = mode; }
-
-static long up2v_ncu() {
-    static long ncu = 0;
-    if (!ncu) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        ncu = v;
-    }
-    return ncu;
-}
 
 template <bool F8, int OUTM, bool F6 = false, bool HO = false, bool PERSIST = true, int TQH = 12>
 static int nb_up2v_launch1(const H3Up2Params& p, int n, void* stream) {
@@ -941,7 +930,7 @@ static int nb_up2v_launch1(const H3Up2Params& p, int n, void* stream) {
     // persistent workgroups: one per CU (fewer items than CUs: one each), each walking its items with the next tile's first chunk
     // prefetched under the current tile's epilogue; g_up2v_persist == 0 (test hook): one workgroup per item, as until round 5
     const int items = p.items;
-    const long want = up2v_ncu() * g_persist_wgs_per_cu;                  // (workgroups per CU: NB_PERSIST_WGS_PER_CU in nb_modconv_h3.hip)
+    const long want = (long)nb_num_cus() * g_persist_wgs_per_cu;                  // (workgroups per CU: NB_PERSIST_WGS_PER_CU in nb_modconv_up1_h3.hip)
     dim3 grid(PERSIST && items > want ? (unsigned)want : (unsigned)items);
     hipLaunchKernelGGL((modconv3x3_up2v_kernel<F8, OUTM, F6, HO, PERSIST, TQH>), grid, dim3(NT), lds, (hipStream_t)stream, p);
     NB_CHECK_LAUNCH("modconv3x3_up2v");
@@ -981,15 +970,15 @@ static int nb_up2v_rows(int nchunks, int n, int h, int w, int slices, long ncu) 
 
 // developer / test hook: the tile height nb_up2v_rows picks for a launch shape (c_in in 16-channel chunks)
 extern "C" int nb_debug_up2v_auto_rows(int c_in, int c_out, int n, int h, int w) {
-    return nb_up2v_rows((c_in + 15) / 16, n, h, w, (c_out + CO_WG - 1) / CO_WG, up2v_ncu());
+    return nb_up2v_rows((c_in + 15) / 16, n, h, w, (c_out + CO_WG - 1) / CO_WG, nb_num_cus());
 }
 
-// p as filled in by nb_up2_h3_impl (nb_modconv_h3.hip); tiles are set here.  auto_rows: choose the tile height (else 12 rows, as the
+// p as filled in by nb_up2_h3_impl (nb_modconv_up2_h3.hip); tiles are set here.  auto_rows: choose the tile height (else 12 rows, as the
 // test hook nb_debug_set_up2_v2(1) promises; nb_debug_set_up2v_rows overrides both)
 int nb_up2v_launch(H3Up2Params p, int n, int in_fmt, void* stream, unsigned long long* tstamps, int tstamps_cap, bool auto_rows) {
     NB_REQUIRE(nb_up2v_eligible(in_fmt, p.nchunks * 16, p.h, p.w) && p.co_ld % CO_WG == 0, "modconv3x3_up2v: shape not supported");
     p.slices = (p.c_out + CO_WG - 1) / CO_WG;
-    const int rows = g_up2v_rows == 12 || g_up2v_rows == 13 ? g_up2v_rows : auto_rows ? nb_up2v_rows(p.nchunks, n, p.h, p.w, p.slices, up2v_ncu()) : 12;
+    const int rows = g_up2v_rows == 12 || g_up2v_rows == 13 ? g_up2v_rows : auto_rows ? nb_up2v_rows(p.nchunks, n, p.h, p.w, p.slices, nb_num_cus()) : 12;
     p.tiles_x = p.w / TQW;
     p.tiles_y = (p.h + rows - 1) / rows;
     p.items_x = p.tiles_x * p.tiles_y * p.slices;

@@ -1,5 +1,5 @@
 // Triad ToRGB epilogue shared by the standalone kernel (nb_ops.hip) and the fused conv1+ToRGB kernel
-// (nb_modconv_h3.hip).  Reference: ToRGBColorTriadLayer.forward, training/networks.py:451-485; the RGBA compositing of
+// (nb_modconv_up1_h3.hip).  Reference: ToRGBColorTriadLayer.forward, training/networks.py:451-485; the RGBA compositing of
 // TriadGanPaintEngine._render_stroke_torch, forger/ui/brush.py:763-792; StyleUVSMapper._map_style_s, mapper.py:52-72.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -80,7 +80,7 @@ def pack_enc_weight_h3(w: np.ndarray) -> np.ndarray:
 def pack_enc_weight_f8(w: np.ndarray) -> np.ndarray:
     """[O,I,3,3] fp32 (I % 16 == 0) -> the "f8" weight operands in the same containers as :func:`pack_enc_weight_h3`: hi slots
     = f16(w) of 8 channels; lo slot of chunk group 0 = fp8 e4m3(w), of group 1 = fp8((w - f16(w)) * 2^11), each over the 16
-    channels of the chunk (the weight side of nb_modconv_h3.hip's f8 arithmetic)."""
+    channels of the chunk (the weight side of nb_modconv_up1_h3.hip's f8 arithmetic)."""
     o, i = w.shape[:2]
     assert i % 16 == 0
     nch, co_ld = i // 16, -(-o // 128) * 128

@@ -882,7 +882,7 @@ def blend(features, alpha, x):
 
 
 # ----------------------------------------------------------------------------------------------
-# split-f16 ("h3") fast path (csrc/nb_modconv_h3.hip)
+# split-f16 ("h3") fast path (csrc/nb_modconv_up1_h3.hip, nb_modconv_up2_h3.hip, nb_pack_h2.hip)
 # ----------------------------------------------------------------------------------------------
 
 def pack_conv_weight_h3(weight: torch.Tensor) -> torch.Tensor:

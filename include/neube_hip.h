@@ -245,7 +245,7 @@ int nb_modconv3x3_f32(const float* x1, int c1, const float* x2, int c2, const fl
  * rocprofv3 reports), so that a benchmark can attribute its per-launch timings to kernels. */
 int nb_modconv3x3_variant(int n, int h, int w, int c_out, int up, char* buf, int buflen);
 
-/* ---- split-f16 ("h3") fast path for the large conv1 layers (csrc/nb_modconv_h3.hip) ----------------
+/* ---- split-f16 ("h3") fast path for the large conv1 layers (csrc/nb_modconv_up1_h3.hip, nb_modconv_up2_h3.hip, nb_pack_h2.hip) ----------------
  * Every fp32 operand is carried as hi + lo f16 halves and a product is three f16 MFMAs (xh*wh + xl*wh +
  * xh*wl, fp32 accumulate): fp32-grade results (5e-6 on pixels end to end) at ~5x the fp32-MFMA rate.
  * Activation format H2: _Float16 [n][ceil(c/8)][2 (hi,lo)][h][w][8], ALREADY multiplied by the consuming
@@ -307,7 +307,7 @@ int nb_blend_f32(const float* features, int nf, const float* alpha, int na, cons
                  int hw, void* stream);
 
 /* ---- "f8" operand format of the split-f16 convolutions: the two correction products on one block-scaled fp8 MFMA per
- * tap pair (csrc/nb_modconv_h3.hip).  Same containers as H2 / nb_pack_conv_weight_h3, but the (cg, lo) slots of a
+ * tap pair (csrc/nb_modconv_up1_h3.hip).  Same containers as H2 / nb_pack_conv_weight_h3, but the (cg, lo) slots of a
  * 16-channel chunk hold fp8 e4m3 values: activations (cg 2k, lo) = fp8(xl*2^9), (cg 2k+1, lo) = fp8(x/4); weights
  * (cg 0, lo) = fp8(w), (cg 1, lo) = fp8((w - f16(w))*2^11).  c_in % 16 == 0.  End-to-end pixel error ~1e-4 (H2: 5e-6). */
 int nb_pack_h2f8_f32(const float* x1, int c1, const float* x2, int c2, const float* scale, void* out, int n, int hw,

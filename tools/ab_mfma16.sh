@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box alternating A/B of the NB_MOCK16 timing build (every 32x32 MFMA of the f8 K loops of the up=1 ping-pong kernel and of up2v
 # replaced by two 16x16 MFMAs of half the MACs: same operands, same matrix cycles, WRONG results) against the regular library:
-#   tools/build_variant.sh mock16 nb_modconv_h3.hip,nb_modconv_up2v.hip "-DNB_MOCK16"
+#   tools/build_variant.sh mock16 nb_modconv_up1_h3.hip,nb_modconv_up2v.hip "-DNB_MOCK16"
 #   gpurun -- 'bash tools/ab_mfma16.sh > gpurun_out/r06_ab_mfma16.txt 2>&1'
 # Per pair: launch times of the four large layers (40-launch loops, best of 5), the K-loop cycles and the in-loop clock from the phase
 # stamps (s_memtime ticks per us), and the whole step on one stream (patches/s, board power).

@@ -1,5 +1,6 @@
 # Same-box A/B of library variants (csrc/libneube_<name>.so through NEUBE_LIB_PATH; "shipped" = the regular library), optionally with NB_DEBUG bits:
-#   tools/build_variant_at.sh wrap e618c53 nb_modconv_h3.hip; tools/build_variant_at.sh early e618c53 nb_modconv_up2v.hip,nb_common.h
+#   tools/build_variant_at.sh wrap e618c53 nb_modconv_h3.hip;      (that commit's name for today's nb_modconv_up1_h3.hip + nb_modconv_up2_h3.hip + nb_pack_h2.hip)
+#   tools/build_variant_at.sh early e618c53 nb_modconv_up2v.hip,nb_common.h
 #   gpurun -- 'bash tools/ab_variants.sh "shipped wrap early"'
 # (profiles/r06_ab_variants.txt: "midround" = the kernels shipped now, "shipped" there = wrap + early fetch, ":128" / ":512" their in-build switches)
 R=$(cd $(dirname $0)/.. && pwd); cd $R

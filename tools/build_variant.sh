@@ -2,7 +2,7 @@
 # Developer A/B build from the WORKING TREE: csrc/libneube_<name>.so = the current library with ONE OR MORE source files (comma list)
 # recompiled with extra -D flags (the other objects are the cached ones of the regular build).  Select with NEUBE_LIB_PATH.
 #   python -m brushstroke_engine_amd.build && tools/build_variant.sh actnt nb_modconv_up2v.hip "-DNB_UP2V_ACT_NT=1"
-#   tools/build_variant.sh mock16 nb_modconv_h3.hip,nb_modconv_up2v.hip "-DNB_MOCK16"
+#   tools/build_variant.sh mock16 nb_modconv_up1_h3.hip,nb_modconv_up2v.hip "-DNB_MOCK16"
 set -e
 name=$1; srcs=$2; defs=$3
 root=$(git rev-parse --show-toplevel); cs=$root/brushstroke_engine_amd/csrc

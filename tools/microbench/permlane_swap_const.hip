@@ -1,7 +1,7 @@
 // Reproducer: __builtin_amdgcn_permlane32_swap with hipcc (ROCm 7.2, -O3, gfx950).  When the two results are used in one
 // expression (r[0] + r[1]), or one operand is a constant, the generated code reads the FIRST result for both
 // (v_permlane32_swap v4, v2; v_add_f32 v2, v4, v4): lane 1 prints 2 instead of 1 + 33.  The kernels use inline assembly
-// with two read-write registers instead (nb_swap32, nb_modconv_h3.hip).
+// with two read-write registers instead (nb_swap32, nb_h3_common.h).
 //   hipcc -O3 --offload-arch=gfx950 permlane_swap_const.hip -o permlane_swap_const && ./permlane_swap_const
 #include <hip/hip_runtime.h>
 #include <cstdio>

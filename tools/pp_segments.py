@@ -1,5 +1,5 @@
 """Ping-pong K loop of the up=1 f8 kernel: cycles wave 0 spends in its load segments, compute segments and at the two barriers
-(variant build -DNB_PP_STAMPS=1 -DNB_UP1_PP_DEFAULT=1; tools/build_variant.sh ppst nb_modconv_h3.hip "...")."""
+(variant build -DNB_PP_STAMPS=1 -DNB_UP1_PP_DEFAULT=1; tools/build_variant.sh ppst nb_modconv_up1_h3.hip "...")."""
 import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
