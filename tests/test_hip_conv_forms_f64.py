@@ -35,7 +35,7 @@ pytestmark = pytest.mark.gpu
 
 # hook -> the value that restores the library's own choice
 HOOKS = {"up1_rows": 0, "up1_v2": -1, "up1_pp": -1, "up1_persistent": -1, "up1_small": -1, "persistent_wgs_per_cu": 0,
-         "up2_tile": 0, "up2_pair": -1, "up2_v2": -1, "small_waves": 0, "small_blocks": 0}
+         "up2_tile": 0, "up2_pair": -1, "up2_v2": -1, "up2v_rows": 0, "up2v_persistent": -1, "small_waves": 0, "small_blocks": 0}
 
 
 def _lib():
@@ -115,11 +115,12 @@ def _check_f32(what, y, r, tol):
     return worst
 
 
-def _check_handoff(what, out, d, r, fmt, co, c_next):
-    """Decoded hand-off operand against float64 ref x next style; untouched channel groups stay zero; guards stay NaN."""
+def _check_handoff(what, out, d, r, fmt, co, c_next, tol=None):
+    """Decoded hand-off operand against float64 ref x next style; untouched channel groups stay zero; guards stay NaN.
+    fmt = the container (0 H2, 1 f8); tol: the bound where the operands' format is not the container's (cf.tol_handoff_x)."""
     from brushstroke_engine_amd import ops
     want = cf.handoff_want(d, r["ref"], co)
-    tol = cf.tol_handoff(fmt, r["scale"], d, want, co)
+    tol = cf.tol_handoff(fmt, r["scale"], d, want, co) if tol is None else tol
     body = out.t[:, :co // 8].contiguous()
     if fmt:
         v, v4 = _decode_f8(body, co)
