@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _lock = threading.Lock()
 _lib = None
@@ -141,7 +141,13 @@ PROTOTYPES = {
     # staged passes (the generator split around the feature-canvas blend) and the canvas helpers of a C host
     "nb_generator_forward_staged": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
     "nb_generator_describe_staged": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
-    "nb_dirty_area_alpha_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
+    # brush noise sets: a projected brush's noise_const replacements and their transposes (csrc/nb_brush_noise.hip)
+    "nb_brush_noise_build_f32": (C.c_int, [vp, C.c_int, C.c_float, C.c_float, vp]),
+    "nb_brush_noise_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "nb_brush_noise_load": (C.c_int, [vp, vp, vp, C.c_float, vp]),
+    "nb_generator_bind_brush_noise": (C.c_int, [vp, vp]),
+    "nb_brush_noise_destroy": (C.c_int, [vp]),
+    "nb_dirty_area_alpha_f32":(C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
     "nb_canvas_cells_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
     "nb_canvas_build_cells": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     # drawing preparation (csrc/nb_geomprep.hip): Otsu geometry into the padded buffer, tile picks, crop + on-white
@@ -168,6 +174,11 @@ class NbNoiseSrc(C.Structure):
 
 
 NB_NOISE_IN_KERNEL = -1
+
+
+class NbBrushNoiseLayer(C.Structure):
+    """``struct NbBrushNoiseLayer`` of include/neube_hip.h (one layer of nb_brush_noise_build_f32's host array)."""
+    _fields_ = [("a", vp), ("b", vp), ("dst", vp), ("dst_t", vp), ("res", C.c_int32), ("pad", C.c_int32)]
 
 
 class NbTorgbArgs(C.Structure):

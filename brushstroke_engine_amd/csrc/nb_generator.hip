@@ -386,7 +386,7 @@ int plan_pass(const GenCfg& g, const NbPlanOptions& o, int n, NbPassPlan* p) {
     // the in-kernel noise tiles normalise integer positions per tile; from batch 9 one launch normalises them for the batch
     p->positions_once = o.positions_once && o.noise_positions == NB_PLAN_POS_INT && n > 8;
     // from this layer on every layer runs on the large kernels, which compute their shifted noise in their prologue (not with
-    // per-call noise overrides: their transposes do not exist)
+    // per-call noise overrides: nobody has transposed those; a brush noise set keeps its transposes and is no override)
     p->inkernel_from = -1;
     if (o.noise_in_kernel && positional && !o.noise_overrides) {
         int k = nL;
@@ -530,6 +530,17 @@ struct GenLayerDev {
     float *styles = nullptr, *dcoefs = nullptr, *noise = nullptr;
 };
 
+struct NbGenerator;
+
+// A brush noise set (include/neube_hip.h): per layer noise_const and its transpose in one allocation, and the handle's layer tables
+// with noise_const pointing there
+struct NbBrushNoise {
+    NbGenerator* gen = nullptr;
+    float* buf = nullptr;                        // sum over the layers of 2 res^2 floats (each image padded to 256 bytes)
+    std::vector<float*> nc, nc_t;                // per layer: [res, res] and its transpose, inside buf
+    NbLayerDesc* tables = nullptr;               // as NbGenerator::tables
+};
+
 struct NbGenerator {
     GenCfg cfg;
     NbPlanOptions opts;              // nb_plan_options_default with the generator's conv_mode
@@ -543,6 +554,7 @@ struct NbGenerator {
     const float *trgb_w = nullptr, *trgb_b = nullptr, *trgb_cb = nullptr, *trgb_aw = nullptr, *trgb_ab = nullptr;
     float* trgb_styles = nullptr;
     float* const_rep = nullptr;
+    std::vector<NbLayerDesc> host_tables;      // host copy of `tables` (a brush noise set re-points its noise_const)
     NbLayerDesc* tables = nullptr;   // (layers + 1) tables: table k has noise_const cleared for the conv layers >= k (k = layers: full)
     float* ws_buf = nullptr;
     float* npos = nullptr;
@@ -566,7 +578,13 @@ struct NbGenerator {
         std::vector<void*> allocs;
     } enc;
 
-    const NbLayerDesc* table(int first) const { return tables + (size_t)first * (L.size() + 1); }
+    NbBrushNoise* brush = nullptr;   // the bound brush noise set (nb_generator_bind_brush_noise), or NULL
+    std::vector<NbBrushNoise*> sets; // every live set of this handle (a set that outlives the handle is told so: gen = NULL)
+
+    // bn: the set a constant-noise pass reads its noise_const from (NULL: the checkpoint's)
+    const NbLayerDesc* table(int first, const NbBrushNoise* bn = nullptr) const {
+        return (bn ? bn->tables : tables) + (size_t)first * (L.size() + 1);
+    }
     // the plan of a forward at batch n: constant noise shifted by integer positions, or none; a pass that stops after block
     // stop_res taps that block's fp32 output, one that resumes starts after block resume_res (0 = a whole pass)
     int plan(int n, bool positional, NbPassPlan* p, int stop_res = 0, int resume_res = 0) const {
@@ -612,6 +630,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     const float alpha = 0.2f, gain = g->act_gain;
     const bool cnoise = in->noise_mode == NB_NOISE_CONST, snoise = in->noise_mode == NB_NOISE_SEEDED;
     const int64_t* ipos = cnoise ? in->positions : nullptr;
+    const NbBrushNoise* bn = cnoise ? g->brush : nullptr;      // (the other noise modes ignore a bound set)
     const int stop_res = stage ? stage->stop_res : 0, resume_res = stage ? stage->resume_res : 0;
     const NbGeneratorOutputs no_outputs{};
     if (!out) out = &no_outputs;
@@ -646,7 +665,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
     // ---- styles and noise images (_launch_styles_and_noise) ----
     const int n_tab = nL + 1;
     if (plan.styles_noise) {
-        GEN_TRY(nb_styles_noise_f32(g->table(inkernel_from < 0 ? nL : inkernel_from), n_tab, ws, cfg.num_ws, w_dim, nullptr, ipos, R, n, st));
+        GEN_TRY(nb_styles_noise_f32(g->table(inkernel_from < 0 ? nL : inkernel_from, bn), n_tab, ws, cfg.num_ws, w_dim, nullptr, ipos, R, n, st));
     } else {
         GEN_TRY((plan.styles_fast ? nb_styles_fast_f32 : nb_styles_f32)(g->table(nL), n_tab, ws, cfg.num_ws, w_dim, n, st));
         if (cnoise || snoise) {
@@ -665,7 +684,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
                     GEN_TRY(nb_noise_seeded_f32(g->table(nL) + lo, lo, hi - lo, max_res, in->noise_seed, in->noise_offset, in->noise_state,
                                                 n, st));
                 else
-                    GEN_TRY(nb_noise_f32(g->table(nL) + lo, hi - lo, max_res, npos_k, npos_k ? nullptr : ipos, R, n, st));
+                    GEN_TRY(nb_noise_f32(g->table(nL, bn) + lo, hi - lo, max_res, npos_k, npos_k ? nullptr : ipos, R, n, st));
             }
         }
     }
@@ -731,7 +750,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
         const float* noise = nullptr;
         int64_t nstride = 0;
         if (lp.noise_in_kernel) {
-            nsrc = NbNoiseSrc{d.noise_const_t, d.noise_lin, d.noise_strength, npos_k, npos_k ? nullptr : ipos, res, R};
+            nsrc = NbNoiseSrc{bn ? bn->nc_t[i] : d.noise_const_t, d.noise_lin, d.noise_strength, npos_k, npos_k ? nullptr : ipos, res, R};
             noise = (const float*)&nsrc;
             nstride = NB_NOISE_IN_KERNEL;
         } else if (cnoise || snoise) {
@@ -836,6 +855,7 @@ int gen_walk(NbGenerator* g, const NbGeneratorInputs* in, const NbGeneratorOutpu
 
 void gen_free(NbGenerator* g) {
     if (!g) return;
+    for (NbBrushNoise* s : g->sets) s->gen = nullptr;
     int prev = 0;
     const bool have = hipGetDevice(&prev) == hipSuccess;
     if ((!g->allocs.empty() || !g->enc.allocs.empty()) && hipSetDevice(g->device) == hipSuccess) {
@@ -985,7 +1005,8 @@ extern "C" int nb_generator_create(const NbGeneratorConfig* cfg, const void* con
     const int c_last = C.channels(C.R);
     g->trgb_styles = (float*)alloc((size_t)n_max * (c_last + 9) * sizeof(float));
     // layer tables (_Plan): the full one and, for the fused styles + noise launch of small batches, one per first in-kernel-noise layer
-    std::vector<NbLayerDesc> descs((size_t)(nL + 1) * (nL + 1));
+    std::vector<NbLayerDesc>& descs = g->host_tables;
+    descs.resize((size_t)(nL + 1) * (nL + 1));
     for (int first = 0; first <= nL; ++first) {
         NbLayerDesc* t = descs.data() + (size_t)first * (nL + 1);
         for (int i = 0; i < nL; ++i) {
@@ -1432,5 +1453,120 @@ extern "C" int nb_generator_describe_staged(NbGenerator* gen, int n, int stop_re
     }
     NB_REQUIRE(len > (int)s.size(), "%s: buffer of %d bytes, %d needed", who, len, (int)s.size() + 1);
     memcpy(buf, s.c_str(), s.size() + 1);
+    return NB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// brush noise sets: a projected brush's noise_const replacements and their transposes at fixed addresses (include/neube_hip.h)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+void brush_noise_free(NbBrushNoise* bn, int device) {
+    int prev = 0;
+    const bool have = hipGetDevice(&prev) == hipSuccess;
+    if ((bn->buf || bn->tables) && hipSetDevice(device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        if (bn->buf) (void)hipFree(bn->buf);
+        if (bn->tables) (void)hipFree(bn->tables);
+    }
+    if (have) (void)hipSetDevice(prev);
+    delete bn;
+}
+
+// one nb_brush_noise_build_f32 launch into the set; a NULL a[i] / b[i] is the checkpoint's buffer, b == NULL a plain copy
+int brush_noise_fill(NbBrushNoise* bn, const float* const* a, const float* const* b, float wa, float wb, void* stream) {
+    const NbGenerator* g = bn->gen;
+    const int nL = (int)g->L.size();
+    NbBrushNoiseLayer layers[NB_PLAN_MAX_LAYERS];
+    for (int i = 0; i < nL; ++i) {
+        const float* ck = g->L[i].noise_const;
+        layers[i] = NbBrushNoiseLayer{a && a[i] ? a[i] : ck, b ? (b[i] ? b[i] : ck) : nullptr, bn->nc[i], bn->nc_t[i],
+                                      g->cfg.layers[i].block_res, 0};
+    }
+    return nb_brush_noise_build_f32(layers, nL, wa, wb, stream);
+}
+
+}  // namespace
+
+extern "C" int nb_brush_noise_create(NbGenerator* gen, void* stream, NbBrushNoise** out) {
+    NB_REQUIRE(out, "brush_noise_create: null output handle");
+    *out = nullptr;
+    NB_REQUIRE(gen, "brush_noise_create: null generator");
+    int dev = -1;
+    NB_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev == gen->device, "brush_noise_create: current device %d is not the generator's (%d)", dev,
+               gen->device);
+    const int nL = (int)gen->L.size();
+    size_t floats = 0;
+    // (every image on a 256-byte boundary, as the checkpoint's own copies are)
+    auto padded = [](const GenLayer& s) { return ((size_t)s.block_res * s.block_res + 63) / 64 * 64; };
+    for (const GenLayer& s : gen->cfg.layers) floats += 2 * padded(s);
+    NbBrushNoise* bn = new NbBrushNoise();
+    bn->gen = gen;
+    const size_t table_bytes = gen->host_tables.size() * sizeof(NbLayerDesc);
+    if (hipMalloc((void**)&bn->buf, floats * sizeof(float)) != hipSuccess || hipMalloc((void**)&bn->tables, table_bytes) != hipSuccess) {
+        nb_set_error("brush_noise_create: hipMalloc of %zu bytes failed", floats * sizeof(float) + table_bytes);
+        brush_noise_free(bn, gen->device);
+        return NB_ELAUNCH;
+    }
+    float* p = bn->buf;
+    for (const GenLayer& s : gen->cfg.layers) {
+        bn->nc.push_back(p);
+        bn->nc_t.push_back(p + padded(s));
+        p += 2 * padded(s);
+    }
+    // the handle's tables with noise_const pointing into the set (where a table has it cleared it stays cleared)
+    std::vector<NbLayerDesc> descs = gen->host_tables;
+    for (int first = 0; first <= nL; ++first)
+        for (int i = 0; i < nL; ++i) {
+            NbLayerDesc& d = descs[(size_t)first * (nL + 1) + i];
+            if (d.noise_const) d.noise_const = bn->nc[i];
+        }
+    int rc = brush_noise_fill(bn, nullptr, nullptr, 1.f, 0.f, stream);
+    if (rc == NB_OK && (hipMemcpyAsync(bn->tables, descs.data(), table_bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess ||
+                        hipStreamSynchronize((hipStream_t)stream) != hipSuccess)) {
+        nb_set_error("brush_noise_create: %s", hipGetErrorString(hipGetLastError()));
+        rc = NB_ELAUNCH;
+    }
+    if (rc != NB_OK) {
+        brush_noise_free(bn, gen->device);
+        return rc;
+    }
+    gen->sets.push_back(bn);
+    *out = bn;
+    return NB_OK;
+}
+
+extern "C" int nb_brush_noise_load(NbBrushNoise* bn, const float* const* a_dev, const float* const* b_dev, float alpha, void* stream) {
+    NB_REQUIRE(bn, "brush_noise_load: null set");
+    NB_REQUIRE(bn->gen, "brush_noise_load: the set's generator has been destroyed");
+    NB_REQUIRE(a_dev, "brush_noise_load: null buffer array (a NULL entry stands for the checkpoint's buffer, the array itself may not be NULL)");
+    int dev = -1;
+    NB_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev == bn->gen->device, "brush_noise_load: current device %d is not the generator's (%d)",
+               dev, bn->gen->device);
+    return brush_noise_fill(bn, a_dev, b_dev, alpha, (float)(1.0 - (double)alpha), stream);
+}
+
+extern "C" int nb_generator_bind_brush_noise(NbGenerator* gen, NbBrushNoise* bn) {
+    NB_REQUIRE(gen, "generator_bind_brush_noise: null generator");
+    NB_REQUIRE(!bn || bn->gen == gen, "generator_bind_brush_noise: the set belongs to another generator");
+    gen->brush = bn;
+    return NB_OK;
+}
+
+extern "C" int nb_brush_noise_destroy(NbBrushNoise* bn) {
+    if (!bn) return NB_OK;
+    int device = 0;
+    if (NbGenerator* g = bn->gen) {
+        device = g->device;
+        if (g->brush == bn) g->brush = nullptr;
+        for (size_t k = 0; k < g->sets.size(); ++k)
+            if (g->sets[k] == bn) {
+                g->sets.erase(g->sets.begin() + k);
+                break;
+            }
+    } else {
+        (void)hipGetDevice(&device);              // (an orphan: its generator went first, on the device that was current then)
+    }
+    brush_noise_free(bn, device);
     return NB_OK;
 }

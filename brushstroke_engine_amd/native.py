@@ -161,6 +161,15 @@ class NativeGenerator:
             _lib.check(_lib.lib().nb_generator_attach_encoder(self._h, ptrs, _lib.NB_GEOM_PREPROC[preproc_type], stream),
                        "generator_attach_encoder")
 
+    # ---- brush noise sets (a projected brush's noise buffers; include/neube_hip.h) ----
+    def brush_noise(self) -> "NativeBrushNoise":
+        """A new set of this handle (nb_brush_noise_create), holding the checkpoint's noise until its ``load``."""
+        return NativeBrushNoise(self)
+
+    def bind_brush_noise(self, bn: Optional["NativeBrushNoise"]) -> None:
+        """Every later constant-noise forward of the handle reads ``bn`` (None: the checkpoint's noise again).  Host state only."""
+        _lib.check(_lib.lib().nb_generator_bind_brush_noise(self._h, None if bn is None else bn._h), "generator_bind_brush_noise")
+
     # ---- forward ----
     def _f32(self, t, shape, name):
         t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
@@ -314,3 +323,49 @@ def pack_weights_dev(weight: torch.Tensor, kind: str, resample_filter: Optional[
             _lib.check(lib.nb_pack_conv_weight_h3_up2_dev(_p(w), _p(f), o, i, _p(out), stream), "pack_conv_weight_h3_up2_dev")
             return out
     raise ValueError(f"unknown kind {kind!r}")
+
+
+class NativeBrushNoise:
+    """One ``NbBrushNoise`` handle (``NativeGenerator.brush_noise()``): a projected brush's noise buffers on the device, for the C
+    generator.  ``load`` takes the reference's ``noise_buffers`` dicts like ``networks.BrushNoise.load``; close it before its
+    generator."""
+
+    def __init__(self, gen: NativeGenerator):
+        self.gen = gen
+        h = ctypes.c_void_p()
+        with torch.cuda.device(gen.device):
+            _lib.check(_lib.lib().nb_brush_noise_create(gen._h, torch.cuda.current_stream(gen.device).cuda_stream, ctypes.byref(h)),
+                       "brush_noise_create")
+        self._h = h.value
+
+    def _pointers(self, buffers, keep):
+        ptrs = (ctypes.c_void_p * len(self.gen.cfg.layers))()
+        for i, s in enumerate(self.gen.cfg.layers):
+            buf = None if not buffers else buffers.get(f"b{s.block_res}.conv{0 if s.up == 2 else 1}.noise_const")
+            if buf is not None:
+                buf = self.gen._f32(buf if torch.is_tensor(buf) else np.asarray(buf), [s.block_res, s.block_res], s.name + ".noise_const")
+                keep.append(buf)
+                ptrs[i] = buf.data_ptr()
+        return ptrs
+
+    def load(self, noise_buffers, other=None, alpha: float = 1.0) -> "NativeBrushNoise":
+        """nb_brush_noise_load on the current stream: missing keys / None values = the checkpoint's buffer; with ``other`` the set
+        becomes ``noise_buffers * alpha + other * (1 - alpha)`` (alpha as a C float)."""
+        keep = []
+        a = self._pointers(noise_buffers, keep)
+        b = None if other is None else self._pointers(other, keep)
+        with torch.cuda.device(self.gen.device):
+            _lib.check(_lib.lib().nb_brush_noise_load(self._h, a, b, alpha, torch.cuda.current_stream(self.gen.device).cuda_stream),
+                       "brush_noise_load")
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().nb_brush_noise_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                    # noqa: BLE001  (interpreter shutdown)
+            pass

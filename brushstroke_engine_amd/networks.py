@@ -242,6 +242,99 @@ class _Plan:
         return self._upload(descs), keep
 
 
+def _noise_key(s: LayerSpec) -> str:
+    """The reference's ``noise_buffers`` key of a layer (networks_modified.py:163-165)."""
+    return f"b{s.block_res}.conv{0 if s.up == 2 else 1}.noise_const"
+
+
+class BrushNoise:
+    """A projected brush's noise as a device object (``SynthesisNetwork.brush_noise()``): per layer the ``noise_const``
+    replacement and its transpose at device addresses that never change, written by one launch (``nb_brush_noise_build_f32``).
+
+    The reference's brush libraries store ``{'w': ws, 'noise': {...}}`` (forger/ui/library.py:146-202) and its engine renders such a
+    brush with ``noise_buffers=`` (forger/ui/brush.py:746-754).  ``noise_buffers=dict`` does the same here, with per-call noise
+    overrides in the plan (no in-kernel noise, no fused styles + noise launch) and a layer table built and uploaded per call.  A
+    pass with ``noise_set=`` runs the ordinary plan on this object's tables, which are cached per workspace, so after the first pass
+    at a batch size it uploads nothing -- and since the addresses are fixed, a captured graph renders whatever ``load`` wrote last.
+
+    A fresh set holds the checkpoint's noise: it renders exactly like no set.  It belongs to the network and to the weights it was
+    created under (a pass raises after ``load_state_dict`` / ``.to()`` / ``set_conv_mode``: make a new one)."""
+
+    def __init__(self, syn: "SynthesisNetwork"):
+        syn._ensure_packed()
+        self.syn, self.epoch = syn, syn.packed
+        self.device = syn.get_last_block().conv1.weight.device
+        if self.device.type != "cuda":
+            raise _lib.NeubeHipError("a brush noise set lives on the GPU: move the generator there first")
+        specs = syn.cfg.layers
+        # one allocation, every image on a 256-byte boundary (as the checkpoint's own tensors are)
+        step = lambda s: -(-s.block_res * s.block_res // 64) * 64      # noqa: E731
+        self.buf = torch.empty([sum(2 * step(s) for s in specs)], dtype=torch.float32, device=self.device)
+        self.noise_const, self.noise_const_t, o = [], [], 0
+        for s in specs:
+            px = s.block_res * s.block_res
+            self.noise_const.append(self.buf[o:o + px].view(s.block_res, s.block_res))
+            self.noise_const_t.append(self.buf[o + step(s):o + step(s) + px].view(s.block_res, s.block_res))
+            o += 2 * step(s)
+        self._tables = {}           # id(workspace) -> (workspace, {first: device table})
+        self.load(None)
+
+    def _sources(self, buffers, keep) -> list:
+        """Per layer the device pointer of ``buffers``' entry (None / a missing key / a None value: the checkpoint's buffer)."""
+        out = []
+        for s in self.syn.cfg.layers:
+            buf = None if not buffers else buffers.get(_noise_key(s))
+            if buf is None:
+                buf = self.syn.layer_module(s).noise_const
+            else:
+                if not torch.is_tensor(buf):
+                    buf = torch.from_numpy(np.asarray(buf))
+                buf = buf.to(device=self.device, dtype=torch.float32).contiguous()
+                _assert_shape(buf, [s.block_res, s.block_res])
+            keep.append(buf)
+            out.append(buf.data_ptr())
+        return out
+
+    def load(self, noise_buffers, other=None, alpha: float = 1.0) -> "BrushNoise":
+        """Write the set: ``noise_buffers`` (a dict under the reference's key names, ``b{res}.conv{0,1}.noise_const``; tensors or
+        arrays on any device; a missing key or a None value = the checkpoint's buffer), or with ``other`` the lerp
+        ``noise_buffers[k] * alpha + other[k] * (1 - alpha)`` in float32 exactly as numpy evaluates that expression on float32
+        arrays (``formats.WBrushLibrary.set_interpolated_style``).  One launch on the current stream, nothing else: capturable, and
+        ordered like any other kernel -- passes that read the set on OTHER streams are the caller's to order around it."""
+        if self.epoch is not self.syn.packed:
+            raise RuntimeError("this brush noise set was created before the generator's weights were reloaded or moved: make a new one")
+        keep = []
+        a = self._sources(noise_buffers, keep)
+        b = None if other is None else self._sources(other, keep)
+        layers = (_lib.NbBrushNoiseLayer * len(a))()
+        for i, s in enumerate(self.syn.cfg.layers):
+            L = layers[i]
+            L.a, L.b, L.res = a[i], None if b is None else b[i], s.block_res
+            L.dst, L.dst_t = self.noise_const[i].data_ptr(), self.noise_const_t[i].data_ptr()
+        wa, wb = (1.0, 0.0) if b is None else (float(np.float32(alpha)), float(np.float32(1 - alpha)))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_brush_noise_build_f32(layers, len(a), wa, wb, torch.cuda.current_stream(self.device).cuda_stream),
+                       "brush_noise_build")
+        return self            # (`keep`: the caching allocator reuses a freed block in stream order, behind the launch)
+
+    def table(self, plan: "_Plan", first: Optional[int] = None) -> torch.Tensor:
+        """The workspace's layer table with ``noise_const`` pointing into the set -- the full one, or
+        ``plan.table_without_noise_from(first)``'s.  Built and uploaded once per (workspace, first)."""
+        ent = self._tables.get(id(plan))
+        if ent is None or ent[0] is not plan:
+            live = {id(p) for p in self.syn._plans.values()}
+            self._tables = {k: v for k, v in self._tables.items() if k in live}      # workspaces that were replaced (growth)
+            ent = self._tables[id(plan)] = (plan, {})
+        t = ent[1].get(first)
+        if t is None:
+            descs = (_lib.NbLayerDesc * plan.n_layers)()
+            ctypes.memmove(descs, plan.host_descs, ctypes.sizeof(descs))
+            for i in range(plan.n_layers - 1):
+                descs[i].noise_const = 0 if first is not None and i >= first else self.noise_const[i].data_ptr()
+            t = ent[1][first] = plan._upload(descs)
+        return t
+
+
 class _KernelPlan:
     """A pass's kernel decisions (nb_synthesis_plan's NbPassPlan, include/neube_hip.h) as plain Python values."""
 
@@ -347,6 +440,7 @@ class _Pass:
     blended_features: dict
     noise_buffers: Optional[dict]
     table: torch.Tensor
+    noise_set: Optional["BrushNoise"] = None       # constant noise from a brush noise set (None: the checkpoint's, or noise_buffers)
     stream: int = 0
     npos: Optional[torch.Tensor] = None
     ipos: Optional[torch.Tensor] = None
@@ -499,16 +593,22 @@ class SynthesisNetwork(torch.nn.Module):
             ev[2].record()
             self.layer_events.append(ev)
 
+    def brush_noise(self) -> "BrushNoise":
+        """A new brush noise set of this network (holding the checkpoint's noise until its ``load``): what ``noise_set=`` takes."""
+        return BrushNoise(self)
+
     # -- forward --
     def forward(self, ws, geom_feature, pos_encoding=None, return_debug_data=False, return_features=None,
-                blended_features=None, noise_buffers=None, **block_kwargs):
+                blended_features=None, noise_buffers=None, noise_set=None, **block_kwargs):
         """``networks_modified.py:123-223``.  Public keywords as the reference; the underscore keywords are the private options of
-        this build's schedules (``_PassOptions``).  Three steps: ``_begin_pass`` (validation, workspace), ``_prepare`` (styles,
+        this build's schedules (``_PassOptions``); ``noise_set`` is a ``BrushNoise`` of this network: the brush's noise buffers as a
+        device object, read by the ordinary planned pass (``noise_buffers=dict`` is the reference's per-call form).
+        Three steps: ``_begin_pass`` (validation, workspace), ``_prepare`` (styles,
         noise images, geometry operands: everything a pass needs before its first layer), ``_run_layers``."""
         opts = _PassOptions.from_kwargs(block_kwargs)
         if pos_encoding is not None:
             raise RuntimeError("positional encodings are not part of the shipped configuration (SG/train.py:680)")
-        ps = self._begin_pass(ws, geom_feature, opts, return_debug_data, return_features, blended_features, noise_buffers)
+        ps = self._begin_pass(ws, geom_feature, opts, return_debug_data, return_features, blended_features, noise_buffers, noise_set)
         with torch.cuda.device(ps.device):
             ps.stream = ops._stream(ps.ws)
             self._prepare(ps)
@@ -517,7 +617,7 @@ class SynthesisNetwork(torch.nn.Module):
             return self._run_layers(ps)
 
     def _begin_pass(self, ws, geom_feature, opts: "_PassOptions", return_debug_data, return_features, blended_features,
-                    noise_buffers) -> "_Pass":
+                    noise_buffers, noise_set=None) -> "_Pass":
         """Validate the call (networks_modified.py:145), pick the workspace slot and collect the state of one pass."""
         _assert_shape(ws, [None, self.num_ws, self.w_dim])          # networks_modified.py:145
         device = self.get_last_block().conv1.weight.device
@@ -530,6 +630,15 @@ class SynthesisNetwork(torch.nn.Module):
         return_features = [] if return_features is None else return_features
         blended_features = {} if blended_features is None else blended_features
         const = opts.noise_mode == "const"
+        if not const:
+            noise_set = None                       # ignored under the other noise modes, as noise_buffers is
+        if noise_set is not None:
+            if noise_buffers:
+                raise RuntimeError("noise_set and noise_buffers: a pass takes its constant noise from one of the two")
+            if not isinstance(noise_set, BrushNoise) or noise_set.syn is not self:
+                raise RuntimeError("noise_set: not a brush noise set of this network (SynthesisNetwork.brush_noise())")
+            if noise_set.epoch is not self.packed:
+                raise RuntimeError("noise_set: created before the generator's weights were reloaded or moved: make a new one")
         kplan = self.pass_plan(
             n, noise_positions=(_lib.NB_PLAN_POS_NONE if not const else _lib.NB_PLAN_POS_INT if opts.positions is not None
                                 else _lib.NB_PLAN_POS_NORM if opts.norm_noise_positions is not None else _lib.NB_PLAN_POS_NONE),
@@ -546,7 +655,7 @@ class SynthesisNetwork(torch.nn.Module):
             geom_feature = list(geom_feature) if isinstance(geom_feature, (list, tuple)) else [geom_feature]
         return _Pass(opts=opts, ws=ws, n=n, device=device, plan=plan, kplan=kplan, lazy_geom=lazy_geom, geom_feature=geom_feature,
                      return_debug_data=return_debug_data, return_features=return_features, blended_features=blended_features,
-                     noise_buffers=noise_buffers, table=plan.table)
+                     noise_buffers=noise_buffers, table=plan.table, noise_set=noise_set)
 
     # ---- step 1: what a pass needs before its first layer ----
     def _prepare(self, ps: "_Pass") -> None:
@@ -565,7 +674,9 @@ class SynthesisNetwork(torch.nn.Module):
         """Per-call noise overrides and the patch positions in the form the kernels take them."""
         opts, plan, n, device = ps.opts, ps.plan, ps.n, ps.device
         if opts.noise_mode == "const":
-            if ps.noise_buffers:
+            if ps.noise_set is not None:
+                ps.table = ps.noise_set.table(plan)          # (cached per workspace: no upload after the first pass)
+            elif ps.noise_buffers:
                 ps.table, keep = plan.table_with_noise_overrides(self, ps.noise_buffers)
                 ps.keep_alive += [ps.table] + keep
             if opts.positions is not None:
@@ -600,14 +711,18 @@ class SynthesisNetwork(torch.nn.Module):
         if opts.reuse_styles:
             if noise_mode == "seeded":
                 raise RuntimeError("_reuse_styles: a seeded pass writes its own noise images")
-            if resume is None or (inkernel_from is None and noise_mode == "const") or table is not plan.table:
+            overridden = table is not plan.table and ps.noise_set is None      # (per-call noise_buffers; a set keeps its tables)
+            if resume is None or (inkernel_from is None and noise_mode == "const") or overridden:
                 raise RuntimeError("_reuse_styles needs a resumed pass whose layers compute their noise themselves")
             if any(i_ < inkernel_from for i_, sp in enumerate(cfg.layers) if sp.block_res > resume[0]) and noise_mode == "const":
                 raise RuntimeError("_reuse_styles: a resumed layer would need a noise image that no launch of this pass writes")
             return
         if ps.kplan.styles_noise:
             # small batches: styles + per-sample noise in one launch (a launch costs more than either computes)
-            tbl = plan.table if inkernel_from is None else plan.table_without_noise_from(inkernel_from)
+            if ps.noise_set is not None:
+                tbl = ps.noise_set.table(plan, inkernel_from)
+            else:
+                tbl = plan.table if inkernel_from is None else plan.table_without_noise_from(inkernel_from)
             _lib.check(lib.nb_styles_noise_f32(_p(tbl), plan.n_layers, _p(ps.ws), self.num_ws, self.w_dim, _p(npos),
                                                _p(ipos), self.img_resolution, n, stream), "styles_noise")
             return
@@ -761,7 +876,8 @@ class SynthesisNetwork(torch.nn.Module):
         lp = ps.kplan.layers[i]
         noise_ptr, nstride = None, 0
         if noise_mode == "const" and lp.noise_in_kernel:
-            nsrc = _lib.NbNoiseSrc(_p(pk["noise_const_t"]), _p(pk["noise_lin"]), _p(layer.noise_strength),
+            const_t = pk["noise_const_t"] if ps.noise_set is None else ps.noise_set.noise_const_t[i]
+            nsrc = _lib.NbNoiseSrc(_p(const_t), _p(pk["noise_lin"]), _p(layer.noise_strength),
                                    _p(ps.npos if ps.npos_k is None else ps.npos_k), _p(ps.ipos if ps.npos_k is None else None),
                                    s.block_res, self.img_resolution)
             ps.keep_alive.append(nsrc)
@@ -1082,7 +1198,10 @@ class Generator(torch.nn.Module):
 
     def forward_pre_mapped(self, ws, geom_feature, positions=None, return_debug_data=False, return_features=None,
                            blended_features=None, noise_buffers=None, noise_seed=None, noise_offset=0, noise_state=None,
-                           **synthesis_kwargs):
+                           noise_set=None, **synthesis_kwargs):
+        # noise_set: a BrushNoise of self.synthesis (the brush's noise buffers on the device; SynthesisNetwork.forward)
+        if noise_set is not None:
+            synthesis_kwargs["noise_set"] = noise_set
         # noise_mode="seeded" (this build's reproducible 'random'): sample k draws the noise of (noise_seed, noise_offset + k), or of
         # the two values in the int64[2] device tensor noise_state
         synthesis_kwargs.update(_seeded_kwargs(noise_seed, noise_offset, noise_state))
@@ -1177,14 +1296,14 @@ class Generator(torch.nn.Module):
 
     def forward(self, z, c, geom_feature, positions=None, noise_buffers=None, truncation_psi=1, truncation_cutoff=None,
                 return_debug_data=False, return_features=None, blended_features=None, style_mixing_prob=0,
-                noise_seed=None, noise_offset=0, noise_state=None, **synthesis_kwargs):
+                noise_seed=None, noise_offset=0, noise_state=None, noise_set=None, **synthesis_kwargs):
         ws = self.mapping(z, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
         if style_mixing_prob > 0:
             ws = mix_styles(self.mapping, ws, z, c, style_mixing_prob, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
         return self.forward_pre_mapped(ws, geom_feature, positions=positions, return_debug_data=return_debug_data,
                                        return_features=return_features, blended_features=blended_features,
                                        noise_buffers=noise_buffers, noise_seed=noise_seed, noise_offset=noise_offset,
-                                       noise_state=noise_state, **synthesis_kwargs)
+                                       noise_state=noise_state, noise_set=noise_set, **synthesis_kwargs)
 
     def render_triad(self, z=None, ws=None, geom_feature=None, positions=None, render_mode="clear", user_colors=None,
                      want_u8=True, want_f32=False, sfactor=None, join=True, noise_seed=None, noise_offset=0, noise_state=None, **kw):

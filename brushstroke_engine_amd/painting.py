@@ -295,30 +295,43 @@ class TileOps:
     # ``slot``: which of the generator's per-batch workspaces to use -- consecutive batches alternate between two HIP
     # streams (``stream``/``join_streams``), each with its own workspace, so that one batch's kernel tails and small
     # launches are covered by the other batch's work
-    def head(self, ws, geom_feats, positions, stop_res: int, slot: int = 0) -> torch.Tensor:
+    # ``noise_set``: the brush's noise buffers (``networks.BrushNoise``, ``brush_noise()`` below; None = the checkpoint's noise).  Its
+    # identity is part of a graph's key, its contents are not: the set's addresses are fixed, so a captured pass renders whatever the
+    # set holds when it is replayed.
+    def brush_noise(self):
+        return self.G.synthesis.brush_noise()
+
+    @staticmethod
+    def _set_key(noise_set):
+        return None if noise_set is None else id(noise_set)       # (the graph's closure keeps the set alive: the id stays its own)
+
+    def head(self, ws, geom_feats, positions, stop_res: int, slot: int = 0, noise_set=None) -> torch.Tensor:
         if self._use_graph(ws):
-            return self._graphed(("head", stop_res), [ws, geom_feats[0], geom_feats[1], positions],
-                                 lambda w, g0, g1, ps: self.head(w, [g0, g1], ps, stop_res, slot=self._GRAPH_SLOT))
+            return self._graphed(("head", stop_res, self._set_key(noise_set)), [ws, geom_feats[0], geom_feats[1], positions],
+                                 lambda w, g0, g1, ps: self.head(w, [g0, g1], ps, stop_res, slot=self._GRAPH_SLOT, noise_set=noise_set))
         return self.G.forward_pre_mapped(ws, geom_feats, positions=positions, noise_mode="const", _stop_after=stop_res,
-                                         _plan_slot=slot)
+                                         _plan_slot=slot, noise_set=noise_set)
 
     def tail(self, ws, feats, geom_feats, positions, resume_res: int, render_mode, user_colors, sfactor=None,
-             slot: int = 0) -> torch.Tensor:
+             slot: int = 0, noise_set=None) -> torch.Tensor:
         if self._use_graph(ws) and (sfactor is None or torch.is_tensor(sfactor)):
-            return self._graphed(("tail", resume_res, render_mode), [ws, feats, geom_feats[0], geom_feats[1], positions, user_colors, sfactor],
+            return self._graphed(("tail", resume_res, render_mode, self._set_key(noise_set)),
+                                 [ws, feats, geom_feats[0], geom_feats[1], positions, user_colors, sfactor],
                                  lambda w, f, g0, g1, ps, uc, sf: self.tail(w, f, [g0, g1], ps, resume_res, render_mode, uc, sf,
-                                                                           slot=self._GRAPH_SLOT + 1))
+                                                                           slot=self._GRAPH_SLOT + 1, noise_set=noise_set))
         u8, _, _ = self.G.render_triad(ws=ws, geom_feature=geom_feats, positions=positions, render_mode=render_mode,
-                                       user_colors=user_colors, sfactor=sfactor, _resume=(resume_res, feats), _plan_slot=slot)
+                                       user_colors=user_colors, sfactor=sfactor, _resume=(resume_res, feats), _plan_slot=slot,
+                                       noise_set=noise_set)
         return u8
 
-    def full(self, ws, geom_feats, positions, render_mode, user_colors, sfactor=None, slot: int = 0) -> torch.Tensor:
+    def full(self, ws, geom_feats, positions, render_mode, user_colors, sfactor=None, slot: int = 0, noise_set=None) -> torch.Tensor:
         if self._use_graph(ws) and (sfactor is None or torch.is_tensor(sfactor)):
-            return self._graphed(("full", render_mode), [ws, geom_feats[0], geom_feats[1], positions, user_colors, sfactor],
+            return self._graphed(("full", render_mode, self._set_key(noise_set)),
+                                 [ws, geom_feats[0], geom_feats[1], positions, user_colors, sfactor],
                                  lambda w, g0, g1, ps, uc, sf: self.full(w, [g0, g1], ps, render_mode, uc, sf,
-                                                                         slot=self._GRAPH_SLOT + 2))
+                                                                         slot=self._GRAPH_SLOT + 2, noise_set=noise_set))
         u8, _, _ = self.G.render_triad(ws=ws, geom_feature=geom_feats, positions=positions, render_mode=render_mode,
-                                       user_colors=user_colors, sfactor=sfactor, _plan_slot=slot)
+                                       user_colors=user_colors, sfactor=sfactor, _plan_slot=slot, noise_set=noise_set)
         return u8
 
     # -- hipGraph replay of the generator passes of ONE tile (interactive strokes) --
@@ -632,6 +645,27 @@ class PaintingHelper:
         self.halo_bytes = None
         self.down_factor = None
         self._alpha_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}
+        self._noise_set, self._noise_src = None, None       # the brush's noise buffers on the device, and the dict they came from
+
+    def _brush_noise(self, opts: "GanBrushOptions"):
+        """The noise set of a projected brush: ``opts.custom_args['noise_buffers']`` (what ``formats.WBrushLibrary`` hands to
+        ``set_style_w``; the reference renders with ``**opts.custom_args``, brush.py:746-754) as a ``networks.BrushNoise`` that every
+        generator pass of the schedule reads.  None -- the checkpoint's noise -- for a z brush, for no / None / empty buffers, and for
+        an ``ops`` without noise sets (the CPU stand-ins of the tests).  The helper keeps ONE set and reloads it (one launch on the
+        caller's stream, behind the previous call's joined batches) when the dict is another non-empty dict OBJECT than last time:
+        a dict changed in place is not seen -- hand ``set_style_w`` a new one.  Every rank of a process group builds its own set
+        from the same ``opts``; there is no collective in it."""
+        bufs = opts.custom_args.get("noise_buffers") if (opts.style_ws is not None and opts.custom_args) else None
+        if not bufs or not hasattr(self.ops, "brush_noise"):
+            return None
+        bn = self._noise_set
+        if bn is None or bn.epoch is not bn.syn.packed:       # first brush, or the weights were reloaded / moved since
+            bn, self._noise_src = self.ops.brush_noise(), None
+            self._noise_set = bn
+        if bufs is not self._noise_src:
+            bn.load(bufs)
+            self._noise_src = bufs
+        return bn
 
     # -- canvas state --
     def make_new_canvas(self, rows: int, cols: int, feature_blending: Optional[int] = None):
@@ -731,6 +765,9 @@ class PaintingHelper:
         geom_dev = geom_img.contiguous() if torch.is_tensor(geom_img) else ops.to_device(np.ascontiguousarray(geom_img))
         ws1 = ops.map_style(z=opts.style_z, ws=opts.style_ws)                  # one brush style for all tiles
         user = opts.user_colors()
+        # a projected brush's noise buffers (the UVS calibration below stays without them, as the reference's: mapper.py:84-87)
+        noise_set = self._brush_noise(opts)
+        nkw = {} if noise_set is None else {"noise_set": noise_set}
         sfac = None
         if opts.enable_uvs_mapping:                                            # brush.py:773-774
             if self.uvs_mapper is None:
@@ -770,7 +807,7 @@ class PaintingHelper:
                 with on_stream(k):
                     g = ops.geom_tiles(geom_dev, own_yx[b0:b1])
                     outs.append(ops.full(style(b1 - b0), ops.encode(g), pos(b0, b1), self.render_mode, colors(b1 - b0), sfac,
-                                         slot=plan_slot(k)))
+                                         slot=plan_slot(k), **nkw))
             join(outs)
         else:
             bres = R // df
@@ -821,7 +858,7 @@ class PaintingHelper:
                 with on_stream(k):
                     gf = ops.encode(ops.geom_tiles(geom_dev, own_yx[b0:b1]))
                     geom_feats_own[k] = gf
-                    mine[b0:b1] = ops.head(style(b1 - b0), gf, pos(b0, b1), bres, slot=plan_slot(k))
+                    mine[b0:b1] = ops.head(style(b1 - b0), gf, pos(b0, b1), bres, slot=plan_slot(k), **nkw)
                 if sharded and work is None and b0 <= first_send:
                     exchange()
             if sharded and work is None:
@@ -879,7 +916,7 @@ class PaintingHelper:
             for i, (b0, b1) in blist:
                 with on_stream(i):
                     outs.append(ops.tail(style(b1 - b0), mine[b0:b1], geom_feats_own[i], pos(b0, b1), bres,
-                                         self.render_mode, colors(b1 - b0), sfac, slot=plan_slot(i)))
+                                         self.render_mode, colors(b1 - b0), sfac, slot=plan_slot(i), **nkw))
             join(outs)
         rgba_own = torch.cat(outs) if outs else None
         if not sharded:

@@ -783,6 +783,51 @@ int nb_generator_forward_staged(NbGenerator* gen, const NbGeneratorInputs* in, c
  * records for them), and for a tail the ToRGB's line.  Host only. */
 int nb_generator_describe_staged(NbGenerator* gen, int n, int stop_res, int resume_res, char* buf, int len);
 
+/* ---- brush noise sets: a projected brush's noise buffers as a device object -----------------------------------------------------
+ * A projected brush is a W+ code AND a noise_const replacement for every synthesis layer, optimised together with it (the
+ * reference's brush libraries store {'w': ws, 'noise': {...}}, forger/ui/library.py:146-202; its engine renders with
+ * G.forward_pre_mapped(ws, ..., noise_buffers=...), forger/ui/brush.py:746-754; the buffers replace noise_const before the
+ * positional shift, networks.py:372-382).  A noise set holds, per layer, that replacement and its transpose at device addresses that
+ * never change, so the pass that reads it is the ordinary planned pass: in-kernel noise of the large kernels (which read the
+ * transpose, NbNoiseSrc) and the fused styles + noise launch of small batches included. */
+
+/* One launch that writes every layer of a set: dst = a (b == NULL) or a * wa + b * wb, and dst_t = dst transposed.  The lerp is two
+ * rounded fp32 products and one rounded fp32 sum, never an FMA: what `a * alpha + b * (1 - alpha)` gives on float32 arrays
+ * (formats.WBrushLibrary.set_interpolated_style); the caller rounds wa = (float)alpha and wb = (float)(1 - alpha) from double.
+ * layers_host is a HOST array of at most NB_PLAN_MAX_LAYERS entries, passed to the kernel by value; its pointers are device
+ * pointers to fp32 [res, res] images (4-byte alignment suffices), res a power of two >= 4.  dst may be a (a reload in place); dst_t
+ * must alias neither a nor b nor dst.  Enqueue only.  NULL layers_host, n_layers outside [1, NB_PLAN_MAX_LAYERS], a NULL a / dst /
+ * dst_t or a bad res: NB_EINVAL, nothing enqueued. */
+typedef struct NbBrushNoiseLayer {
+    const float* a;            /* [res, res] */
+    const float* b;            /* [res, res] or NULL */
+    float* dst;                /* [res, res] = a (b == NULL) | a * wa + b * wb */
+    float* dst_t;              /* [res, res] = dst transposed */
+    int32_t res, pad;
+} NbBrushNoiseLayer;
+int nb_brush_noise_build_f32(const NbBrushNoiseLayer* layers_host, int n_layers, float wa, float wb, void* stream);
+
+/* The set of a generator handle.
+ *   create   allocates the set (sum over the layers of 2 res^2 floats), fills it with the checkpoint's noise_const -- an unloaded set
+ *            renders exactly like no set --, uploads copies of every layer table the handle keeps with noise_const pointing into the
+ *            set, and synchronises `stream` (as nb_generator_create does).  The current device must be the generator's.
+ *   load     a_dev[i] / b_dev[i]: device fp32 [res_i, res_i] buffers in the order of nb_generator_layer_info; a NULL entry stands for
+ *            the checkpoint's buffer of that layer, b_dev itself may be NULL.  With b_dev the set becomes a * alpha + b * (1 - alpha)
+ *            (nb_brush_noise_build_f32 with wa = (float)alpha, wb = (float)(1 - (double)alpha)), else a.  One launch, enqueue only,
+ *            capturable; the buffers must stay valid until it has run.
+ *   bind     host state only: every later nb_generator_forward, _forward_geom and _forward_staged of the handle with NB_NOISE_CONST
+ *            reads noise_const from the set's tables and hands the set's transposes to the kernels that compute their noise
+ *            themselves.  The plan does not change (nb_generator_describe gives the same lines).  The other noise modes ignore the
+ *            binding.  bn = NULL: back to the checkpoint's noise.  A set of another generator: NB_EINVAL.
+ *   destroy  unbinds the set if it is bound, synchronises the device and frees it.  Destroy a generator's sets before the generator.
+ * Graphs: the set's addresses never change, so a graph captured while a set is bound renders whatever nb_brush_noise_load wrote
+ * last: switching brushes costs one launch (in stream order with the replays) and no recapture. */
+typedef struct NbBrushNoise NbBrushNoise;
+int nb_brush_noise_create(NbGenerator* gen, void* stream, NbBrushNoise** out);
+int nb_brush_noise_load(NbBrushNoise* bn, const float* const* a_dev, const float* const* b_dev, float alpha, void* stream);
+int nb_generator_bind_brush_noise(NbGenerator* gen, NbBrushNoise* bn);
+int nb_brush_noise_destroy(NbBrushNoise* bn);
+
 /* ---- the per-batch layer plan (host only: no HIP call, works without a GPU) ------------------------------------------------
  * Every kernel decision of one synthesis pass at batch n: which kernel each layer runs, its operand formats, the operand hand-off,
  * the fused ToRGB, in-kernel noise, the styles / noise launches and the early geometry packs.  The package's Python pass
