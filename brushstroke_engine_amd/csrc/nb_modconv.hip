@@ -413,7 +413,9 @@ __global__ __launch_bounds__(256) void modconv3x3_up2_kernel(const ModconvParams
     // small-tile variants (the latency-bound launches): the epilogue's operands - demodulation, bias, hand-off scale of
     // the 16 channels and the tile's noise - go to LDS now instead of being fetched in each of the 4 epilogue rounds
     constexpr bool PRE = NBP <= 3;
-    constexpr int NZ_MAX = !PRE ? 1 : NBP == 3 ? 512 : NBP == 2 ? 256 : 64;
+    // 4 x quads of the largest tile of the instantiation: 8 x 16 / 16 x 8 (NBP 3), 8 x 8 / 4 x 16 / 16 x 4 (NBP 2), and for NBP 1
+    // not only the square 4 x 4 but the 4 x 8 / 8 x 4 tiles of an image 4 high or wide ((4 + 2) x (8 + 2) = 60 positions)
+    constexpr int NZ_MAX = !PRE ? 1 : NBP == 3 ? 512 : NBP == 2 ? 256 : 128;
     __shared__ float s_pd[16], s_pb[16], s_psc[16], s_pnz[NZ_MAX];
     if constexpr (PRE) {
         if (tid < 16) {

@@ -1,8 +1,8 @@
-"""The split-f16 conv launchers and the operand packers refuse bad calls on the host, before any launch: one table of bad calls,
-each with the NB_EINVAL it must return and the text nb_last_error() must hold.  No GPU is needed -- no row gets as far as the
-zero page or a kernel.  The up=1 and up=2 families share their launcher set-up (csrc/nb_h3_launch.h) but not every rule or text;
-rows that break two rules at once pin the ORDER of the checks (the two families report a bad slope and a bad image size in
-opposite orders)."""
+"""The split-f16 conv launchers, the fp32 conv launchers (nb_modconv3x3_f32, nb_modconv3x3_up2_f32_h2, nb_modconv3x3_variant) and
+the operand packers refuse bad calls on the host, before any launch: one table of bad calls, each with the NB_EINVAL it must return
+and the text nb_last_error() must hold.  No GPU is needed -- no row gets as far as the zero page or a kernel.  The split-f16 up=1
+and up=2 families share their launcher set-up (csrc/nb_h3_launch.h) but not every rule or text; rows that break two rules at once
+pin the ORDER of the checks (the two families report a bad slope and a bad image size in opposite orders)."""
 import ctypes
 
 import pytest
@@ -129,6 +129,40 @@ def rows():
     good = dict(w=P, c_out=64, c_in=64, co_align=64, transpose_flip=0, out=P, stream=None)
     for kw in (dict(w=None), dict(out=None), dict(out=ODD), dict(c_out=0), dict(c_in=0), dict(co_align=32), dict(co_align=0)):
         add(("nb_pack_conv_weight_h3_dev", tuple(dict(good, **kw).values())), "pack_conv_weight_h3_dev: bad arguments")
+    # the fp32 kernels (csrc/nb_modconv.hip): every rule stands before the zero page and the launch.  (New rows go to the END of the
+    # table: a row's id carries its index.)
+    f32 = dict(x1=P, c1=32, x2=None, c2=0, wpk=P, styles=P, dcoefs=P, noise=None, nsn=0, bias=P, out_scale=P, y=P, n=2, h=16, w=16, c_out=32,
+               up=2, alpha=0.2, gain=1.0, clamp=256.0, stream=None)
+    orders = {"nb_modconv3x3_f32": "x1 c1 x2 c2 wpk styles dcoefs noise nsn bias y n h w c_out up alpha gain clamp stream",
+              "nb_modconv3x3_up2_f32_h2": "x1 c1 x2 c2 wpk styles dcoefs noise nsn bias out_scale y n h w c_out alpha gain clamp stream"}
+    for entry, order in orders.items():
+        call = lambda **kw: (entry, tuple(dict(f32, **kw)[k] for k in order.split()), None)
+        for k in ("x1", "wpk", "styles", "dcoefs", "bias", "y"):
+            add(call(**{k: None}), "modconv3x3: null pointer")
+        add(call(c2=8), "modconv3x3: bad channel split c1=32 c2=8")
+        add(call(c1=0), "modconv3x3: bad channel split c1=0 c2=0")
+        add(call(c2=-1, x2=P), "modconv3x3: bad channel split c1=32 c2=-1")
+        add(call(n=0), "modconv3x3: batch 0 out of range")
+        add(call(n=65536), "modconv3x3: batch 65536 out of range")
+        add(call(h=2), "modconv3x3: h,w must be powers of two >= 4 (got 2x16)")
+        add(call(w=2), "modconv3x3: h,w must be powers of two >= 4 (got 16x2)")
+        add(call(h=24), "modconv3x3: h,w must be powers of two >= 4 (got 24x16)")
+        add(call(w=48), "modconv3x3: h,w must be powers of two >= 4 (got 16x48)")
+        add(call(c_out=0), "modconv3x3: c_out=0")
+        for k in ("x1", "wpk", "y"):
+            add(call(**{k: ODD}), "modconv3x3: x1, x2, wpk and y must be 16-byte aligned")
+        add(call(x2=ODD, c2=8), "modconv3x3: x1, x2, wpk and y must be 16-byte aligned")
+        # two rules broken at once: the order of the checks
+        add(call(x1=None, n=0), "modconv3x3: null pointer")
+        add(call(n=0, w=48), "modconv3x3: batch 0 out of range")
+        add(call(w=48, y=ODD), "modconv3x3: h,w must be powers of two")
+    add(("nb_modconv3x3_f32", tuple(dict(f32, up=3)[k] for k in orders["nb_modconv3x3_f32"].split()), None), "modconv3x3: up=3 unsupported")
+    add(("nb_modconv3x3_f32", tuple(dict(f32, up=0, y=ODD)[k] for k in orders["nb_modconv3x3_f32"].split()), None), "modconv3x3: up=0 unsupported")
+    good = dict(n=2, h=16, w=16, c_out=32, up=1, buf=ctypes.create_string_buffer(64), buflen=64)
+    for kw in (dict(buf=None), dict(buflen=0), dict(buflen=-1)):
+        add(("nb_modconv3x3_variant", tuple(dict(good, **kw).values()), good["buf"]), "modconv3x3_variant: bad buffer")
+    for kw in (dict(n=0), dict(h=2), dict(w=0), dict(c_out=0), dict(up=3), dict(up=0)):
+        add(("nb_modconv3x3_variant", tuple(dict(good, **kw).values()), good["buf"]), "modconv3x3_variant: bad shape")
     return out
 
 

@@ -116,8 +116,11 @@ def test_modulated_conv2d_kats(dev):
 @pytest.mark.parametrize("shape", [(2, 36, 32, 4), (3, 40, 32, 8), (2, 32, 16, 16), (1, 128, 128, 32), (2, 16, 64, 64),
                                    (1, 144, 128, 32), (1, 64, 64, 128)])
 def test_modconv_vs_oracle(dev, up, shape):
-    """Fused layer (conv + demod + noise + bias + lrelu + clamp) against the CPU oracle; ragged channel
-    counts (36, 40), every tile shape from 4x4 to 128x128, with a split geometry input."""
+    """Fused layer (conv + demod + noise + bias + lrelu + clamp) through ops.modulated_conv2d against the fp32 CPU oracle;
+    ragged channel counts (36, 40), images from 4x4 to 128x128, with a split geometry input.  What runs: the five shapes up to
+    32x32 reach the split-K kernel modconv3x3_up1_kernel<4,1,1,8,4,true> (up = 1) and modconv3x3_up2_kernel<1,8> on 4x4 quad tiles
+    (up = 2); the two large shapes are _split_f16_eligible and go to the split-f16 kernels.  The other nine fp32 kernels, each
+    against float64 with the kernel named: tests/test_hip_modconv_f32_f64.py."""
     from brushstroke_engine_amd import ops
     from oracle import neube_oracle as orc
     n, ic, oc, h = shape
