@@ -26,16 +26,17 @@ tests inject an oracle-backed ``TileOps`` stand-in to check the host logic and t
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import os
 import time
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _lib
-from .sharding import halo_plan, shard_bounds
+from .sharding import HaloExchange, shard_bounds, shard_sizes
 
 CELL_H, CELL_W = 4, 64          # NB_CELL_H / NB_CELL_W of include/neube_hip.h
 PAINT_SLOT0 = 8                 # first generator workspace slot of the tiled schedule (TileOps._GRAPH_SLOT = 16 onwards: graphs)
@@ -231,9 +232,46 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-class TileOps:
+class TileOpsBase:
+    """The scheduling hooks ``PaintingHelper`` calls on its ``ops``, with defaults that do nothing: one stream, no workspaces to
+    prepare, no noise sets, no captured graphs.  ``TileOps`` overrides all of them; the CPU stand-ins of the
+    tests derive from this class and define the device operations (``geom_tiles``, ``encode``, ``head`` / ``tail`` / ``full``, the
+    canvas operations) only."""
+    n_streams = 1
+    stream_policy = 0
+    graph_single = None          # None: no graphs to switch on (render_stroke leaves it alone)
+
+    def stream(self, k: int):
+        return contextlib.nullcontext()
+
+    def comm_stream(self):
+        return contextlib.nullcontext()
+
+    def join_streams(self, tensors=()) -> None:
+        pass
+
+    def join_comm(self, tensors=()) -> None:
+        pass
+
+    def prepare(self, n: int, slots) -> None:
+        pass
+
+    def choose_streams(self, n: int, render_mode: str = "clear") -> None:
+        pass
+
+    def brush_noise(self):
+        """None: this ops has no noise sets, and is never handed one."""
+        return None
+
+    def to_host(self, t: torch.Tensor) -> np.ndarray:
+        return t.cpu().numpy()
+
+
+class TileOps(TileOpsBase):
     """What the tiled schedule needs from the device: the HIP generator split in two, the geometry encoder, and the
     canvas kernels of ``csrc/nb_canvas.hip``."""
+    _comm = None                 # the halo exchange's side stream (comm_stream creates it)
+    _prep_ws = None              # workspace of nb_geom_prepare_u8 (prepare_geometry creates it)
 
     def __init__(self, G, encoder, device=None):
         self.G, self.encoder = G, encoder
@@ -417,7 +455,7 @@ class TileOps:
 
         def run(k, batches):
             # (each stream count keeps its own side streams across the interleaved rounds)
-            self.n_streams = k
+            self._set_n_streams(k)
             self.prepare(n, sorted({PAINT_SLOT0 + i % k for i in range(k)}))
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
@@ -439,7 +477,7 @@ class TileOps:
         # 1.85 -> 1.87 ms per batch: a probe within noise must not cost the job its overlap; a box that loses with concurrent chains
         # (the round-3 driver run saw three streams 14 % below one) shows it as > 3 % here
         best = 1 if times[2] > 1.03 * times[1] else 2
-        self.n_streams = best
+        self._set_n_streams(best)
         self.stream_probe = {"ms_per_batch": {str(k): round(v, 4) for k, v in times.items()}, "chosen": best, "batch": n}
         return best
 
@@ -461,7 +499,7 @@ class TileOps:
     def comm_stream(self):
         """Context manager for the halo exchange: a side stream that first waits for everything enqueued so far on the
         batch streams (the boundary tiles' phase 1), so that packing + the collective overlap the remaining batches."""
-        if getattr(self, "_comm", None) is None:
+        if self._comm is None:
             self._comm = torch.cuda.Stream(device=self.device)
         self._comm.wait_stream(torch.cuda.current_stream(self.device))
         rr = self._rr.get(self.n_streams)
@@ -470,7 +508,7 @@ class TileOps:
         return torch.cuda.stream(self._comm)
 
     def join_comm(self, tensors=()):
-        if getattr(self, "_comm", None) is not None:
+        if self._comm is not None:
             main = torch.cuda.current_stream(self.device)
             main.wait_stream(self._comm)
             for t in tensors:
@@ -556,7 +594,7 @@ class TileOps:
         ch = 1 if img.dim() == 2 else img.shape[2]
         out_h, out_w = (h, w) if out_shape is None else out_shape
         out = torch.empty([out_h, out_w], dtype=torch.uint8, device=self.device)
-        if getattr(self, "_prep_ws", None) is None:
+        if self._prep_ws is None:
             self._prep_ws = torch.empty([_lib.NB_GEOM_PREP_WS_BYTES // 4], dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().nb_geom_prepare_u8(_p(img), h, w, ch, _p(out), out_h, out_w, int(offset[0]), int(offset[1]),
@@ -623,6 +661,42 @@ class StyleUVSMapper:
 # ------------------------------------------------------------------------------------------------
 # the painting helper
 # ------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class _Job:
+    """What one ``PaintingHelper._schedule`` call decides up front and every phase reads."""
+    rank: int
+    world: int
+    sharded: bool                      # the multi-rank schedule: halo exchange, pieces replay, tile gather
+    T: int                             # tiles of the call; this rank owns t0..t1 (``bounds``: every rank's range)
+    bounds: List[Tuple[int, int]]
+    t0: int
+    t1: int
+    geom_dev: torch.Tensor             # the geometry image on the device
+    ws1: torch.Tensor                  # the one brush style of all tiles
+    user_dev: Optional[torch.Tensor]   # the user's colours on the device
+    sfac: Optional[torch.Tensor]       # UVS factor
+    nkw: dict                          # {"noise_set": ...} for a projected brush, else empty
+    own_yx: Optional[torch.Tensor]     # geometry corners / noise positions of my tiles, on the device
+    own_pos: Optional[torch.Tensor]
+    batches: List[Tuple[int, int]]     # (b0, b1) ranges of my tiles; batch k runs under on_stream(k) with workspace plan_slot(k)
+    on_stream: Callable
+    join: Callable
+    plan_slot: Callable
+
+    @property
+    def n_own(self) -> int:
+        return self.t1 - self.t0
+
+    def style(self, n: int) -> torch.Tensor:
+        return self.ws1.expand(n, -1, -1).contiguous()
+
+    def pos(self, b0: int, b1: int) -> Optional[torch.Tensor]:
+        return None if self.own_pos is None else self.own_pos[b0:b1]
+
+    def colors(self, n: int) -> Optional[torch.Tensor]:
+        return None if self.user_dev is None else self.user_dev.expand(n, -1, -1).contiguous()
+
+
 class PaintingHelper:
     """Server-side canvas state + rendering (reference: ``PaintingHelper``, brush.py:95-398).
 
@@ -646,6 +720,8 @@ class PaintingHelper:
         self.down_factor = None
         self._alpha_cache: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self._noise_set, self._noise_src = None, None       # the brush's noise buffers on the device, and the dict they came from
+        self.comm_timing = False                            # record HIP events around the sharded calls' collectives (comm_times)
+        self._comm_events: Dict[str, list] = {}
 
     def _brush_noise(self, opts: "GanBrushOptions"):
         """The noise set of a projected brush: ``opts.custom_args['noise_buffers']`` (what ``formats.WBrushLibrary`` hands to
@@ -656,11 +732,13 @@ class PaintingHelper:
         a dict changed in place is not seen -- hand ``set_style_w`` a new one.  Every rank of a process group builds its own set
         from the same ``opts``; there is no collective in it."""
         bufs = opts.custom_args.get("noise_buffers") if (opts.style_ws is not None and opts.custom_args) else None
-        if not bufs or not hasattr(self.ops, "brush_noise"):
+        if not bufs:
             return None
         bn = self._noise_set
         if bn is None or bn.epoch is not bn.syn.packed:       # first brush, or the weights were reloaded / moved since
             bn, self._noise_src = self.ops.brush_noise(), None
+            if bn is None:
+                return None
             self._noise_set = bn
         if bufs is not self._noise_src:
             bn.load(bufs)
@@ -750,24 +828,40 @@ class PaintingHelper:
         ``geom_yx[i]``, canvas area at ``areas_yx[i]`` (already floored to the blending grid), noise position
         ``positions[i]`` (None: unshifted noise).  Returns the RGBA tiles [T,R,R,4] uint8 on rank 0 (None elsewhere)
         and leaves the feature canvas updated -- the result of the reference's tile-by-tile loop."""
-        ops, R = self.ops, self.patch_width
+        ops, df = self.ops, self.down_factor
+        job = self._begin_job(geom_img, geom_yx, positions, opts, areas_yx.shape[0])
+        if self.feature_blending_level == 0:
+            outs = self._render_unblended(job)
+        else:
+            bres = self.patch_width // df
+            C = ops.cfg.channels(bres)
+            rects = np.concatenate([areas_yx // df, areas_yx // df + bres], axis=1).astype(np.int64)
+            if self.features is None:
+                self.features, self.mask = ops.new_feature_canvas(C, -(-self.rows // df), -(-self.cols // df))
+            alpha0 = self._alpha0(bres, self.feature_blending_margin // df, crop_margin // df)
+            halo = HaloExchange(rects, job.bounds, job.rank, job.world, C, self_probe=job.world == 1) if job.sharded else None
+            mine, geom_feats = self._run_heads(job, bres, C, halo)
+            self._replay(job, mine, areas_yx // df, rects, alpha0, crop_margin // df, halo)
+            outs = self._run_tails(job, mine, geom_feats, bres)
+        rgba_own = torch.cat(outs) if outs else None
+        return self._gather_tiles(job, rgba_own) if job.sharded else rgba_own
+
+    def _begin_job(self, geom_img, geom_yx, positions, opts: GanBrushOptions, T: int) -> _Job:
+        """World split, uploads, the brush (style, noise set, UVS factor) and the stream / slot policy of one call."""
+        ops = self.ops
         rank, world = self._world()
         sharded = self._sharded(world)
-        T = areas_yx.shape[0]
-        level, df = self.feature_blending_level, self.down_factor
-        if sharded and level > 0 and self._canvas_rank_local:
+        if sharded and self.feature_blending_level > 0 and self._canvas_rank_local:
             self.sync_canvas()                   # the previous sharded call left every rank with ITS tiles' paint sequence only
-        t0, t1 = shard_bounds(T, rank, world)
+        bounds = [shard_bounds(T, r, world) for r in range(world)]
+        t0, t1 = bounds[rank]
         n_own = t1 - t0
-        n_pad = -(-T // world)                                                 # equal per-rank count for collectives
-        counts = [shard_bounds(T, r, world)[1] - shard_bounds(T, r, world)[0] for r in range(world)]
 
         geom_dev = geom_img.contiguous() if torch.is_tensor(geom_img) else ops.to_device(np.ascontiguousarray(geom_img))
         ws1 = ops.map_style(z=opts.style_z, ws=opts.style_ws)                  # one brush style for all tiles
         user = opts.user_colors()
         # a projected brush's noise buffers (the UVS calibration below stays without them, as the reference's: mapper.py:84-87)
         noise_set = self._brush_noise(opts)
-        nkw = {} if noise_set is None else {"noise_set": noise_set}
         sfac = None
         if opts.enable_uvs_mapping:                                            # brush.py:773-774
             if self.uvs_mapper is None:
@@ -776,180 +870,134 @@ class PaintingHelper:
         own_yx = ops.to_device(geom_yx[t0:t1].astype(np.int32)) if n_own else None
         own_pos = ops.to_device(positions[t0:t1].astype(np.int64)) if (positions is not None and n_own) else None
 
-        def batches():
-            for b0 in range(0, n_own, self.batch):
-                yield b0, min(b0 + self.batch, n_own)
-
-        def style(n):
-            return ws1.expand(n, -1, -1).contiguous()
-
-        def pos(b0, b1):
-            return None if own_pos is None else own_pos[b0:b1]
-
-        on_stream = getattr(ops, "stream", lambda k: contextlib.nullcontext())      # (CPU stand-ins have no streams)
-        join = getattr(ops, "join_streams", lambda tensors=(): None)
+        on_stream, join = ops.stream, ops.join_streams
         # workspace slots of the painting schedule: disjoint from the generator's own sub-batch slots (1..sub_streams), whose
         # side-stream kernels of an un-joined throughput call may still be reading theirs
         # 1 or 2 batch streams: measured, once per TileOps -- by jobs long enough for the ~80 ms probe to be noise (smaller ones keep the
         # default of two: what they could gain or lose is a fraction of a millisecond)
-        if hasattr(ops, "choose_streams") and (n_own >= 6 * self.batch or getattr(ops, "stream_policy", 0) > 0):
+        if n_own >= 6 * self.batch or ops.stream_policy > 0:
             ops.choose_streams(min(self.batch, n_own), self.render_mode)          # (a fixed policy applies to every canvas size)
-        plan_slot = lambda k: PAINT_SLOT0 + k % getattr(ops, "n_streams", 1)
+        plan_slot = lambda k: PAINT_SLOT0 + k % ops.n_streams
         if n_own <= self.batch:                      # a single batch (interactive strokes): nothing to overlap with
             on_stream, join, plan_slot = (lambda k: contextlib.nullcontext()), (lambda tensors=(): None), (lambda k: 0)
-        elif hasattr(ops, "prepare"):
-            ops.prepare(min(self.batch, n_own), sorted({plan_slot(k) for k in range(getattr(ops, "n_streams", 1))}))
-        user_dev = None if user is None else user.to(ops.device)
-        colors = lambda n_: None if user_dev is None else user_dev.expand(n_, -1, -1).contiguous()
-        outs = []
-        if level == 0:
-            for k, (b0, b1) in enumerate(batches()):
-                with on_stream(k):
-                    g = ops.geom_tiles(geom_dev, own_yx[b0:b1])
-                    outs.append(ops.full(style(b1 - b0), ops.encode(g), pos(b0, b1), self.render_mode, colors(b1 - b0), sfac,
-                                         slot=plan_slot(k), **nkw))
-            join(outs)
         else:
-            bres = R // df
-            C = ops.cfg.channels(bres)
-            margin, crop_sc = self.feature_blending_margin // df, crop_margin // df
-            rects = np.concatenate([areas_yx // df, areas_yx // df + bres], axis=1).astype(np.int64)
-            if self.features is None:
-                self.features, self.mask = ops.new_feature_canvas(C, -(-self.rows // df), -(-self.cols // df))
-            hc, wc = self.mask.shape
-            alpha0 = self._alpha0(bres, margin, crop_sc)
-            # halo plan: the strips of earlier foreign tiles under my tiles (recv) and of my tiles under later ranks' (send)
-            bounds = [shard_bounds(T, r, world) for r in range(world)]
-            plan = halo_plan(rects, bounds) if sharded else {}
-            send = {d: plan[(rank, d)] for d in range(world) if (rank, d) in plan}
-            recv = {s_: plan[(s_, rank)] for s_ in range(world) if (s_, rank) in plan}
-            # one rank under NB_FORCE_PG=1: nothing to exchange, so the all-to-all would carry no bytes -- let it carry ONE strip of
-            # my first tile to myself (checked bit for bit after the exchange, not replayed): the packing, the split lists and the
-            # collective itself then run as they do between ranks
-            self_probe = None
-            if sharded and world == 1 and n_own:
-                r0 = rects[t0]
-                self_probe = (t0, (int(r0[0]), int(r0[1]), int(r0[0]) + min(bres, 20), int(r0[3])))
-                send = {0: [self_probe]}
-                recv_probe = {0: [self_probe]}
-            first_send = min((f for lst in send.values() for f, _ in lst), default=t1) - t0
-            # phase 1: everything up to the blending resolution, own tiles.  The batches run last-to-first: the tiles the
-            # later ranks need (the end of my range) finish first, and their strips travel under the rest of phase 1.
-            mine = torch.empty([n_own, C, bres, bres], dtype=torch.float32, device=ops.device)
-            geom_feats_own = {}
-            work = recv_buf = send_buf = None
-            nfl = lambda lst: sum(C * (q[2] - q[0]) * (q[3] - q[1]) for _, q in lst)
-            in_split = [nfl(send.get(d, [])) for d in range(world)]
-            out_split = [nfl((recv if self_probe is None else recv_probe).get(s_, [])) for s_ in range(world)]
-            comm = getattr(ops, "comm_stream", lambda: contextlib.nullcontext())
+            ops.prepare(min(self.batch, n_own), sorted({plan_slot(k) for k in range(ops.n_streams)}))
+        return _Job(rank=rank, world=world, sharded=sharded, T=T, bounds=bounds, t0=t0, t1=t1, geom_dev=geom_dev, ws1=ws1,
+                    user_dev=None if user is None else user.to(ops.device), sfac=sfac,
+                    nkw={} if noise_set is None else {"noise_set": noise_set}, own_yx=own_yx, own_pos=own_pos,
+                    batches=[(b0, min(b0 + self.batch, n_own)) for b0 in range(0, n_own, self.batch)],
+                    on_stream=on_stream, join=join, plan_slot=plan_slot)
 
-            def exchange():
-                nonlocal work, recv_buf, send_buf
-                recv_buf = torch.empty([sum(out_split)], dtype=torch.float32, device=ops.device)
-                with comm():
-                    parts = [mine[f - t0, :, q[0] - rects[f, 0]:q[2] - rects[f, 0], q[1] - rects[f, 1]:q[3] - rects[f, 1]].reshape(-1)
-                             for d in range(world) for f, q in send.get(d, [])]
-                    send_buf = torch.cat(parts) if parts else torch.empty([0], dtype=torch.float32, device=ops.device)
-                    work = dist.all_to_all_single(recv_buf, send_buf, out_split, in_split, group=self.group, async_op=True)
-                self.halo_bytes = {"sent": 4 * sum(in_split), "received": 4 * sum(out_split)}
+    def _render_unblended(self, job: _Job) -> List[torch.Tensor]:
+        """Level 0: every batch is one full generator pass."""
+        ops, outs = self.ops, []
+        for k, (b0, b1) in enumerate(job.batches):
+            with job.on_stream(k):
+                g = ops.geom_tiles(job.geom_dev, job.own_yx[b0:b1])
+                outs.append(ops.full(job.style(b1 - b0), ops.encode(g), job.pos(b0, b1), self.render_mode, job.colors(b1 - b0),
+                                     job.sfac, slot=job.plan_slot(k), **job.nkw))
+        job.join(outs)
+        return outs
 
-            blist = list(enumerate(batches()))
-            for k, (b0, b1) in reversed(blist):
-                with on_stream(k):
-                    gf = ops.encode(ops.geom_tiles(geom_dev, own_yx[b0:b1]))
-                    geom_feats_own[k] = gf
-                    mine[b0:b1] = ops.head(style(b1 - b0), gf, pos(b0, b1), bres, slot=plan_slot(k), **nkw)
-                if sharded and work is None and b0 <= first_send:
-                    exchange()
-            if sharded and work is None:
-                exchange()                                                        # (a rank without tiles still takes part)
-            join()
-            if work is not None:
-                # (events on the caller's stream: the first fires when phase 1 is through, the second when the strips are there
-                #  -- what of the exchange was NOT hidden under phase 1; comm_times())
-                ev = self._comm_event_pair("halo_exchange_exposed_ms")
-                work.wait()
-                getattr(ops, "join_comm", lambda tensors=(): None)([recv_buf])
+    def _run_heads(self, job: _Job, bres: int, C: int, halo: Optional[HaloExchange]):
+        """Phase 1: everything up to the blending resolution, own tiles -> (``mine`` [n_own,C,bres,bres], the batches' geometry
+        features).  The batches run last-to-first: the tiles the later ranks need (the end of my range) finish first, and their
+        strips travel under the rest of phase 1.  Returns with the strips of the other ranks received."""
+        ops = self.ops
+        mine = torch.empty([job.n_own, C, bres, bres], dtype=torch.float32, device=ops.device)
+        geom_feats = {}
+        for k, (b0, b1) in reversed(list(enumerate(job.batches))):
+            with job.on_stream(k):
+                gf = ops.encode(ops.geom_tiles(job.geom_dev, job.own_yx[b0:b1]))
+                geom_feats[k] = gf
+                mine[b0:b1] = ops.head(job.style(b1 - b0), gf, job.pos(b0, b1), bres, slot=job.plan_slot(k), **job.nkw)
+            if halo is not None and not halo.started and b0 <= halo.first_send:
+                self._start_exchange(halo, mine, job)
+        if halo is not None and not halo.started:
+            self._start_exchange(halo, mine, job)                                 # (a rank without tiles still takes part)
+        job.join()
+        if halo is not None:
+            # (events on the caller's stream: the first fires when phase 1 is through, the second when the strips are there
+            #  -- what of the exchange was NOT hidden under phase 1; comm_times())
+            ev = self._comm_event_pair("halo_exchange_exposed_ms")
+
+            def arrived(bufs):
+                ops.join_comm(bufs)
                 if ev is not None:
                     ev[1].record()
-                if self_probe is not None:
-                    f, q = self_probe
-                    src = mine[f - t0, :, q[0] - rects[f, 0]:q[2] - rects[f, 0], q[1] - rects[f, 1]:q[3] - rects[f, 1]].reshape(-1)
-                    if recv_buf.numel() != src.numel() or not torch.equal(recv_buf, src):
-                        raise RuntimeError("NB_FORCE_PG: the strip sent to myself through all_to_all_single came back changed")
-            # phase 2: the sequential canvas blend of my tiles, replayed in one launch
-            if not sharded:
-                off, lst = build_cells(rects, hc, wc)
-                # few tiles on a large canvas (interactive strokes): replay only the cells inside their bounding box
-                box = None
-                if T * bres * bres * 4 < hc * wc:
-                    box = (int(rects[:, 0].min()), int(rects[:, 1].min()), int(rects[:, 2].max()), int(rects[:, 3].max()))
-                self.mask = ops.replay(mine, ops.to_device((areas_yx // df).astype(np.int32)), alpha0, crop_sc,
-                                       self.features, self.mask, ops.to_device(off), ops.to_device(lst), **({"box": box} if box else {}))
-            elif n_own:
-                # pieces in paint order: received strips of earlier foreign tiles (compact [C,h,w] blocks of recv_buf), then
-                # my own full tiles (every foreign tile a rank needs precedes its range)
-                pieces, prect, o = [], [], 0
-                for s_ in range(world):
-                    for f, q in recv.get(s_, []):
-                        h_, w_ = q[2] - q[0], q[3] - q[1]
-                        pieces.append((f, recv_buf[o:o + C * h_ * w_].view(C, h_, w_), q[0], q[1], q[0] - rects[f, 0], q[1] - rects[f, 1]))
-                        prect.append(q)
-                        o += C * h_ * w_
-                order = sorted(range(len(pieces)), key=lambda i: pieces[i][0])
-                pieces = [pieces[i][1:] for i in order]
-                prect = [prect[i] for i in order]
-                for i in range(n_own):
-                    pieces.append((mine[i], int(rects[t0 + i, 0]), int(rects[t0 + i, 1]), 0, 0))
-                    prect.append(tuple(int(v) for v in rects[t0 + i]))
-                off, lst = build_cells(np.asarray(prect, np.int64), hc, wc)
-                own_r = rects[t0:t1]
-                box = (int(own_r[:, 0].min()), int(own_r[:, 1].min()), int(own_r[:, 2].max()), int(own_r[:, 3].max()))
-                self.mask = ops.replay_pieces(pieces, bres, alpha0, crop_sc, self.features, self.mask,
-                                              ops.to_device(off), ops.to_device(lst), box)
-            if sharded:
-                # my canvas now holds the paint sequence under MY tiles only; what it takes to make it whole again
-                # (sync_canvas, run lazily by the next sharded call on this canvas) is the tile layout of this call
-                self._canvas_rank_local = True
-                self._sync_layout = (rects.copy(), bounds)
-            # phase 3: last block(s) + ToRGB + compositing on the blended features, own tiles
-            for i, (b0, b1) in blist:
-                with on_stream(i):
-                    outs.append(ops.tail(style(b1 - b0), mine[b0:b1], geom_feats_own[i], pos(b0, b1), bres,
-                                         self.render_mode, colors(b1 - b0), sfac, slot=plan_slot(i), **nkw))
-            join(outs)
-        rgba_own = torch.cat(outs) if outs else None
-        if not sharded:
-            return rgba_own
-        buf = torch.zeros([n_pad, R, R, 4], dtype=torch.uint8, device=ops.device)
-        if n_own:
-            buf[:n_own] = rgba_own
-        recv = [torch.empty_like(buf) for _ in range(world)] if rank == 0 else None
+            halo.finish(mine, job.t0, arrived)
+        return mine, geom_feats
+
+    def _start_exchange(self, halo: HaloExchange, mine: torch.Tensor, job: _Job) -> None:
+        halo.start(mine, job.t0, self.ops.comm_stream, self.group)
+        self.halo_bytes = halo.halo_bytes
+
+    def _replay(self, job: _Job, mine, areas, rects, alpha0, crop_sc: int, halo: Optional[HaloExchange]) -> None:
+        """Phase 2: the sequential canvas blend of my tiles, replayed in one launch -- over whole tiles, or (sharded) over the
+        received strips and my tiles."""
+        ops = self.ops
+        bres = mine.shape[-1]
+        hc, wc = self.mask.shape
+        if halo is None:
+            off, lst = build_cells(rects, hc, wc)
+            # few tiles on a large canvas (interactive strokes): replay only the cells inside their bounding box
+            box = None
+            if job.T * bres * bres * 4 < hc * wc:
+                box = (int(rects[:, 0].min()), int(rects[:, 1].min()), int(rects[:, 2].max()), int(rects[:, 3].max()))
+            self.mask = ops.replay(mine, ops.to_device(areas.astype(np.int32)), alpha0, crop_sc,
+                                   self.features, self.mask, ops.to_device(off), ops.to_device(lst), **({"box": box} if box else {}))
+            return
+        if job.n_own:
+            pieces, prect = halo.pieces(mine, job.t0, job.t1)
+            off, lst = build_cells(np.asarray(prect, np.int64), hc, wc)
+            own_r = rects[job.t0:job.t1]
+            box = (int(own_r[:, 0].min()), int(own_r[:, 1].min()), int(own_r[:, 2].max()), int(own_r[:, 3].max()))
+            self.mask = ops.replay_pieces(pieces, bres, alpha0, crop_sc, self.features, self.mask,
+                                          ops.to_device(off), ops.to_device(lst), box)
+        # my canvas now holds the paint sequence under MY tiles only; what it takes to make it whole again
+        # (sync_canvas, run lazily by the next sharded call on this canvas) is the tile layout of this call
+        self._canvas_rank_local = True
+        self._sync_layout = (rects.copy(), job.bounds)
+
+    def _run_tails(self, job: _Job, mine, geom_feats, bres: int) -> List[torch.Tensor]:
+        """Phase 3: last block(s) + ToRGB + compositing on the blended features, own tiles."""
+        ops, outs = self.ops, []
+        for k, (b0, b1) in enumerate(job.batches):
+            with job.on_stream(k):
+                outs.append(ops.tail(job.style(b1 - b0), mine[b0:b1], geom_feats[k], job.pos(b0, b1), bres,
+                                     self.render_mode, job.colors(b1 - b0), job.sfac, slot=job.plan_slot(k), **job.nkw))
+        job.join(outs)
+        return outs
+
+    def _gather_tiles(self, job: _Job, rgba_own: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """The ranks' RGBA tiles on rank 0, in paint order (None elsewhere): one gather of equally padded buffers."""
+        R, world = self.patch_width, job.world
+        buf = torch.zeros([-(-job.T // world), R, R, 4], dtype=torch.uint8, device=self.ops.device)
+        if job.n_own:
+            buf[:job.n_own] = rgba_own
+        recv = [torch.empty_like(buf) for _ in range(world)] if job.rank == 0 else None
         ev = self._comm_event_pair("tile_gather_ms")
         dist.gather(buf, recv, dst=0, group=self.group)
         if ev is not None:
             ev[1].record()
-        if rank != 0:
+        if job.rank != 0:
             return None
-        return torch.cat([recv[r][:counts[r]] for r in range(world)])
+        return torch.cat([recv[r][:n] for r, n in enumerate(shard_sizes(job.T, world))])
 
     def _comm_event_pair(self, name: str):
         """A pair of HIP events around a collective of the sharded schedule (first one recorded here, on the caller's stream).
         Only when ``self.comm_timing`` is set (benchmarks: tools/bench_canvas.py): the product path records nothing."""
-        dev = getattr(self.ops, "device", None)
-        if not getattr(self, "comm_timing", False) or dev is None or getattr(dev, "type", "cpu") != "cuda":
+        if not self.comm_timing or self.ops.device.type != "cuda":
             return None
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        if not hasattr(self, "_comm_events"):
-            self._comm_events = {}
         self._comm_events.setdefault(name, []).append((e0, e1))
         return e0, e1
 
     def comm_times(self, reset: bool = True) -> Dict[str, float]:
         """Milliseconds this rank's stream spent on the collectives of the sharded calls since the last reset: the part of the
         halo exchange that phase 1 did not hide, and the gather of the RGBA tiles on rank 0 (synchronises the device)."""
-        evs = getattr(self, "_comm_events", {})
+        evs = self._comm_events
         if not evs:
             return {}
         torch.cuda.synchronize(self.ops.device)
@@ -1005,7 +1053,7 @@ class PaintingHelper:
         fy, fx = (y // df) * df, (x // df) * df
         geom = (255 - stroke_patch[:, :, -1]).astype(np.uint8)                     # back to 255 = background
         pos = None if opts.position is None else opts.position.numpy().reshape(1, 2)
-        prev = getattr(self.ops, "graph_single", None)
+        prev = self.ops.graph_single
         if prev is not None and self.graph_strokes:
             self.ops.graph_single = True                  # one tile per call: replay captured generator passes
         try:
@@ -1031,7 +1079,7 @@ class PaintingHelper:
         if canvas is None:
             return None
         m, (h0, w0) = crop_margin, geom.shape[:2]
-        to_host = getattr(self.ops, "to_host", lambda t: t.cpu().numpy())
+        to_host = self.ops.to_host
         result = canvas[m:m + h0, m:m + w0]                          # crop on the device: only the answer crosses PCIe
         if on_white:                                                # paint_image_main.py:179-183 (3 channels out)
             # alpha = a / 255 through a host-computed table: device division is not correctly rounded
@@ -1041,8 +1089,7 @@ class PaintingHelper:
         out = to_host(result.contiguous())
         if not return_full:
             return out
-        full = to_host(canvas)
-        return (out, full, crops, padded) if return_full else out
+        return out, to_host(canvas), crops, padded
 
     def paint_drawing(self, img: np.ndarray, opts: GanBrushOptions, crop_margin: int = 10, stitching_mode: str = "all",
                       on_white: bool = False, return_full: bool = False):

@@ -87,6 +87,86 @@ def halo_plan(rects: np.ndarray, bounds: Sequence[Tuple[int, int]]) -> Dict[Tupl
     return plan
 
 
+class HaloExchange:
+    """One rank's side of the halo exchange of ONE sharded, feature-blended call: the strips of earlier foreign tiles under my tiles
+    (``recv``) and of my tiles under later ranks' (``send``) out of ``halo_plan``, the split lists of the ONE ``all_to_all_single``
+    that moves them, and the paint-ordered piece list the rank replays afterwards.  ``rects`` [T,4] are all tiles' rectangles on the
+    feature canvas, ``bounds`` every rank's tile range, ``channels`` the feature channels; tiles arrive as ``mine`` [n_own,C,h,w]
+    (the rank's own tiles, ``mine[f - t0]`` = tile f).
+
+    ``self_probe`` (one rank under ``NB_FORCE_PG=1``): there is nothing to exchange, so the all-to-all would carry no bytes -- it
+    carries ONE strip (at most 20 rows) of my first tile to myself, checked bit for bit in ``finish`` and not replayed: the packing,
+    the split lists and the collective itself then run as they do between ranks."""
+
+    def __init__(self, rects: np.ndarray, bounds: Sequence[Tuple[int, int]], rank: int, world: int, channels: int,
+                 self_probe: bool = False):
+        self.rects, self.world, self.channels = rects, world, channels
+        t0, t1 = bounds[rank]
+        plan = halo_plan(rects, bounds)
+        self.send = {d: plan[(rank, d)] for d in range(world) if (rank, d) in plan}
+        self.recv = {s: plan[(s, rank)] for s in range(world) if (s, rank) in plan}
+        arriving = self.recv                       # what the collective delivers; ``recv`` is what gets replayed
+        self.probe = None
+        if self_probe and world == 1 and t1 > t0:
+            r0 = rects[t0]
+            self.probe = (t0, (int(r0[0]), int(r0[1]), int(r0[0]) + min(int(r0[2] - r0[0]), 20), int(r0[3])))
+            self.send = arriving = {0: [self.probe]}
+        # (relative to t0) the first of my tiles somebody else needs: the exchange can start once phase 1 has reached it
+        self.first_send = min((f for lst in self.send.values() for f, _ in lst), default=t1) - t0
+        nfl = lambda lst: sum(channels * (q[2] - q[0]) * (q[3] - q[1]) for _, q in lst)
+        self.in_split = [nfl(self.send.get(d, [])) for d in range(world)]
+        self.out_split = [nfl(arriving.get(s, [])) for s in range(world)]
+        self.halo_bytes = {"sent": 4 * sum(self.in_split), "received": 4 * sum(self.out_split)}
+        self._work = self._recv_buf = self._send_buf = None
+
+    def strip(self, mine: torch.Tensor, t0: int, f: int, q: Rect) -> torch.Tensor:
+        """The canvas rectangle ``q`` of my tile ``f`` as a view [C,h,w] of ``mine``."""
+        y, x = self.rects[f, 0], self.rects[f, 1]
+        return mine[f - t0, :, q[0] - y:q[2] - y, q[1] - x:q[3] - x]
+
+    @property
+    def started(self) -> bool:
+        return self._work is not None
+
+    def start(self, mine: torch.Tensor, t0: int, comm_ctx, group=None) -> None:
+        """Pack my strips and start the all-to-all inside ``comm_ctx()`` (a context manager factory: ``TileOps.comm_stream``)."""
+        self._recv_buf = torch.empty([sum(self.out_split)], dtype=torch.float32, device=mine.device)
+        with comm_ctx():
+            parts = [self.strip(mine, t0, f, q).reshape(-1) for d in range(self.world) for f, q in self.send.get(d, [])]
+            self._send_buf = torch.cat(parts) if parts else torch.empty([0], dtype=torch.float32, device=mine.device)
+            self._work = dist.all_to_all_single(self._recv_buf, self._send_buf, self.out_split, self.in_split, group=group,
+                                                async_op=True)
+
+    def finish(self, mine: torch.Tensor, t0: int, on_arrival=None) -> None:
+        """Wait for the strips; ``on_arrival([buffer])`` then lets the caller's stream join the one the collective ran on, before
+        the self-probe strip is compared with what was sent."""
+        self._work.wait()
+        if on_arrival is not None:
+            on_arrival([self._recv_buf])
+        if self.probe is not None:
+            src = self.strip(mine, t0, *self.probe).reshape(-1)
+            if self._recv_buf.numel() != src.numel() or not torch.equal(self._recv_buf, src):
+                raise RuntimeError("NB_FORCE_PG: the strip sent to myself through all_to_all_single came back changed")
+
+    def pieces(self, mine: torch.Tensor, t0: int, t1: int):
+        """(pieces, rectangles) in paint order: received strips of earlier foreign tiles (compact [C,h,w] blocks of the receive
+        buffer, by source rank, then stably by tile index), then my own full tiles (every foreign tile a rank needs precedes its
+        range).  A piece is (view [C,h,w], cy, cx, ly0, lx0), as ``TileOps.replay_pieces`` takes them."""
+        C, rects = self.channels, self.rects
+        got, o = [], 0
+        for s in range(self.world):
+            for f, q in self.recv.get(s, []):
+                h, w = q[2] - q[0], q[3] - q[1]
+                got.append((f, q, (self._recv_buf[o:o + C * h * w].view(C, h, w), q[0], q[1], q[0] - rects[f, 0], q[1] - rects[f, 1])))
+                o += C * h * w
+        got.sort(key=lambda g: g[0])
+        pieces, prect = [g[2] for g in got], [g[1] for g in got]
+        for i in range(t1 - t0):
+            pieces.append((mine[i], int(rects[t0 + i, 0]), int(rects[t0 + i, 1]), 0, 0))
+            prect.append(tuple(int(v) for v in rects[t0 + i]))
+        return pieces, prect
+
+
 class TileGatherer:
     """Gathers equally shaped per-rank tile tensors to ``dst`` with pre-allocated receive buffers.
 

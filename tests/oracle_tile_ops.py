@@ -6,9 +6,10 @@ import torch
 
 from oracle import neube_oracle as no
 from oracle import painting_oracle as po
+from brushstroke_engine_amd.painting import TileOpsBase
 
 
-class OracleTileOps:
+class OracleTileOps(TileOpsBase):
     def __init__(self, cfg, sd, esd, preproc_type=None):
         self.G = no.OracleGenerator(cfg, sd)
         self.cfg, self.esd, self.preproc = cfg, esd, preproc_type

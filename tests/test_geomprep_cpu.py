@@ -88,7 +88,7 @@ def test_header_and_binding_agree_on_the_entries(library):
     assert "nb_geomprep.hip" in build.SOURCES
 
 
-class _NoPrepOps:
+class _NoPrepOps(painting.TileOpsBase):
     """What the CPU stand-ins of TileOps look like to paint_drawing: no preparation kernels."""
     patch_width = 128
 
