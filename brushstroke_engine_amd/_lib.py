@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _lock = threading.Lock()
 _lib = None
@@ -155,6 +155,10 @@ PROTOTYPES = {
     "nb_tile_stroke_counts_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "nb_composite_on_white_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "nb_stitching_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5),
+    # vector strokes (csrc/nb_strokes.hip): splines cut into capsule segments, segments rasterised into the geometry
+    "nb_raster_segments_u8": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "nb_spline_flatten_f32": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp]),
+    "nb_spline_segment_count": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -251,6 +255,7 @@ class NbPassPlan(C.Structure):
 
 
 NB_GEOM_PREP_WS_BYTES = 1040
+NB_SEG_PITCH = 8
 
 NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3
 NB_CONV_MODES = {"f32": 0, "h3": 1, "f8": 2, "f6": 3, "f16": 4}

@@ -5,6 +5,9 @@
     python -m brushstroke_engine_amd.paint_image_main --gan_checkpoint engine.npz --geom_image drawing.png \\
         --output_file_prefix out/drawing --style_id 594 --feature_blending_level 2 [--on_white]
 
+``--strokes strokes.json --canvas_size H,W`` takes vector strokes instead of ``--geom_image``: polylines and Catmull-Rom splines
+(``painting.StrokeList``'s JSON schema), rasterised into the geometry on the device.
+
 ``--gpus N`` (or running it under ``torch.distributed.run``, one process per GPU) shards the tiles over the ranks;
 rank 0 writes the file.  ``--conv_mode`` chooses the arithmetic of the conv layers explicitly (default: the library
 default, ``f8``; ``h3`` = fp32-grade products, ``f32`` = exact fp32 MFMA).
@@ -41,7 +44,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Tiled canvas stylization on MI355X.")
     ap.add_argument("--gan_checkpoint", required=True, help=".npz engine container (generator + encoder)")
     ap.add_argument("--output_file_prefix", required=True)
-    ap.add_argument("--geom_image", required=True, help="Large geometry guidance")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--geom_image", help="Large geometry guidance")
+    src.add_argument("--strokes", help="vector strokes instead of a drawing: a JSON list of {type: polyline | spline, points: [[x, y], ...], "
+                                       "radius: r | [r, ...]} (painting.StrokeList); needs --canvas_size")
+    ap.add_argument("--canvas_size", default=None, help="H,W of the drawing the --strokes are placed on (pixels)")
     ap.add_argument("--stitching_mode", default="all", help="Which patches to paint: all | full")
     ap.add_argument("--feature_blending_level", type=int, default=0)
     ap.add_argument("--library", default="rand100")
@@ -66,8 +73,27 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def parse_canvas_size(text: str):
+    """'H,W' -> (H, W), both positive."""
+    parts = text.split(",")
+    if len(parts) != 2:
+        raise ValueError(f"--canvas_size takes H,W, got {text!r}")
+    h, w = int(parts[0]), int(parts[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"--canvas_size must be positive, got {text!r}")
+    return h, w
+
+
 def main(argv=None) -> str:
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if (args.strokes is None) != (args.canvas_size is None):
+        ap.error("--strokes and --canvas_size go together")
+    if args.strokes is not None:
+        try:
+            canvas_hw = parse_canvas_size(args.canvas_size)
+        except ValueError as e:
+            ap.error(str(e))
     if args.gpus > 1 and not launch.under_torchrun():
         import sys
         raise SystemExit(launch.self_launch(__file__, sys.argv[1:] if argv is None else list(argv), args.gpus))
@@ -92,13 +118,20 @@ def main(argv=None) -> str:
     else:
         library.set_interpolated_style(args.style_id, args.style_id2, args.style_blend_alpha, opts)
     from PIL import Image
-    drawing = np.array(Image.open(args.geom_image))
+    if args.strokes is not None:
+        with open(args.strokes) as f:
+            strokes = painting.StrokeList.from_json(f.read())
+    else:
+        drawing = np.array(Image.open(args.geom_image))
     helper = painting.PaintingHelper(ops, batch=args.batch, uvs_mapper=mapper)
     helper.set_feature_blending(args.feature_blending_level)
     helper.set_render_mode(args.render_mode)
     with torch.no_grad():
         # (the kernels take 8-bit gray / RGB / RGBA; 1-bit, 16-bit and gray + alpha files keep the numpy route)
-        if args.host_prepare or drawing.dtype != np.uint8 or (drawing.ndim == 3 and drawing.shape[2] not in (1, 3, 4)):
+        if args.strokes is not None:
+            result = helper.paint_strokes(strokes, canvas_hw, opts, crop_margin=args.crop_margin, stitching_mode=args.stitching_mode,
+                                          on_white=args.on_white)
+        elif args.host_prepare or drawing.dtype != np.uint8 or (drawing.ndim == 3 and drawing.shape[2] not in (1, 3, 4)):
             result = helper.paint_image(painting.prepare_geometry_image(drawing), opts, crop_margin=args.crop_margin,
                                         stitching_mode=args.stitching_mode, on_white=args.on_white)
         else:

@@ -175,6 +175,191 @@ def build_cells(rects: np.ndarray, h: int, w: int) -> Tuple[np.ndarray, np.ndarr
 
 
 # ------------------------------------------------------------------------------------------------
+# vector strokes (csrc/nb_strokes.hip): polylines and centripetal Catmull-Rom splines as capsule segments
+# ------------------------------------------------------------------------------------------------
+SEG_PITCH = _lib.NB_SEG_PITCH     # floats per segment row: x0, y0, x1, y1, r, three reserved
+
+
+class StrokeList:
+    """Strokes as points: what a tablet or a vector file gives, and what ``TileOps.raster_strokes`` /
+    ``PaintingHelper.paint_strokes`` turn into the geometry without a raster on the host.
+
+    Coordinates are drawing coordinates ``(x, y)`` in pixels; pixel (row y, column x) has its centre at exactly ``(x, y)``.
+    A stroke covers every pixel whose centre is within the radius of its centre line.  Everything is kept as float32, the
+    values the device reads.
+
+    JSON schema (``to_json`` / ``from_json``): a list of objects
+    ``{"type": "polyline" | "spline", "points": [[x, y], ...], "radius": r | [r, ...]}``; a spline may carry
+    ``"through_ends": false`` (default true)."""
+
+    def __init__(self):
+        self.items: List[dict] = []           # what was added, in order (the JSON form)
+        self._poly: List[np.ndarray] = []     # [n, 5] float32 segment rows per polyline
+        self._ctrl: List[np.ndarray] = []     # [P, 3] float32 control points (x, y, r) per spline, phantom ends included
+
+    @staticmethod
+    def _points_radius(points, radius) -> Tuple[np.ndarray, np.ndarray]:
+        p = np.asarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+            raise ValueError(f"stroke points must be [K, 2] with K >= 1, got {p.shape}")
+        r = np.asarray(radius, np.float32)
+        if r.ndim == 0:
+            r = np.full(p.shape[0], r, np.float32)
+        if r.shape != (p.shape[0],):
+            raise ValueError(f"radius must be a scalar or one per point ({p.shape[0]}), got {r.shape}")
+        if not (np.isfinite(p).all() and np.isfinite(r).all() and (r >= 0).all()):
+            raise ValueError("stroke points and radii must be finite, radii >= 0")
+        return p, r
+
+    @staticmethod
+    def _json_radius(radius):
+        r = np.asarray(radius, np.float32)
+        return float(r) if r.ndim == 0 else [float(v) for v in r]
+
+    def add_polyline(self, points, radius) -> "StrokeList":
+        """Straight segments through ``points`` [K, 2]; ``radius`` a scalar or one per point (a segment's radius is the mean of
+        its end points').  A single point is a disc."""
+        p, r = self._points_radius(points, radius)
+        if p.shape[0] == 1:
+            p, r = np.repeat(p, 2, 0), np.repeat(r, 2)
+        rows = np.concatenate([p[:-1], p[1:], ((r[:-1] + r[1:]) * np.float32(0.5))[:, None]], axis=1).astype(np.float32)
+        self._poly.append(rows)
+        self.items.append({"type": "polyline", "points": np.asarray(points, np.float32).tolist(), "radius": self._json_radius(radius)})
+        return self
+
+    def add_spline(self, points, radius, through_ends: bool = True) -> "StrokeList":
+        """A centripetal Catmull-Rom spline (the curve of the reference's ``forger/core/curve.py``) through ``points`` [K, 2];
+        ``radius`` a scalar or one per point, interpolated linearly along each span.  The curve of P control points runs from the
+        second to the last but one; ``through_ends`` adds the reflected phantom points ``2 P0 - P1`` and ``2 P_last - P_prev`` so
+        that it passes through the first and last given point.  Consecutive duplicate points are dropped (a repeated control point
+        has no curve: its knot interval is zero)."""
+        p, r = self._points_radius(points, radius)
+        keep = np.concatenate([[True], np.any(p[1:] != p[:-1], axis=1)])
+        p, r = p[keep], r[keep]
+        if through_ends:
+            if p.shape[0] < 2:
+                raise ValueError("a spline through its ends needs at least 2 distinct points")
+            p = np.concatenate([(2 * p[:1] - p[1:2]), p, (2 * p[-1:] - p[-2:-1])]).astype(np.float32)
+            r = np.concatenate([r[:1], r, r[-1:]])
+        if p.shape[0] < 4:
+            raise ValueError(f"a spline needs at least 4 distinct control points, got {p.shape[0]}")
+        self._ctrl.append(np.concatenate([p, r[:, None]], axis=1).astype(np.float32))
+        item = {"type": "spline", "points": np.asarray(points, np.float32).tolist(), "radius": self._json_radius(radius)}
+        if not through_ends:
+            item["through_ends"] = False
+        self.items.append(item)
+        return self
+
+    def __len__(self) -> int:
+        return len(self.items)
+
+    def to_json(self) -> str:
+        import json
+        return json.dumps(self.items)
+
+    @classmethod
+    def from_json(cls, text) -> "StrokeList":
+        """From a JSON string or the list it decodes to."""
+        import json
+        data = json.loads(text) if isinstance(text, (str, bytes)) else text
+        if not isinstance(data, list):
+            raise ValueError("strokes JSON: a list of stroke objects expected")
+        out = cls()
+        for it in data:
+            kind = it.get("type") if isinstance(it, dict) else None
+            if kind == "polyline":
+                out.add_polyline(it["points"], it["radius"])
+            elif kind == "spline":
+                out.add_spline(it["points"], it["radius"], through_ends=bool(it.get("through_ends", True)))
+            else:
+                raise ValueError(f"strokes JSON: unknown stroke {it!r}")
+        return out
+
+    def polyline_segments(self) -> np.ndarray:
+        """[n, SEG_PITCH] float32 segment rows of all polylines."""
+        rows = np.zeros((sum(a.shape[0] for a in self._poly), SEG_PITCH), np.float32)
+        if self._poly:
+            rows[:, :5] = np.concatenate(self._poly)
+        return rows
+
+    def spline_control(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(ctrl [P_total, 3] float32, stroke_off [n_splines + 1] int32): the inputs of ``nb_spline_flatten_f32``."""
+        off = np.zeros(len(self._ctrl) + 1, np.int32)
+        np.cumsum([a.shape[0] for a in self._ctrl], out=off[1:])
+        ctrl = np.concatenate(self._ctrl) if self._ctrl else np.zeros((0, 3), np.float32)
+        return np.ascontiguousarray(ctrl, np.float32), off
+
+    def spline_segment_count(self, subdiv: int) -> int:
+        return (sum(a.shape[0] for a in self._ctrl) - 3 * len(self._ctrl)) * int(subdiv)
+
+
+def flatten_splines_numpy(ctrl: np.ndarray, stroke_off: np.ndarray, subdiv: int, alpha: float = 0.5, dtype=np.float64) -> np.ndarray:
+    """``nb_spline_flatten_f32`` restated in numpy: [n, 5] rows (x0, y0, x1, y1, r) in ``dtype``.  Per span the knots are
+    t0 = 0, t1 = |P1 - P0|^alpha, t2 = t1 + |P2 - P1|^alpha, t3 = t2 + |P3 - P2|^alpha; a sample is the pyramid A1..A3 -> B1, B2 -> C
+    of linear interpolations over the knot intervals; sample k of a stroke closes segment k - 1 and opens segment k."""
+    ctrl, subdiv = np.asarray(ctrl), int(subdiv)
+    out = []
+    for s in range(len(stroke_off) - 1):
+        c = ctrl[int(stroke_off[s]):int(stroke_off[s + 1])].astype(dtype)
+        p, rad = c[:, :2], c[:, 2]
+        nsp = p.shape[0] - 3
+        assert nsp >= 1, "every stroke needs at least 4 control points"
+        k = np.arange(nsp * subdiv + 1)
+        span = np.minimum(k // subdiv, nsp - 1)
+        j = k - span * subdiv
+        dx, dy = p[1:, 0] - p[:-1, 0], p[1:, 1] - p[:-1, 1]
+        gap = np.power(np.sqrt(dx * dx + dy * dy), dtype(alpha)).astype(dtype)
+        t0 = np.zeros(len(k), dtype)
+        t1 = gap[span]
+        t2 = t1 + gap[span + 1]
+        t3 = t2 + gap[span + 2]
+        t = np.where(j == subdiv, t2, t1 + (t2 - t1) * (j.astype(dtype) / dtype(subdiv)))
+
+        def lerp(ta, tb, pa, pb):
+            return ((tb - t) / (tb - ta))[:, None] * pa + ((t - ta) / (tb - ta))[:, None] * pb
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a1, a2, a3 = lerp(t0, t1, p[span], p[span + 1]), lerp(t1, t2, p[span + 1], p[span + 2]), lerp(t2, t3, p[span + 2], p[span + 3])
+            b1, b2 = lerp(t0, t2, a1, a2), lerp(t1, t3, a2, a3)
+            pts = lerp(t1, t2, b1, b2)
+        ks, kj = span[:-1], j[:-1]
+        r = rad[ks + 1] + (rad[ks + 2] - rad[ks + 1]) * ((kj.astype(dtype) + dtype(0.5)) / dtype(subdiv))
+        out.append(np.concatenate([pts[:-1], pts[1:], r[:, None]], axis=1).astype(dtype))
+    return np.concatenate(out) if out else np.zeros((0, 5), dtype)
+
+
+def raster_segments_numpy(segs: np.ndarray, out_shape: Tuple[int, int], offset=(0, 0), out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``nb_raster_segments_u8`` in float64: pixel (Y, X) is stroke (0) iff the distance from (X - off_x, Y - off_y) to the closed
+    segment is <= r for some row; rows with a non-finite value or r < 0 draw nothing.  ``out`` given: darkened in place."""
+    h, w = out_shape
+    if out is None:
+        out = np.full((h, w), 255, np.uint8)
+    ys, xs = np.arange(h, dtype=np.float64) - offset[0], np.arange(w, dtype=np.float64) - offset[1]
+    for x0, y0, x1, y1, r in np.asarray(segs, np.float64)[:, :5]:
+        if not np.isfinite([x0, y0, x1, y1, r]).all() or r < 0:
+            continue
+        # the pixels of the segment's bounding box grown by r (and one more: the box is only a shortcut)
+        ia, ib = np.searchsorted(ys, min(y0, y1) - r - 1), np.searchsorted(ys, max(y0, y1) + r + 1, side="right")
+        ja, jb = np.searchsorted(xs, min(x0, x1) - r - 1), np.searchsorted(xs, max(x0, x1) + r + 1, side="right")
+        if ib <= ia or jb <= ja:
+            continue
+        dx, dy = xs[None, ja:jb] - x0, ys[ia:ib, None] - y0
+        ex, ey = x1 - x0, y1 - y0
+        ee = ex * ex + ey * ey
+        t = np.clip((dx * ex + dy * ey) / ee, 0.0, 1.0) if ee > 0 else 0.0
+        fx, fy = dx - t * ex, dy - t * ey
+        out[ia:ib, ja:jb][np.sqrt(fx * fx + fy * fy) - r <= 0] = 0
+    return out
+
+
+def raster_strokes_numpy(strokes: StrokeList, out_shape: Tuple[int, int], offset=(0, 0), subdiv: int = 8) -> np.ndarray:
+    """``TileOps.raster_strokes`` restated in numpy (float64 on the float32 stroke values): [h, w] uint8, 255 = background,
+    0 = stroke, drawing position (0, 0) at pixel ``offset`` = (off_y, off_x).  The route of an ``ops`` without the kernels."""
+    ctrl, off = strokes.spline_control()
+    segs = np.concatenate([strokes.polyline_segments()[:, :5].astype(np.float64), flatten_splines_numpy(ctrl, off, subdiv)])
+    return raster_segments_numpy(segs, out_shape, offset)
+
+
+# ------------------------------------------------------------------------------------------------
 # brush options (the subset of GanBrushOptions, brush.py:410-527, that the tiled path reads)
 # ------------------------------------------------------------------------------------------------
 class GanBrushOptions:
@@ -618,6 +803,49 @@ class TileOps(TileOpsBase):
             _lib.check(_lib.lib().nb_composite_on_white_u8(_p(canvas), ch, cw, y0, x0, h, w, _p(out), self._stream()),
                        "composite_on_white")
         return out
+
+    # -- vector strokes (csrc/nb_strokes.hip) --
+    spline_alpha = 0.5           # centripetal Catmull-Rom, the reference's default (curve.py:24)
+
+    def stroke_segments(self, strokes: StrokeList, subdiv: int = 8) -> torch.Tensor:
+        """[n, SEG_PITCH] float32 on the device: the polylines' segment rows (uploaded) followed by the splines' (control points
+        uploaded, cut into ``subdiv`` pieces per span by ``nb_spline_flatten_f32``).  Kilobytes cross PCIe."""
+        poly = strokes.polyline_segments()
+        ctrl, off = strokes.spline_control()
+        n_poly, n_spl = poly.shape[0], strokes.spline_segment_count(subdiv)
+        segs = torch.empty([n_poly + n_spl, SEG_PITCH], dtype=torch.float32, device=self.device)
+        if n_poly:
+            segs[:n_poly].copy_(torch.from_numpy(poly), non_blocking=True)
+        if n_spl:
+            d_ctrl, d_off = self.to_device(ctrl), self.to_device(off)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().nb_spline_flatten_f32(_p(d_ctrl), _p(d_off), ctrl.shape[0], len(off) - 1, int(subdiv),
+                                                            float(self.spline_alpha), _p(segs[n_poly:]), n_spl, self._stream()),
+                           "spline_flatten")
+        return segs
+
+    def raster_segments(self, segs: torch.Tensor, out_shape=None, offset=(0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``nb_raster_segments_u8`` on device segment rows [n, SEG_PITCH]: a new [out_h, out_w] uint8 geometry (255 = background,
+        0 = stroke), or, with ``out`` given, the strokes darkened onto that tensor and everything else left as it is."""
+        if segs.dtype != torch.float32 or segs.dim() != 2 or segs.shape[1] != SEG_PITCH or not segs.is_contiguous():
+            raise ValueError(f"raster_segments: contiguous float32 [n, {SEG_PITCH}] expected, got {segs.dtype} {tuple(segs.shape)}")
+        clear = out is None
+        if clear:
+            out = torch.empty([int(out_shape[0]), int(out_shape[1])], dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.dim() != 2 or not out.is_contiguous() or out.device != segs.device:
+            raise ValueError(f"raster_segments: out must be a contiguous uint8 [H,W] device tensor, got {out.dtype} {tuple(out.shape)}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_raster_segments_u8(_p(segs) if segs.shape[0] else None, segs.shape[0], _p(out), out.shape[0],
+                                                        out.shape[1], int(offset[0]), int(offset[1]), int(clear), self._stream()),
+                       "raster_segments")
+        return out
+
+    def raster_strokes(self, strokes: StrokeList, out_shape=None, offset=(0, 0), out: Optional[torch.Tensor] = None,
+                       subdiv: int = 8) -> torch.Tensor:
+        """The strokes as [out_h, out_w] uint8 geometry on the device (255 = background, 0 = stroke), drawing position (0, 0) at
+        pixel ``offset`` = (off_y, off_x): splines are flattened on the device, and polyline and spline segments are rasterised in
+        one ``nb_raster_segments_u8`` launch.  ``out`` given: the strokes are added to that geometry (every other byte untouched)."""
+        return self.raster_segments(self.stroke_segments(strokes, subdiv), out_shape, offset, out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1108,6 +1336,14 @@ class PaintingHelper:
         h0, w0 = img.shape[:2]
         nrows, ncols, stride, ph, pw = stitching_grid(h0 + m, w0 + m, R, 2 * m)
         padded = ops.prepare_geometry(img, (ph, pw), (m, m))
+        return self._paint_padded(padded, (h0, w0), (nrows, ncols, stride), opts, m, stitching_mode, on_white, return_full)
+
+    def _paint_padded(self, padded: torch.Tensor, size_hw, grid, opts: GanBrushOptions, m: int, stitching_mode: str, on_white: bool,
+                      return_full: bool):
+        """The device route behind the padded geometry [ph, pw] uint8 (the drawing at (m, m), 255 around it): tile picks, the
+        schedule, crop / composite on white."""
+        ops, R = self.ops, self.patch_width
+        (h0, w0), (nrows, ncols, stride), (ph, pw) = size_hw, grid, padded.shape
         if stitching_mode == "all":
             keep = np.ones((nrows, ncols), bool)
         else:
@@ -1125,3 +1361,26 @@ class PaintingHelper:
         if not return_full:
             return out
         return out, ops.to_host(canvas), crops, ops.to_host(padded)[..., None]
+
+    def paint_strokes(self, strokes: StrokeList, size_hw, opts: GanBrushOptions, crop_margin: int = 10, stitching_mode: str = "all",
+                      on_white: bool = False, return_full: bool = False, subdiv: int = 8):
+        """``paint_drawing`` from strokes instead of a raster: the strokes of a [h, w] = ``size_hw`` drawing (``StrokeList``: points and
+        radii, kilobytes) are uploaded, splines are cut into segments and all segments rasterised straight into the padded geometry on
+        the device (``nb_spline_flatten_f32``, ``nb_raster_segments_u8``); tile picks, schedule, crop and on-white follow as in
+        ``paint_drawing``.  Strokes are clipped to the drawing: the padding around it stays background.  Same bytes as
+        ``paint_image`` on the rasterised strokes.  An ``ops`` without the kernels (the CPU stand-ins of the tests) takes the numpy
+        restatement.  Every rank of a sharded run rasterises the stroke list itself."""
+        ops, R, m = self.ops, self.patch_width, int(crop_margin)
+        h0, w0 = int(size_hw[0]), int(size_hw[1])
+        if h0 < 1 or w0 < 1:
+            raise ValueError(f"paint_strokes: bad canvas size {size_hw}")
+        if not all(hasattr(ops, k) for k in ("raster_strokes", "stroke_counts", "composite_on_white")):
+            return self.paint_image(raster_strokes_numpy(strokes, (h0, w0), (0, 0), subdiv), opts, crop_margin=crop_margin,
+                                    stitching_mode=stitching_mode, on_white=on_white, return_full=return_full)
+        nrows, ncols, stride, ph, pw = stitching_grid(h0 + m, w0 + m, R, 2 * m)
+        padded = ops.raster_strokes(strokes, (ph, pw), (m, m), subdiv=subdiv)
+        padded[:m].fill_(255)                                 # the padding is background, whatever the strokes reach
+        padded[m + h0:].fill_(255)
+        padded[:, :m].fill_(255)
+        padded[:, m + w0:].fill_(255)
+        return self._paint_padded(padded, (h0, w0), (nrows, ncols, stride), opts, m, stitching_mode, on_white, return_full)

@@ -544,6 +544,48 @@ int nb_composite_on_white_u8(const uint8_t* canvas, int ch, int cw, int y0, int 
 int nb_stitching_grid(int h, int w, int patch_width, int overlap_margin, int* nrows, int* ncols, int* stride, int* padded_h,
                       int* padded_w);
 
+/* ---- vector strokes: polylines and splines rasterised into the geometry on the device (csrc/nb_strokes.hip) -----------------------
+ * The route from stroke points to the padded geometry without a raster on the host: what drawing the strokes into an image, then
+ * _read_any_geo and the padding of forger/viz/paint_image_main.py:30-61 would produce, with nothing the size of the canvas uploaded.
+ * Coordinates: drawing coordinates are (x, y) in pixels, pixel (row y, column x) has its centre at exactly (x, y), and pixel (Y, X)
+ * of an output buffer is the drawing position (X - off_x, Y - off_y).  A segment row is NB_SEG_PITCH = 8 floats (32 bytes):
+ * x0, y0, x1, y1, r and three reserved floats (ignored by the rasteriser, written as zeros by the flattener).  Both device entries
+ * only enqueue on `stream` (no allocation, no synchronisation, no read-back: they can be captured into a hipGraph), validate on the
+ * host before any launch and never dereference their pointers on the host. */
+#define NB_SEG_PITCH 8
+
+/* out [out_h,out_w] uint8 geometry (255 = background, 0 = stroke; any alignment, any width): a pixel is stroke iff the distance from
+ * its centre to the closed segment (x0,y0)-(x1,y1) is <= r for some of the n_segs rows of segs (device fp32, 16-byte aligned).  A row
+ * with equal end points is a disc; a row in which one of the five values is not finite, or r < 0, draws nothing.  clear = 1: every
+ * byte of out is written (255 where no stroke); clear = 0: only stroke pixels are written, as 0, and every other byte keeps its
+ * value (more strokes on a prepared drawing).  n_segs = 0 is legal (segs may then be NULL): with clear = 1 it fills 255.  The result
+ * is a union: independent of the order of the rows, bit-identical from run to run.  Arithmetic: fp32, unfused, distances relative to
+ * the segment's first point (differences first): within ~1e-4 px of the exact distance on canvases up to 8192.
+ * Cost: one workgroup per 64 x 64 pixels of out, each reading all rows (ceil(out_h / 64) * ceil(out_w / 64) * n_segs box tests).
+ * NB_EINVAL: a null pointer, n_segs < 0, non-positive sizes, out_h * out_w >= 2^31, clear other than 0 / 1, unaligned segs. */
+int nb_raster_segments_u8(const float* segs, int n_segs, uint8_t* out, int out_h, int out_w, int off_y, int off_x, int clear,
+                          void* stream);
+
+/* Centripetal Catmull-Rom strokes cut into segment rows: the curve of forger/core/curve.py (knots ts = cumsum(|dP|^alpha), lines
+ * 24-37; a point by the pyramid A1..A3 -> B1, B2 -> C of sample_t_one, lines 50-85).  ctrl [n_points_total][3] device fp32 (x, y, r
+ * per control point), stroke_off [n_strokes + 1] device int32 offsets into ctrl (stroke_off[0] = 0, stroke_off[n_strokes] =
+ * n_points_total, every stroke >= 4 points).  Like the reference's, the curve of a stroke with P points runs from its control point 1
+ * to its control point P - 2: P - 3 spans, each cut into subdiv pieces uniform in t.  Every sample point is evaluated once and
+ * written as the end of one segment and the start of the next (bit-equal: watertight polylines); a segment's radius is its span's two
+ * control radii interpolated linearly at the piece's mid t.  Stroke s starts at row (stroke_off[s] - 3 s) * subdiv of segs (closed
+ * form: no scan, no atomics); nb_spline_segment_count rows are written in all.  A span next to a repeated control point has a zero
+ * knot interval and yields non-finite rows, which nb_raster_segments_u8 does not draw (drop consecutive duplicates beforehand).
+ * stroke_off is read on the device only: the capacity check uses the totals passed here, and a table that disagrees with them (an
+ * offset outside 0..n_points_total, a stroke of fewer than 4 points) makes the kernel skip that stroke, never write outside segs.
+ * NB_EINVAL: a null pointer, n_strokes < 1, subdiv < 1, n_points_total < 4 * n_strokes, alpha outside [0, 1], seg_capacity (rows)
+ * below the count, unaligned segs. */
+int nb_spline_flatten_f32(const float* ctrl, const int32_t* stroke_off, int n_points_total, int n_strokes, int subdiv, float alpha,
+                          float* segs, int seg_capacity, void* stream);
+
+/* (n_points_total - 3 * n_strokes) * subdiv: the segment rows nb_spline_flatten_f32 writes (HOST ONLY: no HIP call, works without a
+ * GPU).  NB_EINVAL (negative) for n_strokes < 0, subdiv < 1 or n_points_total < 4 * n_strokes. */
+long long nb_spline_segment_count(int n_points_total, int n_strokes, int subdiv);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
