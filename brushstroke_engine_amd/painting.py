@@ -360,6 +360,80 @@ def raster_strokes_numpy(strokes: StrokeList, out_shape: Tuple[int, int], offset
 
 
 # ------------------------------------------------------------------------------------------------
+# compositing (csrc/nb_compose.hip): the two contracts of include/neube_hip.h restated in int64
+# ------------------------------------------------------------------------------------------------
+COMPOSE_MODES = {"paint": 0, "erase": 1}
+
+
+def cell_box(box, h: int, w: int) -> Optional[Tuple[int, int, int, int]]:
+    """(cell_x0, cell_y0, cells_x, cells_y): the cells of an h x w canvas that the pixel box (y0, x0, y1, x1; end-exclusive) touches,
+    the whole canvas for None; None if the box misses the canvas."""
+    if box is None:
+        box = (0, 0, h, w)
+    y0, x0 = max(0, int(box[0])) // CELL_H, max(0, int(box[1])) // CELL_W
+    y1, x1 = -(-min(h, int(box[2])) // CELL_H), -(-min(w, int(box[3])) // CELL_W)
+    if y1 <= y0 or x1 <= x0:
+        return None
+    return x0, y0, x1 - x0, y1 - y0
+
+
+def over_tiles_numpy(canvas: np.ndarray, tiles: np.ndarray, dst_yx, crop: int, mode: int = 0, opacity: int = 255,
+                     cells: Optional[Tuple[int, int, int, int]] = None) -> np.ndarray:
+    """``nb_over_tiles_u8`` in int64, in place on ``canvas`` [h,w,4] uint8 (returned): per pixel the LAST of ``tiles`` [t,r,r,4]
+    whose interior ``[crop, r-crop)^2`` at ``dst_yx[i] + crop`` covers it goes over (mode 0) or out of (mode 1) the pixel; only
+    inside ``cells`` = (cell_x0, cell_y0, cells_x, cells_y), the whole canvas for None."""
+    if mode not in (0, 1) or not 0 <= int(opacity) <= 255:
+        raise ValueError(f"over_tiles: bad mode {mode} or opacity {opacity}")
+    h, w = canvas.shape[:2]
+    tiles = np.asarray(tiles)
+    r, m = tiles.shape[1], int(crop)
+    src = np.zeros((h, w, 4), np.uint8)
+    cov = np.zeros((h, w), bool)
+    for i, (y, x) in enumerate(np.asarray(dst_yx).reshape(-1, 2).tolist()):       # ascending: a later tile replaces an earlier one
+        y0, x0, y1, x1 = max(0, y + m), max(0, x + m), min(h, y + r - m), min(w, x + r - m)
+        if y1 > y0 and x1 > x0:
+            src[y0:y1, x0:x1] = tiles[i, y0 - y:y1 - y, x0 - x:x1 - x]
+            cov[y0:y1, x0:x1] = True
+    if cells is not None:
+        inside = np.zeros((h, w), bool)
+        inside[cells[1] * CELL_H:(cells[1] + cells[3]) * CELL_H, cells[0] * CELL_W:(cells[0] + cells[2]) * CELL_W] = True
+        cov &= inside
+    s, d = src[cov].astype(np.int64), canvas[cov].astype(np.int64)
+    ae = (s[:, 3] * int(opacity) + 127) // 255
+    t = d[:, 3] * (255 - ae)
+    out = d.copy()
+    if mode == 1:
+        out[:, 3] = (t + 127) // 255
+    else:
+        den = ae * 255 + t
+        out[:, 3] = (den + 127) // 255
+        num = s[:, :3] * (ae * 255)[:, None] + d[:, :3] * t[:, None] + (den // 2)[:, None]
+        out[:, :3] = np.where(den[:, None] > 0, num // np.maximum(den, 1)[:, None], 0)
+    canvas[cov] = out.astype(np.uint8)
+    return canvas
+
+
+def canvas_view_numpy(canvas: np.ndarray, y0: int, x0: int, h: int, w: int, k: int = 1, on_white: bool = False) -> np.ndarray:
+    """``nb_canvas_view_u8`` in int64: the window of ``canvas`` [ch,cw,4] uint8 reduced by ``k`` -> [ceil(h/k), ceil(w/k), 4 | 3]."""
+    ch, cw = canvas.shape[:2]
+    if not (1 <= int(k) <= 16 and h >= 1 and w >= 1 and y0 >= 0 and x0 >= 0 and y0 + h <= ch and x0 + w <= cw):
+        raise ValueError(f"canvas_view: bad factor {k} or window {h} x {w} at ({y0}, {x0}) of a {ch} x {cw} canvas")
+    win = canvas[y0:y0 + h, x0:x0 + w].astype(np.int64)
+    ys, xs = np.arange(0, h, k), np.arange(0, w, k)
+
+    def blocks(a):
+        return np.add.reduceat(np.add.reduceat(a, ys, axis=0), xs, axis=1)
+    sa = blocks(win[..., 3])
+    sc = blocks(win[..., :3] * win[..., 3:])
+    n = np.outer(np.minimum(k, h - ys), np.minimum(k, w - xs))
+    if on_white:
+        den = (255 * n)[..., None]
+        return ((sc + 255 * (den - sa[..., None]) + den // 2) // den).astype(np.uint8)
+    colour = np.where(sa[..., None] > 0, (sc + (sa // 2)[..., None]) // np.maximum(sa, 1)[..., None], 0)
+    return np.concatenate([colour, ((sa + n // 2) // n)[..., None]], axis=2).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------
 # brush options (the subset of GanBrushOptions, brush.py:410-527, that the tiled path reads)
 # ------------------------------------------------------------------------------------------------
 class GanBrushOptions:
@@ -450,6 +524,19 @@ class TileOpsBase:
 
     def to_host(self, t: torch.Tensor) -> np.ndarray:
         return t.cpu().numpy()
+
+    # -- compositing: the numpy restatements, on host tensors (``TileOps`` runs the kernels of csrc/nb_compose.hip) --
+    def over_tiles(self, canvas, tiles_u8, dst_yx, crop, cell_off, cell_tiles, box=None, mode: int = 0, opacity: int = 255) -> None:
+        """``tiles_u8`` [t,r,r,4] over (mode 0) or out of (mode 1) ``canvas`` [h,w,4], in place, inside the cells that the pixel box
+        (y0, x0, y1, x1) touches (None: everywhere).  The cell lists are those of ``paste``."""
+        h, w = canvas.shape[:2]
+        cells = cell_box(box, h, w)
+        if cells is not None:
+            over_tiles_numpy(canvas.numpy(), tiles_u8.numpy(), dst_yx.numpy(), crop, mode, opacity, cells)
+
+    def canvas_view(self, canvas, y0: int, x0: int, h: int, w: int, k: int = 1, on_white: bool = False) -> torch.Tensor:
+        """[ceil(h/k), ceil(w/k), 4 | 3] uint8: the window of the RGBA canvas at (y0, x0) reduced by ``k``."""
+        return torch.from_numpy(canvas_view_numpy(canvas.numpy(), y0, x0, h, w, k, on_white))
 
 
 class TileOps(TileOpsBase):
@@ -804,6 +891,31 @@ class TileOps(TileOpsBase):
                        "composite_on_white")
         return out
 
+    # -- compositing (csrc/nb_compose.hip) --
+    def over_tiles(self, canvas, tiles_u8, dst_yx, crop, cell_off, cell_tiles, box=None, mode: int = 0, opacity: int = 255) -> None:
+        """``tiles_u8`` [t,r,r,4] over (mode 0) or out of (mode 1) ``canvas`` [h,w,4], in place, inside the cells that the pixel box
+        (y0, x0, y1, x1) touches (None: everywhere).  The cell lists are those of ``paste`` (``nb_over_tiles_u8``)."""
+        t, r = tiles_u8.shape[0], tiles_u8.shape[1]
+        h, w = canvas.shape[:2]
+        cells = cell_box(box, h, w)
+        if cells is None:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_over_tiles_u8(_p(tiles_u8), t, r, _p(dst_yx), crop, _p(canvas), h, w, _p(cell_off), _p(cell_tiles),
+                                                   *cells, int(mode), int(opacity), self._stream()), "over_tiles")
+
+    def canvas_view(self, canvas, y0: int, x0: int, h: int, w: int, k: int = 1, on_white: bool = False) -> torch.Tensor:
+        """[ceil(h/k), ceil(w/k), 4 | 3] uint8: the window of the RGBA canvas at (y0, x0) reduced by ``k`` (``nb_canvas_view_u8``)."""
+        ch, cw = canvas.shape[:2]
+        k = int(k)
+        if not 1 <= k <= 16:
+            raise ValueError(f"canvas_view: factor {k} outside 1..16")
+        out = torch.empty([-(-int(h) // k), -(-int(w) // k), 3 if on_white else 4], dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_canvas_view_u8(_p(canvas), ch, cw, int(y0), int(x0), int(h), int(w), k, int(bool(on_white)), _p(out),
+                                                    self._stream()), "canvas_view")
+        return out
+
     # -- vector strokes (csrc/nb_strokes.hip) --
     spline_alpha = 0.5           # centripetal Catmull-Rom, the reference's default (curve.py:24)
 
@@ -884,6 +996,15 @@ class StyleUVSMapper:
         if opts.style_id is not None:
             self.sfactors[opts.style_id] = sfactor
         return sfactor
+
+
+def _on_white_torch(ops, rgba: torch.Tensor) -> torch.Tensor:
+    """paint_image_main.py:179-183 as a torch expression (3 channels out): what ``nb_composite_on_white_u8`` computes, for an
+    ``ops`` without that kernel."""
+    # alpha = a / 255 through a host-computed table: device division is not correctly rounded
+    lut = ops.to_device(np.arange(256, dtype=np.float32) / np.float32(255))
+    a = lut[rgba[..., 3:].to(torch.int64)]
+    return (rgba[..., :3].to(torch.float32) * a + 255 * (1 - a)).clip(0, 255).to(torch.uint8)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1309,11 +1430,8 @@ class PaintingHelper:
         m, (h0, w0) = crop_margin, geom.shape[:2]
         to_host = self.ops.to_host
         result = canvas[m:m + h0, m:m + w0]                          # crop on the device: only the answer crosses PCIe
-        if on_white:                                                # paint_image_main.py:179-183 (3 channels out)
-            # alpha = a / 255 through a host-computed table: device division is not correctly rounded
-            lut = self.ops.to_device(np.arange(256, dtype=np.float32) / np.float32(255))
-            a = lut[result[..., 3:].to(torch.int64)]
-            result = (result[..., :3].to(torch.float32) * a + 255 * (1 - a)).clip(0, 255).to(torch.uint8)
+        if on_white:
+            result = _on_white_torch(self.ops, result)
         out = to_host(result.contiguous())
         if not return_full:
             return out
@@ -1384,3 +1502,165 @@ class PaintingHelper:
         padded[:, :m].fill_(255)
         padded[:, m + w0:].fill_(255)
         return self._paint_padded(padded, (h0, w0), (nrows, ncols, stride), opts, m, stitching_mode, on_white, return_full)
+
+
+# ------------------------------------------------------------------------------------------------
+# the paint session: a canvas that stays on the device, strokes added one call at a time, each with its own brush
+# ------------------------------------------------------------------------------------------------
+EMPTY_BOX = (0, 0, 0, 0)
+
+
+def strokes_bounds(strokes: StrokeList, subdiv: int = 8) -> Optional[Tuple[int, int, int, int]]:
+    """(y0, x0, y1, x1), end-exclusive, in drawing pixels: a box around every pixel the strokes can cover, from their points and
+    radii on the host -- the polylines' segment rows and the splines' (a Catmull-Rom curve leaves the hull of its control points, so
+    they are flattened here in float64), grown by the radius and one pixel for the device's fp32 flattening.  None: nothing to draw."""
+    ctrl, off = strokes.spline_control()
+    rows = np.concatenate([strokes.polyline_segments()[:, :5].astype(np.float64), flatten_splines_numpy(ctrl, off, subdiv)])
+    rows = rows[np.isfinite(rows).all(axis=1) & (rows[:, 4] >= 0)]
+    if rows.shape[0] == 0:
+        return None
+    grow = rows[:, 4] + 1
+    x0, x1 = (np.minimum(rows[:, 0], rows[:, 2]) - grow).min(), (np.maximum(rows[:, 0], rows[:, 2]) + grow).max()
+    y0, y1 = (np.minimum(rows[:, 1], rows[:, 3]) - grow).min(), (np.maximum(rows[:, 1], rows[:, 3]) + grow).max()
+    lim = float(1 << 30)
+    y0, x0, y1, x1 = (int(np.floor(np.clip(v, -lim, lim))) for v in (y0, x0, y1, x1))
+    return y0, x0, y1 + 1, x1 + 1
+
+
+class PaintSession:
+    """What a paint program does with the engine: a RGBA canvas that stays on the device, onto which every ``add`` renders a few
+    strokes with their own brush and colours and composites them over (or erases with them) what is already there.  Only the tiles the
+    strokes touch are rendered, and the caller fetches only what it wants to look at (``view``, ``image``).
+
+    The canvas has the frame of ``paint_strokes``: the padded size of ``stitching_grid(h0 + m, w0 + m, R, 2 m)`` with the drawing at
+    (m, m), so tiles sit on the same grid and get the same noise positions, and one ``add`` on an empty canvas leaves what
+    ``paint_strokes(..., stitching_mode="stroke")`` paints.  Feature blending works among the tiles of one call; the reference's one
+    feature canvas across all strokes of a session remains what ``render_stroke`` offers.  Single process, like ``render_stroke``.
+
+    In the reference this is split between the server (rendering) and the browser client, which writes the returned patches into a
+    foreground layer and draws that layer over the background canvas when the stroke ends (main_controller.js:776, 131-141)."""
+
+    def __init__(self, helper: "PaintingHelper", size_hw, crop_margin: int = 10, undo_depth: int = 8):
+        import collections
+        _, world = helper._world()
+        if helper._sharded(world):
+            raise RuntimeError("PaintSession runs in a single process (a sharded helper paints whole drawings: paint_strokes)")
+        h0, w0, m = int(size_hw[0]), int(size_hw[1]), int(crop_margin)
+        if h0 < 1 or w0 < 1 or m < 0 or int(undo_depth) < 0:
+            raise ValueError(f"PaintSession: bad size {size_hw}, crop margin {crop_margin} or undo depth {undo_depth}")
+        self.helper, self.ops, self.size_hw, self.crop_margin = helper, helper.ops, (h0, w0), m
+        self.grid = stitching_grid(h0 + m, w0 + m, helper.patch_width, 2 * m)       # (nrows, ncols, stride, padded_h, padded_w)
+        ph, pw = self.grid[3:]
+        self.canvas = torch.zeros([ph, pw, 4], dtype=torch.uint8, device=self.ops.device)
+        helper.make_new_canvas(ph, pw)
+        self._undo = collections.deque(maxlen=int(undo_depth))                      # (canvas box, the bytes it held)
+        self._mask_seen, self._mask_rect = None, None                               # the helper's feature mask as the last add left it
+        self.last_tiles = 0                                                         # tiles the last add rendered
+
+    def _drawing_box(self, box) -> Tuple[int, int, int, int]:
+        """A canvas box in drawing coordinates, clipped to the drawing."""
+        m, (h0, w0) = self.crop_margin, self.size_hw
+        y0, x0, y1, x1 = max(0, box[0] - m), max(0, box[1] - m), min(h0, box[2] - m), min(w0, box[3] - m)
+        return (y0, x0, y1, x1) if y1 > y0 and x1 > x0 else EMPTY_BOX
+
+    def _reset_feature_mask(self) -> None:
+        """Feature blending is per call: un-set the feature mask where the previous add set it.  The features stay -- the replay never
+        reads a feature whose mask bit is 0 -- and so does the allocation."""
+        helper = self.helper
+        ph, pw = self.grid[3:]
+        if (helper.rows, helper.cols) != (ph, pw):              # the helper has painted something else in between
+            helper.make_new_canvas(ph, pw)
+        elif helper.mask is not None:
+            if helper.mask is self._mask_seen and self._mask_rect is not None:
+                y0, x0, y1, x1 = self._mask_rect
+                helper.mask[y0:y1, x0:x1].zero_()
+            else:
+                helper.mask.zero_()
+        self._mask_seen = self._mask_rect = None
+
+    def add(self, strokes: StrokeList, opts: GanBrushOptions, mode: str = "paint", opacity: int = 255, subdiv: int = 8):
+        """Render ``strokes`` with the brush of ``opts`` and composite them into the canvas: ``mode`` "paint" (source-over) or "erase"
+        (destination-out by the rendered strokes' alpha), ``opacity`` 0..255 on top of the strokes' own alpha.  Returns the dirty box
+        (y0, x0, y1, x1), end-exclusive, in drawing coordinates; a call that renders no tile (strokes outside the drawing, or at most
+        10 stroke pixels per tile) changes nothing, saves no undo entry and returns ``EMPTY_BOX``."""
+        if mode not in COMPOSE_MODES:
+            raise ValueError(f"PaintSession.add: mode {mode!r} is neither 'paint' nor 'erase'")
+        if int(opacity) != opacity or not 0 <= int(opacity) <= 255:
+            raise ValueError(f"PaintSession.add: opacity {opacity!r} outside 0..255")
+        helper, ops, R, m = self.helper, self.ops, self.helper.patch_width, self.crop_margin
+        (h0, w0), (nrows, ncols, stride, ph, pw) = self.size_hw, self.grid
+        self.last_tiles = 0
+        bounds = strokes_bounds(strokes, subdiv)
+        if bounds is None:
+            return EMPTY_BOX
+        by0, bx0, by1, bx1 = max(0, bounds[0]), max(0, bounds[1]), min(h0, bounds[2]), min(w0, bounds[3])
+        if by1 <= by0 or bx1 <= bx0:
+            return EMPTY_BOX
+        # the tiles of the stitching grid whose window [row * stride, row * stride + R) meets the box (canvas = drawing + m)
+        r0, r1 = max(0, -(-(by0 + m - R + 1) // stride)), min(nrows - 1, (by1 + m - 1) // stride)
+        c0, c1 = max(0, -(-(bx0 + m - R + 1) // stride)), min(ncols - 1, (bx1 + m - 1) // stride)
+        nr, nc, gy0, gx0 = r1 - r0 + 1, c1 - c0 + 1, r0 * stride, c0 * stride
+        # this call's strokes alone, in a scratch geometry over just those tiles; the padding around the drawing stays background
+        sh, sw = (nr - 1) * stride + R, (nc - 1) * stride + R
+        top, bottom = min(sh, max(0, m - gy0)), min(sh, max(0, m + h0 - gy0))
+        left, right = min(sw, max(0, m - gx0)), min(sw, max(0, m + w0 - gx0))
+        if hasattr(ops, "raster_strokes") and hasattr(ops, "stroke_counts"):
+            geom = ops.raster_strokes(strokes, (sh, sw), (m - gy0, m - gx0), subdiv=subdiv)
+            for pad in (geom[:top], geom[bottom:], geom[:, :left], geom[:, right:]):
+                pad.fill_(255)
+            counts = ops.to_host(ops.stroke_counts(geom, R, stride, nr, nc))
+        else:
+            g = raster_strokes_numpy(strokes, (sh, sw), (m - gy0, m - gx0), subdiv)
+            for pad in (g[:top], g[bottom:], g[:, :left], g[:, right:]):
+                pad[...] = 255
+            counts = np.array([[int((g[r * stride:r * stride + R, c * stride:c * stride + R] == 0).sum()) for c in range(nc)]
+                               for r in range(nr)])
+            geom = ops.to_device(g)
+        geom_yx = np.argwhere(counts > 10).astype(np.int64) * stride       # row-major: the order of generate_stitching_crops
+        if geom_yx.shape[0] == 0:
+            return EMPTY_BOX
+        self.last_tiles = geom_yx.shape[0]
+        crops = geom_yx + np.array([gy0, gx0], np.int64)
+        df = helper.down_factor
+        floored = crops if helper.feature_blending_level == 0 else (crops // df) * df
+        self._reset_feature_mask()
+        rgba = helper._schedule(geom, geom_yx, floored, crops, opts, m)
+        if helper.feature_blending_level > 0:
+            a, bres = floored // df, R // df
+            self._mask_seen = helper.mask
+            self._mask_rect = (int(a[:, 0].min()), int(a[:, 1].min()), int(a[:, 0].max()) + bres, int(a[:, 1].max()) + bres)
+        rects = np.concatenate([floored + m, floored + R - m], axis=1)     # the interiors: what the paste of render_tiles writes
+        box = (max(0, int(rects[:, 0].min())), max(0, int(rects[:, 1].min())), min(ph, int(rects[:, 2].max())), min(pw, int(rects[:, 3].max())))
+        self._undo.append((box, self.canvas[box[0]:box[2], box[1]:box[3]].clone()))
+        off, lst = build_cells(rects, ph, pw)
+        ops.over_tiles(self.canvas, rgba, ops.to_device(floored.astype(np.int32)), m, ops.to_device(off), ops.to_device(lst), box=box,
+                       mode=COMPOSE_MODES[mode], opacity=int(opacity))
+        return self._drawing_box(box)
+
+    def undo(self) -> Tuple[int, int, int, int]:
+        """Put back what the last ``add`` that is still remembered (``undo_depth``) painted over; returns its dirty box, ``EMPTY_BOX``
+        when there is nothing to undo."""
+        if not self._undo:
+            return EMPTY_BOX
+        box, saved = self._undo.pop()
+        self.canvas[box[0]:box[2], box[1]:box[3]].copy_(saved)
+        return self._drawing_box(box)
+
+    def view(self, box=None, k: int = 1, on_white: bool = False) -> np.ndarray:
+        """The part (y0, x0, y1, x1) of the drawing (None: all of it) reduced by the integer factor ``k`` in 1..16, as numpy
+        [ceil(h/k), ceil(w/k), 4] RGBA or [.., 3] over white: alpha-weighted means (``canvas_view``).  The preview path -- only the
+        reduced window crosses PCIe; ``image`` is the exported result."""
+        m, (h0, w0) = self.crop_margin, self.size_hw
+        y0, x0, y1, x1 = (0, 0, h0, w0) if box is None else (max(0, int(box[0])), max(0, int(box[1])), min(h0, int(box[2])), min(w0, int(box[3])))
+        if y1 <= y0 or x1 <= x0:
+            raise ValueError(f"PaintSession.view: the box {box} misses the {h0} x {w0} drawing")
+        return self.ops.to_host(self.ops.canvas_view(self.canvas, y0 + m, x0 + m, y1 - y0, x1 - x0, k, on_white))
+
+    def image(self, on_white: bool = False) -> np.ndarray:
+        """The drawing-sized result, as ``paint_strokes`` returns it: [h0, w0, 4] RGBA, or [h0, w0, 3] composited on white."""
+        ops, m, (h0, w0) = self.ops, self.crop_margin, self.size_hw
+        if not on_white:
+            return ops.to_host(self.canvas[m:m + h0, m:m + w0].contiguous())
+        if hasattr(ops, "composite_on_white"):
+            return ops.to_host(ops.composite_on_white(self.canvas, m, m, h0, w0))
+        return ops.to_host(_on_white_torch(ops, self.canvas[m:m + h0, m:m + w0]))

@@ -586,6 +586,46 @@ int nb_spline_flatten_f32(const float* ctrl, const int32_t* stroke_off, int n_po
  * GPU).  NB_EINVAL (negative) for n_strokes < 0, subdiv < 1 or n_points_total < 4 * n_strokes. */
 long long nb_spline_segment_count(int n_points_total, int n_strokes, int subdiv);
 
+/* ---- compositing for a paint session: tiles over a canvas, a reduced view of a window (csrc/nb_compose.hip) ----------------------
+ * What the reference leaves to its browser client -- the patches of a stroke written into a foreground layer with putImageData
+ * (forger/ui/js/main_controller.js:776) and that layer drawn over the background canvas when the stroke ends
+ * (main_controller.js:131-141) -- on a canvas that stays on the device.  RGBA8 with straight (unpremultiplied) alpha; all of it is
+ * integer arithmetic with floor division, so a restatement in integers matches byte for byte (painting.over_tiles_numpy,
+ * painting.canvas_view_numpy).  Both entries only enqueue on `stream` (no allocation, no synchronisation: they can be captured into
+ * a hipGraph) and validate on the host before any launch; all pointers are device pointers, canvases and tiles 4-byte aligned.  A
+ * canvas that is 16-byte aligned with a width that is a multiple of 4 pixels is read and written in 16-byte vectors. */
+
+/* RGBA8 tiles [t,r,r,4] composited onto canvas [h,w,4] in place.  Tile selection is that of nb_paste_tiles_u8: the source of a
+ * canvas pixel is the LAST tile i whose interior [crop, r-crop)^2, placed at dst_yx[i] + crop, covers it (origins may be negative,
+ * tiles may hang over the canvas); cell_off / cell_tiles are the cell lists of the interior rectangles over the canvas.  Only the
+ * cells [cell_y0, cell_y0 + cells_y) x [cell_x0, cell_x0 + cells_x) run: a pixel that no interior covers keeps its four bytes, and
+ * so does every pixel outside that box.  With source (cs, as), destination (cd, ad) and opacity in 0..255:
+ *   ae = (as * opacity + 127) / 255
+ *   mode 0 (paint, source-over):   t = ad * (255 - ae);  den = ae * 255 + t;
+ *                                  alpha = (den + 127) / 255;  colour = den > 0 ? (cs * ae * 255 + cd * t + den / 2) / den : 0
+ *   mode 1 (erase, destination-out by the rendered stroke's alpha):
+ *                                  alpha = (ad * (255 - ae) + 127) / 255;  colour = cd
+ * The colour of mode 0 is the integer nearest to the exact quotient, ties rounded up; a transparent destination yields (cs, ae), a
+ * transparent source leaves the alpha as it was; the largest intermediate is 16 613 887.
+ * NB_EINVAL: a null pointer, non-positive sizes, 2 * crop >= r, a mode other than 0 / 1, an opacity outside 0..255, a cell box that
+ * is empty or leaves the canvas's cells, h * w >= 2^31, unaligned tiles or canvas. */
+int nb_over_tiles_u8(const uint8_t* tiles, int t, int r, const int32_t* dst_yx, int crop, uint8_t* canvas, int h, int w,
+                     const int32_t* cell_off, const int32_t* cell_tiles, int cell_x0, int cell_y0, int cells_x, int cells_y,
+                     int mode, int opacity, void* stream);
+
+/* The window [y0, y0 + h) x [x0, x0 + w) of canvas [ch,cw,4] reduced by the integer factor k in 1..16: out is
+ * [ceil(h / k), ceil(w / k), 4] RGBA8 (4-byte aligned), or [.., 3] RGB8 over white with on_white = 1.  Every k x k block is clipped to
+ * the window and n is the number of pixels left in it; with SA = sum of a and SC = sum of c * a (per channel) over the block:
+ *   on_white 0:   alpha = (SA + n / 2) / n;  colour = SA > 0 ? (SC + SA / 2) / SA : 0
+ *   on_white 1:   colour = (SC + 255 * (255 * n - SA) + (255 * n) / 2) / (255 * n)
+ * (alpha-weighted means, rounded half up; the sums stay below 2^25 at k = 16).  This is the PREVIEW path -- a large canvas reduced
+ * before it crosses PCIe; at k = 1 with on_white = 1 it rounds to nearest where nb_composite_on_white_u8 truncates the reference's
+ * fp32 expression, so the exported image keeps nb_composite_on_white_u8.
+ * NB_EINVAL: a null pointer, non-positive sizes, k outside 1..16, on_white other than 0 / 1, a window that leaves the canvas,
+ * ch * cw >= 2^31, an unaligned canvas (or RGBA out). */
+int nb_canvas_view_u8(const uint8_t* canvas, int ch, int cw, int y0, int x0, int h, int w, int k, int on_white, uint8_t* out,
+                      void* stream);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
