@@ -251,7 +251,13 @@ int nb_modconv3x3_variant(int n, int h, int w, int c_out, int up, char* buf, int
  * Activation format H2: _Float16 [n][ceil(c/8)][2 (hi,lo)][h][w][8], ALREADY multiplied by the consuming
  * layer's styles.  Weight format: produced by nb_pack_conv_weight_h3 (static, not modulated). */
 
-/* fp32 NCHW (x1 [n,c1,hw] ++ x2 [n,c2,hw]) * scale[n, c1+c2] (or NULL) -> H2 */
+/* fp32 NCHW (x1 [n,c1,hw] ++ x2 [n,c2,hw]) * scale[n, c1+c2] (or NULL) -> H2: v = x * scale is one fp32 multiply, hi = f16(v) (round to
+ * nearest even), lo = f16(v - hi); channels >= c1 + c2 of the last group are written as zeros.
+ * Input domain (the same for the f8 and f6 packers and the _part forms): x and scale finite, |x * scale| < 65520.  From 65520 on the
+ * hi half is +-inf and the lo half -+inf, so hi + lo is NaN; nothing is clamped here.  The generator stays inside through the
+ * activation clamp of 256 in front of every packer; the two producers that reach a packer without a clamp are the geometry encoder's
+ * features (bounded by its folded weights on inputs in [-1, 1]) and the training path (nb_pack_h2_ranged_f32, whose power of two brings
+ * max|x| max|scale| into (2^12, 2^14]). */
 int nb_pack_h2_f32(const float* x1, int c1, const float* x2, int c2, const float* scale, void* out_h2, int n,
                    int hw, void* stream);
 
@@ -309,7 +315,11 @@ int nb_blend_f32(const float* features, int nf, const float* alpha, int na, cons
 /* ---- "f8" operand format of the split-f16 convolutions: the two correction products on one block-scaled fp8 MFMA per
  * tap pair (csrc/nb_modconv_up1_h3.hip).  Same containers as H2 / nb_pack_conv_weight_h3, but the (cg, lo) slots of a
  * 16-channel chunk hold fp8 e4m3 values: activations (cg 2k, lo) = fp8(xl*2^9), (cg 2k+1, lo) = fp8(x/4); weights
- * (cg 0, lo) = fp8(w), (cg 1, lo) = fp8((w - f16(w))*2^11).  c_in % 16 == 0.  End-to-end pixel error ~1e-4 (H2: 5e-6). */
+ * (cg 0, lo) = fp8(w), (cg 1, lo) = fp8((w - f16(w))*2^11).  c_in % 16 == 0.  End-to-end pixel error ~1e-4 (H2: 5e-6).
+ * Activations: xl = v - f16(v) of v = x * scale; both planes are e4m3 (OCP e4m3fn, subnormals down to 2^-9, round to nearest even) of
+ * the value clamped to +-448, the 16 bytes of a slot in channel order; a zero code keeps the sign of its value.  Domain as for
+ * nb_pack_h2_f32; inside it the fp8(x/4) plane saturates from |v| = 1792 on and fp8(xl*2^9) from |xl| = 0.875 on (|v| >= 2048), while
+ * the hi half stays exact: the corrections lose accuracy there, the leading product does not. */
 int nb_pack_h2f8_f32(const float* x1, int c1, const float* x2, int c2, const float* scale, void* out, int n, int hw,
                      void* stream);
 /* c % 16 == 0 channels into the 16-channel chunks starting at channel group cg0 (even) of an f8-format tensor */
@@ -322,7 +332,12 @@ int nb_pack_h2f8_part_f32(const float* x, int c, const float* scale, int scale_s
  * e2m3(x[ch(i)]/S), S = 2^(exponent of the chunk's largest |x| - 2), byte = S; weights field 2i = e2m3(w[ch(i)]/Sw), field 2i+1 =
  * e2m3((w - f16(w))[ch(i)]*2^11/Sw), byte = Sw*2^-11; ch(i) = channels 0-3, 8-11, 4-7, 12-15 of the chunk.  c_in % 16 == 0.
  * Operand format number 2 of nb_modconv3x3_up1_h3_ex / nb_modconv3x3_up2_h3_ex (0 = H2, 1 = f8).  Replaces nothing in the reference
- * (its convolutions are cuDNN calls, torch_utils/ops/conv2d_gradfix.py:35-43); the math it serves is training/networks.py:30-88. */
+ * (its convolutions are cuDNN calls, torch_utils/ops/conv2d_gradfix.py:35-43); the math it serves is training/networks.py:30-88.
+ * Activations: x above = v = x * scale, the scale byte is floor(log2 m) - 2 + 127 for m = the chunk's largest |v| (so m / S lies in
+ * [4, 8) and (7.5 S, 8 S) saturates), e2m3 rounds to nearest even and a zero code keeps the sign of its value; the 32 fields are a
+ * little-endian 6-bit stream: bytes 0-15 in slot (cg 2k, lo), bytes 16-23, the scale byte and seven zero bytes in slot (cg 2k+1, lo).
+ * An all-zero chunk has scale byte 0 and zero fields: 32 zero bytes (a -0.0 in it leaves the sign bit in its x field).  Domain as for
+ * nb_pack_h2_f32, and m >= 2^-100 for a chunk that is not all zero. */
 int nb_pack_h2f6_f32(const float* x1, int c1, const float* x2, int c2, const float* scale, void* out, int n, int hw,
                      void* stream);
 /* c % 16 == 0 channels into the 16-channel chunks starting at channel group cg0 (even) of an f6-format tensor */
