@@ -1,0 +1,603 @@
+"""The device operations of the painting engine, as the drivers of ``painting`` see them (imports ``tiling`` and ``strokes``, nothing of
+``painting``).
+
+``TileOps`` is the product: the HIP generator split in two, the PyTorch-ROCm geometry encoder, and the canvas, preparation,
+compositing and stroke kernels.  ``TileOpsBase`` is what it derives from, and what the CPU stand-ins of the tests derive from: the
+scheduling hooks with defaults that do nothing, and a host restatement (numpy or torch, also in this module) of every operation
+that has one.  The drivers call ``ops.<operation>`` and never ask which ops they hold; a missing kernel is an error, not a fallback."""
+from __future__ import annotations
+
+import contextlib
+import os
+import time
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .strokes import SEG_PITCH, StrokeList, raster_strokes_numpy
+from .tiling import CELL_H, CELL_W, cell_box, prepare_geometry_image
+
+PAINT_SLOT0 = 8                 # first generator workspace slot of the tiled schedule (TileOps._GRAPH_SLOT = 16 onwards: graphs)
+
+# ------------------------------------------------------------------------------------------------
+# compositing (csrc/nb_compose.hip): the two contracts of include/neube_hip.h restated in int64
+# ------------------------------------------------------------------------------------------------
+COMPOSE_MODES = {"paint": 0, "erase": 1}
+
+
+def over_tiles_numpy(canvas: np.ndarray, tiles: np.ndarray, dst_yx, crop: int, mode: int = 0, opacity: int = 255,
+                     cells: Optional[Tuple[int, int, int, int]] = None) -> np.ndarray:
+    """``nb_over_tiles_u8`` in int64, in place on ``canvas`` [h,w,4] uint8 (returned): per pixel the LAST of ``tiles`` [t,r,r,4]
+    whose interior ``[crop, r-crop)^2`` at ``dst_yx[i] + crop`` covers it goes over (mode 0) or out of (mode 1) the pixel; only
+    inside ``cells`` = (cell_x0, cell_y0, cells_x, cells_y), the whole canvas for None."""
+    if mode not in (0, 1) or not 0 <= int(opacity) <= 255:
+        raise ValueError(f"over_tiles: bad mode {mode} or opacity {opacity}")
+    h, w = canvas.shape[:2]
+    tiles = np.asarray(tiles)
+    r, m = tiles.shape[1], int(crop)
+    src = np.zeros((h, w, 4), np.uint8)
+    cov = np.zeros((h, w), bool)
+    for i, (y, x) in enumerate(np.asarray(dst_yx).reshape(-1, 2).tolist()):       # ascending: a later tile replaces an earlier one
+        y0, x0, y1, x1 = max(0, y + m), max(0, x + m), min(h, y + r - m), min(w, x + r - m)
+        if y1 > y0 and x1 > x0:
+            src[y0:y1, x0:x1] = tiles[i, y0 - y:y1 - y, x0 - x:x1 - x]
+            cov[y0:y1, x0:x1] = True
+    if cells is not None:
+        inside = np.zeros((h, w), bool)
+        inside[cells[1] * CELL_H:(cells[1] + cells[3]) * CELL_H, cells[0] * CELL_W:(cells[0] + cells[2]) * CELL_W] = True
+        cov &= inside
+    s, d = src[cov].astype(np.int64), canvas[cov].astype(np.int64)
+    ae = (s[:, 3] * int(opacity) + 127) // 255
+    t = d[:, 3] * (255 - ae)
+    out = d.copy()
+    if mode == 1:
+        out[:, 3] = (t + 127) // 255
+    else:
+        den = ae * 255 + t
+        out[:, 3] = (den + 127) // 255
+        num = s[:, :3] * (ae * 255)[:, None] + d[:, :3] * t[:, None] + (den // 2)[:, None]
+        out[:, :3] = np.where(den[:, None] > 0, num // np.maximum(den, 1)[:, None], 0)
+    canvas[cov] = out.astype(np.uint8)
+    return canvas
+
+
+def canvas_view_numpy(canvas: np.ndarray, y0: int, x0: int, h: int, w: int, k: int = 1, on_white: bool = False) -> np.ndarray:
+    """``nb_canvas_view_u8`` in int64: the window of ``canvas`` [ch,cw,4] uint8 reduced by ``k`` -> [ceil(h/k), ceil(w/k), 4 | 3]."""
+    ch, cw = canvas.shape[:2]
+    if not (1 <= int(k) <= 16 and h >= 1 and w >= 1 and y0 >= 0 and x0 >= 0 and y0 + h <= ch and x0 + w <= cw):
+        raise ValueError(f"canvas_view: bad factor {k} or window {h} x {w} at ({y0}, {x0}) of a {ch} x {cw} canvas")
+    win = canvas[y0:y0 + h, x0:x0 + w].astype(np.int64)
+    ys, xs = np.arange(0, h, k), np.arange(0, w, k)
+
+    def blocks(a):
+        return np.add.reduceat(np.add.reduceat(a, ys, axis=0), xs, axis=1)
+    sa = blocks(win[..., 3])
+    sc = blocks(win[..., :3] * win[..., 3:])
+    n = np.outer(np.minimum(k, h - ys), np.minimum(k, w - xs))
+    if on_white:
+        den = (255 * n)[..., None]
+        return ((sc + 255 * (den - sa[..., None]) + den // 2) // den).astype(np.uint8)
+    colour = np.where(sa[..., None] > 0, (sc + (sa // 2)[..., None]) // np.maximum(sa, 1)[..., None], 0)
+    return np.concatenate([colour, ((sa + n // 2) // n)[..., None]], axis=2).astype(np.uint8)
+
+
+def stroke_counts_numpy(geom: np.ndarray, r: int, stride: int, nrows: int, ncols: int) -> np.ndarray:
+    """``nb_tile_stroke_counts_u8`` in numpy: [nrows, ncols] int32, the stroke pixels (bytes == 0) of ``geom`` [H,W] uint8 in the
+    r x r window at (row * stride, col * stride) of every tile; what of a window lies outside the image counts nothing."""
+    stroke = np.asarray(geom) == 0
+    return np.array([[stroke[y:y + r, x:x + r].sum() for x in range(0, ncols * stride, stride)]
+                     for y in range(0, nrows * stride, stride)], np.int32).reshape(nrows, ncols)
+
+
+def on_white_torch(rgba: torch.Tensor) -> torch.Tensor:
+    """paint_image_main.py:179-183 as a torch expression (3 channels out), on the device of ``rgba``: what
+    ``nb_composite_on_white_u8`` computes.  The host route ``PaintingHelper.paint_image`` and ``TileOpsBase`` use it."""
+    # alpha = a / 255 through a host-computed table: device division is not correctly rounded
+    lut = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(rgba.device, non_blocking=True)
+    a = lut[rgba[..., 3:].to(torch.int64)]
+    return (rgba[..., :3].to(torch.float32) * a + 255 * (1 - a)).clip(0, 255).to(torch.uint8)
+
+
+# ------------------------------------------------------------------------------------------------
+# device operations (HIP)
+# ------------------------------------------------------------------------------------------------
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+class TileOpsBase:
+    """What ``PaintingHelper`` and ``PaintSession`` call on their ``ops``, as far as it can be said without a device: the scheduling
+    hooks, with defaults that do nothing (one stream, no workspaces to prepare, no noise sets, no captured graphs), and the host
+    restatement of every operation that has one (drawing preparation, stroke raster, tile counts, on-white, compositing, view), on
+    host tensors.  ``TileOps`` overrides all of them; the CPU stand-ins of the tests derive from this class and define only what has
+    no restatement here (``to_device``, ``geom_tiles``, ``encode``, ``head`` / ``tail`` / ``full``, the feature-canvas operations, ``paste``)."""
+    n_streams = 1
+    stream_policy = 0
+    graph_single = None          # None: no graphs exist; False (TileOps): they exist, off -- render_stroke switches on only the latter
+
+    def stream(self, k: int):
+        return contextlib.nullcontext()
+
+    def comm_stream(self):
+        return contextlib.nullcontext()
+
+    def join_streams(self, tensors=()) -> None:
+        pass
+
+    def join_comm(self, tensors=()) -> None:
+        pass
+
+    def prepare(self, n: int, slots) -> None:
+        pass
+
+    def choose_streams(self, n: int, render_mode: str = "clear") -> None:
+        pass
+
+    def brush_noise(self):
+        """None: this ops has no noise sets, and is never handed one."""
+        return None
+
+    def to_host(self, t: torch.Tensor) -> np.ndarray:
+        return t.cpu().numpy()
+
+    # -- drawing preparation and strokes: the host restatements, on host tensors (``TileOps`` runs csrc/nb_geomprep.hip, nb_strokes.hip) --
+    def prepare_geometry(self, img, out_shape=None, offset=(0, 0)) -> torch.Tensor:
+        """``prepare_geometry_image(img)[..., 0]`` at ``offset`` of a [out_h, out_w] uint8 buffer that is 255 elsewhere.  ``img``: decoded
+        drawing, uint8 [H,W], [H,W,3] or [H,W,4], numpy or a host tensor."""
+        img = img.numpy() if torch.is_tensor(img) else np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3):
+            raise ValueError(f"prepare_geometry: uint8 [H,W] or [H,W,C] expected, got {img.dtype} {tuple(img.shape)}")
+        h, w = img.shape[:2]
+        out = np.full((h, w) if out_shape is None else (int(out_shape[0]), int(out_shape[1])), 255, np.uint8)
+        out[int(offset[0]):int(offset[0]) + h, int(offset[1]):int(offset[1]) + w] = prepare_geometry_image(img)[..., 0]
+        return torch.from_numpy(out)
+
+    def stroke_counts(self, geom: torch.Tensor, r: int, stride: int, nrows: int, ncols: int) -> torch.Tensor:
+        """[nrows, ncols] int32: stroke pixels (== 0) in the r x r window of every tile."""
+        return torch.from_numpy(stroke_counts_numpy(geom.numpy(), r, stride, nrows, ncols))
+
+    def composite_on_white(self, canvas: torch.Tensor, y0: int, x0: int, h: int, w: int) -> torch.Tensor:
+        """[h, w, 3] uint8: the window of the RGBA canvas at (y0, x0) over white."""
+        return on_white_torch(canvas[y0:y0 + h, x0:x0 + w])
+
+    def raster_strokes(self, strokes: StrokeList, out_shape=None, offset=(0, 0), out: Optional[torch.Tensor] = None,
+                       subdiv: int = 8) -> torch.Tensor:
+        """The strokes as [out_h, out_w] uint8 geometry (255 = background, 0 = stroke), drawing position (0, 0) at pixel ``offset`` =
+        (off_y, off_x).  ``out`` given: the strokes are added to that geometry (every other byte untouched)."""
+        if out is not None:
+            raster_strokes_numpy(strokes, None, offset, subdiv, out.numpy())
+            return out
+        return torch.from_numpy(raster_strokes_numpy(strokes, (int(out_shape[0]), int(out_shape[1])), offset, subdiv))
+
+    # -- compositing: the numpy restatements, on host tensors (``TileOps`` runs the kernels of csrc/nb_compose.hip) --
+    def over_tiles(self, canvas, tiles_u8, dst_yx, crop, cell_off, cell_tiles, box=None, mode: int = 0, opacity: int = 255) -> None:
+        """``tiles_u8`` [t,r,r,4] over (mode 0) or out of (mode 1) ``canvas`` [h,w,4], in place, inside the cells that the pixel box
+        (y0, x0, y1, x1) touches (None: everywhere).  The cell lists are those of ``paste``."""
+        h, w = canvas.shape[:2]
+        cells = cell_box(box, h, w)
+        if cells is not None:
+            over_tiles_numpy(canvas.numpy(), tiles_u8.numpy(), dst_yx.numpy(), crop, mode, opacity, cells)
+
+    def canvas_view(self, canvas, y0: int, x0: int, h: int, w: int, k: int = 1, on_white: bool = False) -> torch.Tensor:
+        """[ceil(h/k), ceil(w/k), 4 | 3] uint8: the window of the RGBA canvas at (y0, x0) reduced by ``k``."""
+        return torch.from_numpy(canvas_view_numpy(canvas.numpy(), y0, x0, h, w, k, on_white))
+
+
+class TileOps(TileOpsBase):
+    """What the tiled schedule needs from the device: the HIP generator split in two, the geometry encoder, and the
+    canvas kernels of ``csrc/nb_canvas.hip``."""
+    _comm = None                 # the halo exchange's side stream (comm_stream creates it)
+    _prep_ws = None              # workspace of nb_geom_prepare_u8 (prepare_geometry creates it)
+
+    def __init__(self, G, encoder, device=None):
+        self.G, self.encoder = G, encoder
+        self.device = torch.device(device) if device is not None else G.synthesis.get_last_block().conv1.weight.device
+        if self.device.type != "cuda":
+            raise _lib.NeubeHipError("the painting engine needs the generator on a GPU (no CPU path in this build)")
+        self.patch_width = G.img_resolution
+        self.cfg = G.cfg
+        # the encoder computes in the generator's arithmetic: fp8 correction operands between its layers only when the generator
+        # itself runs "f8" (its features then carry ~3e-4 instead of ~2e-5 absolute error on O(5) values)
+        if hasattr(encoder, "arith"):
+            encoder.arith = "f8" if getattr(G.synthesis, "conv_mode", None) == "f8" else "h3"
+        self._rr = {}                # stream count -> pipeline.RoundRobinStreams (created at first use, kept across probes)
+        self._graphs, self._graph_epoch, self._capturing = {}, None, False
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    # -- inputs --
+    def to_device(self, a: np.ndarray) -> torch.Tensor:
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
+
+    def to_host(self, t: torch.Tensor) -> np.ndarray:
+        """Device tensor -> numpy through a pinned buffer (the caching host allocator recycles it once the array dies)."""
+        host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        host.copy_(t, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return host.numpy()
+
+    def geom_tiles(self, geom_dev: torch.Tensor, tile_yx: torch.Tensor) -> torch.Tensor:
+        gh, gw = geom_dev.shape
+        t, r = tile_yx.shape[0], self.patch_width
+        out = torch.empty([t, 1, r, r], dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_geom_tiles_f32(_p(geom_dev), gh, gw, _p(tile_yx), t, r, _p(out), self._stream()),
+                       "geom_tiles")
+        return out
+
+    lazy_geometry = True       # hand the generator a geometry provider (encoder output straight into the layer operands)
+
+    def encode(self, geom: torch.Tensor):
+        if self.lazy_geometry and hasattr(self.encoder, "lazy"):
+            return self.encoder.lazy(geom)
+        return self.encoder.encode(geom)
+
+    def prepare(self, n: int, slots) -> None:
+        """Create the generator workspaces of ``slots`` for batches of ``n`` on the CALLER's stream, before the batch streams fork
+        (a workspace is otherwise created by the first batch that needs it, on that batch's stream, while the other stream is
+        already running)."""
+        for sl in slots:
+            self.G.synthesis._get_plan(n, self.device, sl)
+
+    def map_style(self, z=None, ws=None) -> torch.Tensor:
+        if ws is not None:
+            return ws.to(self.device, torch.float32)
+        return self.G.mapping(z.to(self.device), None)
+
+    # -- generator halves --
+    # ``slot``: which of the generator's per-batch workspaces to use -- consecutive batches alternate between two HIP
+    # streams (``stream``/``join_streams``), each with its own workspace, so that one batch's kernel tails and small
+    # launches are covered by the other batch's work
+    # ``noise_set``: the brush's noise buffers (``networks.BrushNoise``, ``brush_noise()`` below; None = the checkpoint's noise).  Its
+    # identity is part of a graph's key, its contents are not: the set's addresses are fixed, so a captured pass renders whatever the
+    # set holds when it is replayed.
+    def brush_noise(self):
+        return self.G.synthesis.brush_noise()
+
+    @staticmethod
+    def _set_key(noise_set):
+        return None if noise_set is None else id(noise_set)       # (the graph's closure keeps the set alive: the id stays its own)
+
+    def head(self, ws, geom_feats, positions, stop_res: int, slot: int = 0, noise_set=None) -> torch.Tensor:
+        if self._use_graph(ws):
+            return self._graphed(("head", stop_res, self._set_key(noise_set)), [ws, geom_feats[0], geom_feats[1], positions],
+                                 lambda w, g0, g1, ps: self.head(w, [g0, g1], ps, stop_res, slot=self._GRAPH_SLOT, noise_set=noise_set))
+        return self.G.forward_pre_mapped(ws, geom_feats, positions=positions, noise_mode="const", _stop_after=stop_res,
+                                         _plan_slot=slot, noise_set=noise_set)
+
+    def tail(self, ws, feats, geom_feats, positions, resume_res: int, render_mode, user_colors, sfactor=None,
+             slot: int = 0, noise_set=None) -> torch.Tensor:
+        if self._use_graph(ws) and (sfactor is None or torch.is_tensor(sfactor)):
+            return self._graphed(("tail", resume_res, render_mode, self._set_key(noise_set)),
+                                 [ws, feats, geom_feats[0], geom_feats[1], positions, user_colors, sfactor],
+                                 lambda w, f, g0, g1, ps, uc, sf: self.tail(w, f, [g0, g1], ps, resume_res, render_mode, uc, sf,
+                                                                           slot=self._GRAPH_SLOT + 1, noise_set=noise_set))
+        u8, _, _ = self.G.render_triad(ws=ws, geom_feature=geom_feats, positions=positions, render_mode=render_mode,
+                                       user_colors=user_colors, sfactor=sfactor, _resume=(resume_res, feats), _plan_slot=slot,
+                                       noise_set=noise_set)
+        return u8
+
+    def full(self, ws, geom_feats, positions, render_mode, user_colors, sfactor=None, slot: int = 0, noise_set=None) -> torch.Tensor:
+        if self._use_graph(ws) and (sfactor is None or torch.is_tensor(sfactor)):
+            return self._graphed(("full", render_mode, self._set_key(noise_set)),
+                                 [ws, geom_feats[0], geom_feats[1], positions, user_colors, sfactor],
+                                 lambda w, g0, g1, ps, uc, sf: self.full(w, [g0, g1], ps, render_mode, uc, sf,
+                                                                         slot=self._GRAPH_SLOT + 2, noise_set=noise_set))
+        u8, _, _ = self.G.render_triad(ws=ws, geom_feature=geom_feats, positions=positions, render_mode=render_mode,
+                                       user_colors=user_colors, sfactor=sfactor, _plan_slot=slot, noise_set=noise_set)
+        return u8
+
+    # -- hipGraph replay of the generator passes of ONE tile (interactive strokes) --
+    # An interactive stroke is bound by the ~0.2 ms of Python each eager generator pass costs, not by the device.  With
+    # ``graph_single`` set (PaintingHelper.render_stroke does), the passes of a single tile are captured once per call
+    # signature into hipGraphs that own a workspace slot; a call then copies its inputs into the graph's static
+    # tensors and replays.  The returned tensor is the graph's output buffer: valid until the next call of that pass.
+    graph_single = False
+    _GRAPH_SLOT = 16
+
+    def _use_graph(self, ws) -> bool:
+        return (self.graph_single and not self._capturing and ws.shape[0] == 1 and len(self.cfg.geom_feature_channels) == 2
+                and not torch.cuda.is_current_stream_capturing())
+
+    def _graphed(self, key, tensors, fn):
+        packed = self.G.synthesis.packed
+        if self._graph_epoch is not packed:                   # weights were (re)loaded / moved: captured pointers are stale
+            self._graphs, self._graph_epoch = {}, packed
+        key = key + tuple(None if t is None else (tuple(t.shape), t.dtype) for t in tensors)
+        ent = self._graphs.get(key)
+        if ent is None:
+            statics = [None if t is None else t.detach().clone() for t in tensors]
+            self._capturing = True
+            try:
+                cur = torch.cuda.current_stream(self.device)
+                side = torch.cuda.Stream(device=self.device)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):                # creates the slot's workspace, packs weights, warms the kernels
+                    for _ in range(2):
+                        fn(*statics)
+                cur.wait_stream(side)
+                torch.cuda.synchronize(self.device)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    out = fn(*statics)
+            finally:
+                self._capturing = False
+            ent = (graph, statics, out)
+            self._graphs[key] = ent
+        graph, statics, out = ent
+        for s_, t in zip(statics, tensors):
+            if s_ is not None:
+                s_.copy_(t, non_blocking=True)
+        graph.replay()
+        return out
+
+    n_streams = 2
+    # 0 = choose n_streams by a probe the first time a multi-batch canvas is painted (choose_streams); 1 / 2 / 3 = fixed.
+    # Alternating batches over HIP streams lets one batch's kernel tails and small launches run under the other's big ones, which
+    # is worth +5..10 % on most boxes -- and cost 14 % on the box of the round-3 driver run (three chains of 156 KB-LDS workgroups
+    # evicting each other at kernel boundaries), so the schedule measures instead of assuming.
+    stream_policy = int(os.environ.get("NB_CANVAS_STREAMS", "0"))
+    stream_probe = None          # what choose_streams measured: {"ms_per_batch": {1: .., 2: ..}, "chosen": n, "batch": n}
+
+    def _set_n_streams(self, k: int) -> None:
+        """Change the number of batch streams (every count keeps its own ``RoundRobinStreams``; ``stream(k)`` indexes the current one)."""
+        self.n_streams = k
+
+    def _round_robin(self):
+        """The scheduler of the generator's throughput mode (``pipeline.RoundRobinStreams``, also behind ``ConcurrentTriadSteps`` /
+        ``bench.py``): batch b runs on stream b % n_streams with workspace slot PAINT_SLOT0 + b % n_streams."""
+        from .pipeline import RoundRobinStreams
+        rr = self._rr.get(self.n_streams)
+        if rr is None:
+            rr = self._rr[self.n_streams] = RoundRobinStreams(self.device, self.n_streams, PAINT_SLOT0)
+        return rr
+
+    def choose_streams(self, n: int, render_mode: str = "clear") -> int:
+        """Pick the number of batch streams for batches of ``n`` tiles: the fixed policy, or -- once per TileOps and batch size --
+        two streams unless a probe -- three interleaved rounds of six synthetic batches on 1 and on 2 streams, best of three each, full
+        generator passes with random styles and geometry features, ~80 ms -- shows them more than 3 % slower.  Sets ``n_streams``; the probe's figures stay in ``stream_probe`` (tools/bench_canvas.py reports them)."""
+        if self.stream_policy > 0:
+            self._set_n_streams(self.stream_policy)
+            return self.n_streams
+        if self.stream_probe is not None and self.stream_probe.get("batch") == n:
+            return self.n_streams
+        cfg, dev = self.cfg, self.device
+        gen = torch.Generator(device="cpu").manual_seed(1234)
+        ws = torch.randn([n, cfg.num_ws, cfg.w_dim], generator=gen).to(dev)
+        geom = [torch.randn([n, c, r, r], generator=gen).to(dev) for c, r in zip(cfg.geom_feature_channels, cfg.geom_feature_resolutions)]
+        pos = torch.zeros([n, 2], dtype=torch.int64, device=dev)
+        times = {1: [], 2: []}
+
+        def run(k, batches):
+            # (each stream count keeps its own side streams across the interleaved rounds)
+            self._set_n_streams(k)
+            self.prepare(n, sorted({PAINT_SLOT0 + i % k for i in range(k)}))
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            outs = []
+            for b in range(batches):
+                with self.stream(b):
+                    outs.append(self.full(ws, geom, pos, render_mode, None, None, slot=PAINT_SLOT0 + b % k))
+            self.join_streams(outs)
+            torch.cuda.synchronize(dev)
+            return (time.perf_counter() - t0) / batches * 1e3
+        run(1, 2); run(2, 4)                             # workspaces, code objects, clocks
+        for _ in range(3):                               # interleaved, best of three each: a single pair of short runs was off by
+            times[1].append(run(1, 6))                   # +-7 % between processes on one box (r04 collection: 1.89 vs 2.02 ms, then
+            times[2].append(run(2, 6))                   # 1.87 vs 1.77 ms a minute later), more than the effect it is meant to see
+        times = {k: min(v) for k, v in times.items()}
+        # two streams unless they are clearly slower HERE.  The probe renders generator passes only; in the canvas job, where encoder,
+        # canvas kernels and copies sit between them, the second stream is worth 5-7 % on every box measured (same-box A/Bs of the
+        # 4096^2 job in round 4: 44.4 -> 42.2, 44.1 -> 41.0, 43.8 -> 40.8 ms) while their probes said 1.81 -> 1.79, 2.08 -> 1.81 and
+        # 1.85 -> 1.87 ms per batch: a probe within noise must not cost the job its overlap; a box that loses with concurrent chains
+        # (the round-3 driver run saw three streams 14 % below one) shows it as > 3 % here
+        best = 1 if times[2] > 1.03 * times[1] else 2
+        self._set_n_streams(best)
+        self.stream_probe = {"ms_per_batch": {str(k): round(v, 4) for k, v in times.items()}, "chosen": best, "batch": n}
+        return best
+
+    def stream(self, k: int):
+        """Context manager: work of batch k goes to side stream k % n_streams (which first waits for the caller's)."""
+        return self._round_robin().stream(k)
+
+    def join_streams(self, tensors=()):
+        """The caller's stream waits for the side streams; ``tensors`` produced there are about to be read here."""
+        rr = self._rr.get(self.n_streams)
+        if rr is not None:
+            rr.join(tensors)
+        else:
+            main = torch.cuda.current_stream(self.device)
+            for t in tensors:
+                if torch.is_tensor(t) and t.is_cuda:
+                    t.record_stream(main)
+
+    def comm_stream(self):
+        """Context manager for the halo exchange: a side stream that first waits for everything enqueued so far on the
+        batch streams (the boundary tiles' phase 1), so that packing + the collective overlap the remaining batches."""
+        if self._comm is None:
+            self._comm = torch.cuda.Stream(device=self.device)
+        self._comm.wait_stream(torch.cuda.current_stream(self.device))
+        rr = self._rr.get(self.n_streams)
+        for st in (rr.streams if rr is not None else []):
+            self._comm.wait_stream(st)
+        return torch.cuda.stream(self._comm)
+
+    def join_comm(self, tensors=()):
+        if self._comm is not None:
+            main = torch.cuda.current_stream(self.device)
+            main.wait_stream(self._comm)
+            for t in tensors:
+                if torch.is_tensor(t) and t.is_cuda:
+                    t.record_stream(main)
+
+    def background_weight(self, ws, geom_feats) -> torch.Tensor:
+        """S = uvs[:, 2:3] of an un-positioned render (what StyleUVSMapper calibrates on, mapper.py:74-87)."""
+        _, dbg = self.G.forward_pre_mapped(ws, geom_feats, return_debug_data=True, noise_mode="const")
+        return dbg["uvs"][:, 2:3]
+
+    # -- canvas kernels --
+    def new_feature_canvas(self, c, hc, wc):
+        return (torch.zeros([1, c, hc, wc], dtype=torch.float32, device=self.device),
+                torch.zeros([hc, wc], dtype=torch.uint8, device=self.device))
+
+    def replay(self, tiles, tile_yx, alpha0, crop, canvas, mask, cell_off, cell_tiles, box=None) -> torch.Tensor:
+        """In place on ``tiles`` and ``canvas``; returns the new mask buffer.  ``box`` = (y0, x0, y1, x1) canvas pixels
+        that contain every tile (an interactive stroke replays one tile on a large canvas): only those cells run."""
+        t, c, hw, _ = tiles.shape
+        hc, wc = mask.shape
+        with torch.cuda.device(self.device):
+            if box is not None:
+                cells = cell_box(box, hc, wc)
+                if cells is None:
+                    return mask
+                mask_out = mask.clone()
+                _lib.check(_lib.lib().nb_canvas_replay_box_f32(_p(tiles), t, c, hw, _p(tile_yx), _p(alpha0), crop, _p(canvas),
+                                                               _p(mask), _p(mask_out), hc, wc, _p(cell_off), _p(cell_tiles),
+                                                               *cells, self._stream()), "canvas_replay")
+                return mask_out
+            mask_out = torch.empty_like(mask)
+            _lib.check(_lib.lib().nb_canvas_replay_f32(_p(tiles), t, c, hw, _p(tile_yx), _p(alpha0), crop, _p(canvas),
+                                                       _p(mask), _p(mask_out), hc, wc, _p(cell_off), _p(cell_tiles),
+                                                       self._stream()), "canvas_replay")
+        return mask_out
+
+    def replay_pieces(self, pieces, hw, alpha0, crop, canvas, mask, cell_off, cell_pieces, box) -> torch.Tensor:
+        """The replay over tile pieces (multi-GPU halo exchange).  ``pieces`` = [(view [C,h,w] with unit column stride,
+        cy, cx, ly0, lx0), ...] in paint order; in place on the views and ``canvas``; returns the new mask buffer.
+        ``box`` = (y0, x0, y1, x1) canvas pixels containing every piece."""
+        hc, wc = mask.shape
+        c = pieces[0][0].shape[0]
+        arr = (_lib.NbTilePiece * len(pieces))()
+        for i, (v, cy, cx, ly0, lx0) in enumerate(pieces):
+            assert v.dtype == torch.float32 and v.stride(2) == 1 and v.shape[0] == c
+            arr[i] = _lib.NbTilePiece(v.data_ptr(), v.stride(0), v.stride(1), cy, cx, v.shape[1], v.shape[2], ly0, lx0)
+        table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device, non_blocking=True)
+        cells = cell_box(box, hc, wc)
+        if cells is None:
+            return mask
+        mask_out = mask.clone()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_canvas_replay_pieces_f32(_p(table), len(pieces), c, hw, _p(alpha0), crop, _p(canvas),
+                                                              _p(mask), _p(mask_out), hc, wc, _p(cell_off), _p(cell_pieces),
+                                                              *cells, self._stream()), "canvas_replay_pieces")
+        return mask_out
+
+    def paste(self, canvas_u8, tiles_u8, dst_yx, crop, cell_off, cell_tiles) -> None:
+        t, r = tiles_u8.shape[0], tiles_u8.shape[1]
+        h, w = canvas_u8.shape[:2]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_paste_tiles_u8(_p(tiles_u8), t, r, _p(dst_yx), crop, _p(canvas_u8), h, w,
+                                                    _p(cell_off), _p(cell_tiles), self._stream()), "paste_tiles")
+
+    # -- drawing preparation (csrc/nb_geomprep.hip) --
+    def prepare_geometry(self, img, out_shape=None, offset=(0, 0)) -> torch.Tensor:
+        """``prepare_geometry_image(img)[..., 0]`` computed on the device and placed at ``offset`` of a [out_h, out_w] uint8
+        buffer that is 255 elsewhere (``nb_geom_prepare_u8``).  ``img``: decoded drawing, uint8 [H,W], [H,W,3] or [H,W,4],
+        numpy (uploaded here) or a device tensor."""
+        if not torch.is_tensor(img):
+            img = np.asarray(img)
+            if img.dtype != np.uint8:
+                raise ValueError(f"prepare_geometry: the drawing must be uint8, got {img.dtype}")
+            img = self.to_device(img)
+        if img.dtype != torch.uint8 or img.dim() not in (2, 3):
+            raise ValueError(f"prepare_geometry: uint8 [H,W] or [H,W,C] expected, got {img.dtype} {tuple(img.shape)}")
+        img = img.contiguous()
+        h, w = img.shape[:2]
+        ch = 1 if img.dim() == 2 else img.shape[2]
+        out_h, out_w = (h, w) if out_shape is None else out_shape
+        out = torch.empty([out_h, out_w], dtype=torch.uint8, device=self.device)
+        if self._prep_ws is None:
+            self._prep_ws = torch.empty([_lib.NB_GEOM_PREP_WS_BYTES // 4], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_geom_prepare_u8(_p(img), h, w, ch, _p(out), out_h, out_w, int(offset[0]), int(offset[1]),
+                                                     _p(self._prep_ws), self._stream()), "geom_prepare")
+        return out
+
+    def stroke_counts(self, geom_dev: torch.Tensor, r: int, stride: int, nrows: int, ncols: int) -> torch.Tensor:
+        """[nrows, ncols] int32 on the device: stroke pixels (== 0) in the r x r window of every tile (``nb_tile_stroke_counts_u8``)."""
+        gh, gw = geom_dev.shape
+        counts = torch.empty([nrows, ncols], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_tile_stroke_counts_u8(_p(geom_dev), gh, gw, r, stride, nrows, ncols, _p(counts), self._stream()),
+                       "tile_stroke_counts")
+        return counts
+
+    def composite_on_white(self, canvas: torch.Tensor, y0: int, x0: int, h: int, w: int) -> torch.Tensor:
+        """[h, w, 3] uint8: the window of the RGBA canvas at (y0, x0) over white (``nb_composite_on_white_u8``)."""
+        ch, cw = canvas.shape[:2]
+        out = torch.empty([h, w, 3], dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_composite_on_white_u8(_p(canvas), ch, cw, y0, x0, h, w, _p(out), self._stream()),
+                       "composite_on_white")
+        return out
+
+    # -- compositing (csrc/nb_compose.hip) --
+    def over_tiles(self, canvas, tiles_u8, dst_yx, crop, cell_off, cell_tiles, box=None, mode: int = 0, opacity: int = 255) -> None:
+        """``tiles_u8`` [t,r,r,4] over (mode 0) or out of (mode 1) ``canvas`` [h,w,4], in place, inside the cells that the pixel box
+        (y0, x0, y1, x1) touches (None: everywhere).  The cell lists are those of ``paste`` (``nb_over_tiles_u8``)."""
+        t, r = tiles_u8.shape[0], tiles_u8.shape[1]
+        h, w = canvas.shape[:2]
+        cells = cell_box(box, h, w)
+        if cells is None:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_over_tiles_u8(_p(tiles_u8), t, r, _p(dst_yx), crop, _p(canvas), h, w, _p(cell_off), _p(cell_tiles),
+                                                   *cells, int(mode), int(opacity), self._stream()), "over_tiles")
+
+    def canvas_view(self, canvas, y0: int, x0: int, h: int, w: int, k: int = 1, on_white: bool = False) -> torch.Tensor:
+        """[ceil(h/k), ceil(w/k), 4 | 3] uint8: the window of the RGBA canvas at (y0, x0) reduced by ``k`` (``nb_canvas_view_u8``)."""
+        ch, cw = canvas.shape[:2]
+        k = int(k)
+        if not 1 <= k <= 16:
+            raise ValueError(f"canvas_view: factor {k} outside 1..16")
+        out = torch.empty([-(-int(h) // k), -(-int(w) // k), 3 if on_white else 4], dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_canvas_view_u8(_p(canvas), ch, cw, int(y0), int(x0), int(h), int(w), k, int(bool(on_white)), _p(out),
+                                                    self._stream()), "canvas_view")
+        return out
+
+    # -- vector strokes (csrc/nb_strokes.hip) --
+    spline_alpha = 0.5           # centripetal Catmull-Rom, the reference's default (curve.py:24)
+
+    def stroke_segments(self, strokes: StrokeList, subdiv: int = 8) -> torch.Tensor:
+        """[n, SEG_PITCH] float32 on the device: the polylines' segment rows (uploaded) followed by the splines' (control points
+        uploaded, cut into ``subdiv`` pieces per span by ``nb_spline_flatten_f32``).  Kilobytes cross PCIe."""
+        poly = strokes.polyline_segments()
+        ctrl, off = strokes.spline_control()
+        n_poly, n_spl = poly.shape[0], strokes.spline_segment_count(subdiv)
+        segs = torch.empty([n_poly + n_spl, SEG_PITCH], dtype=torch.float32, device=self.device)
+        if n_poly:
+            segs[:n_poly].copy_(torch.from_numpy(poly), non_blocking=True)
+        if n_spl:
+            d_ctrl, d_off = self.to_device(ctrl), self.to_device(off)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().nb_spline_flatten_f32(_p(d_ctrl), _p(d_off), ctrl.shape[0], len(off) - 1, int(subdiv),
+                                                            float(self.spline_alpha), _p(segs[n_poly:]), n_spl, self._stream()),
+                           "spline_flatten")
+        return segs
+
+    def raster_segments(self, segs: torch.Tensor, out_shape=None, offset=(0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``nb_raster_segments_u8`` on device segment rows [n, SEG_PITCH]: a new [out_h, out_w] uint8 geometry (255 = background,
+        0 = stroke), or, with ``out`` given, the strokes darkened onto that tensor and everything else left as it is."""
+        if segs.dtype != torch.float32 or segs.dim() != 2 or segs.shape[1] != SEG_PITCH or not segs.is_contiguous():
+            raise ValueError(f"raster_segments: contiguous float32 [n, {SEG_PITCH}] expected, got {segs.dtype} {tuple(segs.shape)}")
+        clear = out is None
+        if clear:
+            out = torch.empty([int(out_shape[0]), int(out_shape[1])], dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.dim() != 2 or not out.is_contiguous() or out.device != segs.device:
+            raise ValueError(f"raster_segments: out must be a contiguous uint8 [H,W] device tensor, got {out.dtype} {tuple(out.shape)}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_raster_segments_u8(_p(segs) if segs.shape[0] else None, segs.shape[0], _p(out), out.shape[0],
+                                                        out.shape[1], int(offset[0]), int(offset[1]), int(clear), self._stream()),
+                       "raster_segments")
+        return out
+
+    def raster_strokes(self, strokes: StrokeList, out_shape=None, offset=(0, 0), out: Optional[torch.Tensor] = None,
+                       subdiv: int = 8) -> torch.Tensor:
+        """The strokes as [out_h, out_w] uint8 geometry on the device (255 = background, 0 = stroke), drawing position (0, 0) at
+        pixel ``offset`` = (off_y, off_x): splines are flattened on the device, and polyline and spline segments are rasterised in
+        one ``nb_raster_segments_u8`` launch.  ``out`` given: the strokes are added to that geometry (every other byte untouched)."""
+        return self.raster_segments(self.stroke_segments(strokes, subdiv), out_shape, offset, out)

@@ -1,5 +1,8 @@
 """What the CPU and the GPU tests of the compositing kernels and the paint session share (tests/test_compose_cpu.py,
-tests/test_hip_compose.py): the scenes, the contract of the view as a loop, and the assertions on a session."""
+tests/test_hip_compose.py): the scenes, the contract of the view as a loop, and the assertions on a session -- and the drawing,
+cases and once-computed ``paint_image`` results that hold ``paint_strokes`` and ``paint_drawing`` to the host route on the CPU."""
+import functools
+
 import numpy as np
 import torch
 
@@ -121,6 +124,75 @@ def check_session(ops, level, m, to_host):
     assert session.undo() == box2
     assert np.array_equal(to_host(session.canvas), one)
     return session
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# one route whatever the ops: paint_strokes / paint_drawing on the oracle-backed ops against the host route paint_image
+# (tests/test_stroke_refs_cpu.py, tests/test_geomprep_cpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+# 150 x 170 at R = 128, crop margin 10: tiles at stride 88 in 2 rows x 3 columns, neighbours overlapping by 40 px, and a third column
+# without a stroke pixel, which "stroke" mode drops -- the smallest drawing with all of that.
+ROUTE_SIZE = (150, 170)
+ROUTE_CASES = [(level, mode, on_white) for level in (0, 2) for mode in ("stroke", "all") for on_white in (False, True)]
+ROUTE_FULL_CASE = (2, "stroke", True)            # the one case that also compares canvas, crops and padded geometry
+
+
+@functools.lru_cache(maxsize=None)
+def route_ops():
+    """(ops, crop margin): ``OracleTileOps`` on the weights of ``engine_r128.npz``, as tests/test_compose_cpu.py sets it up."""
+    from conftest import load_golden
+    from brushstroke_engine_amd import config as cfgmod, encoder as encmod, weights as wmod
+    from oracle_tile_ops import OracleTileOps
+    g = load_golden("engine_r128.npz")
+    cfg = cfgmod.style1_config(int(g["resolution"]))
+    ops = OracleTileOps(cfg, wmod.random_state_dict(cfg, seed=int(g["weights_seed"])), encmod.random_encoder_state_dict(int(g["encoder_seed"])))
+    return ops, int(g["crop_margin"])
+
+
+def route_helper(level):
+    helper = painting.PaintingHelper(route_ops()[0], batch=4)
+    helper.set_feature_blending(level)
+    return helper
+
+
+@functools.lru_cache(maxsize=None)
+def route_geometry():
+    """[150, 170, 1] uint8, read-only: the first session strokes rasterised on the host."""
+    geom = painting.raster_strokes_numpy(session_strokes()[0], ROUTE_SIZE)[..., None]
+    geom.flags.writeable = False
+    return geom
+
+
+@functools.lru_cache(maxsize=None)
+def host_route(level, mode, on_white):
+    """(image, canvas, crops, padded geometry) of ``paint_image`` on ``route_geometry()``, computed once per case, read-only."""
+    ops, m = route_ops()
+    with torch.no_grad():
+        out = route_helper(level).paint_image(route_geometry(), session_brushes(ops.cfg.z_dim)[0], crop_margin=m, stitching_mode=mode,
+                                              on_white=on_white, return_full=True)
+    for a in (out[0], out[1], out[3]):
+        a.flags.writeable = False
+    return out
+
+
+def check_same_as_host_route(paint, case):
+    """``paint(helper, opts, crop_margin=, stitching_mode=, on_white=, return_full=)`` -- paint_strokes or paint_drawing on the drawing of
+    ``route_geometry()`` -- returns the bytes of the host route, and those are a painting, not a blank."""
+    level, mode, on_white = case
+    ops, m = route_ops()
+    image, canvas, crops, padded = host_route(*case)
+    assert (route_geometry() == 0).sum() > 500 and (padded == 0).sum() == (route_geometry() == 0).sum()
+    assert image.shape == ROUTE_SIZE + ((3,) if on_white else (4,)) and len(np.unique(image.reshape(-1, image.shape[2]), axis=0)) > 10
+    assert len(crops) == (4 if mode == "stroke" else 6)
+    full = case == ROUTE_FULL_CASE
+    with torch.no_grad():
+        got = paint(route_helper(level), session_brushes(ops.cfg.z_dim)[0], crop_margin=m, stitching_mode=mode, on_white=on_white,
+                    return_full=full)
+    if not full:
+        assert got.dtype == np.uint8 and np.array_equal(got, image)
+        return
+    assert np.array_equal(got[0], image) and np.array_equal(got[1], canvas) and canvas.any()
+    assert [tuple(c) for c in got[2]] == [tuple(c) for c in crops] and got[3].dtype == np.uint8 and np.array_equal(got[3], padded)
 
 
 def good_script():

@@ -1,13 +1,16 @@
 """Drawing preparation, the parts that need no GPU: the host-only tile grid ``nb_stitching_grid`` against
-``painting.generate_stitching_crops``, argument checks of the device entries (they validate before any launch), and the
-header / binding agreement on the four entries of ``csrc/nb_geomprep.hip``."""
+``painting.generate_stitching_crops``, argument checks of the device entries (they validate before any launch), the
+header / binding agreement on the four entries of ``csrc/nb_geomprep.hip``, the host restatements ``TileOpsBase`` carries for them,
+and ``paint_drawing`` on the oracle-backed ops against the host route ``paint_image``."""
 import ctypes as C
 import os
 import re
 
 import numpy as np
 import pytest
+import torch
 
+import compose_refs as cr
 from brushstroke_engine_amd import _lib, build, painting
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,21 +91,44 @@ def test_header_and_binding_agree_on_the_entries(library):
     assert "nb_geomprep.hip" in build.SOURCES
 
 
-class _NoPrepOps(painting.TileOpsBase):
-    """What the CPU stand-ins of TileOps look like to paint_drawing: no preparation kernels."""
-    patch_width = 128
+def test_the_base_ops_restate_the_preparation_and_tile_ops_overrides_it():
+    """The CPU stand-ins inherit the host restatements; TileOps overrides them with the kernels."""
+    for name in ("prepare_geometry", "stroke_counts", "composite_on_white", "raster_strokes"):
+        assert hasattr(painting.TileOpsBase, name) and getattr(painting.TileOps, name) is not getattr(painting.TileOpsBase, name)
+    ops = painting.TileOpsBase()
+    rs = np.random.RandomState(2)
+    geom = np.where(rs.rand(45, 70) < 0.3, 0, 255).astype(np.uint8)
+    counts = ops.stroke_counts(torch.from_numpy(geom), 32, 20, 2, 3)
+    padded = np.full((20 + 32, 40 + 32 + 10), 255, np.uint8)
+    padded[:45, :70] = geom
+    want = [[int((padded[y:y + 32, x:x + 32] == 0).sum()) for x in (0, 20, 40)] for y in (0, 20)]
+    assert counts.dtype == torch.int32 and counts.tolist() == want and min(map(min, want)) > 10
+    assert painting.tiles_with_strokes(np.array([[11, 10, 0], [0, 12, 300]]), 7).tolist() == [[0, 0], [7, 7], [7, 14]]
+    img = rs.randint(0, 256, (21, 33, 4)).astype(np.uint8)
+    out = ops.prepare_geometry(img, (40, 50), (3, 5))
+    want = np.full((40, 50), 255, np.uint8)
+    want[3:24, 5:38] = painting.prepare_geometry_image(img)[..., 0]
+    assert out.dtype == torch.uint8 and np.array_equal(out.numpy(), want) and (want[3:24, 5:38] == 0).any()
+    canvas = torch.from_numpy(rs.randint(0, 256, (30, 40, 4)).astype(np.uint8))
+    a = canvas[2:22, 3:33, 3:].numpy().astype(np.float32) / np.float32(255)
+    white = (canvas[2:22, 3:33, :3].numpy().astype(np.float32) * a + 255 * (1 - a)).clip(0, 255).astype(np.uint8)
+    assert np.array_equal(ops.composite_on_white(canvas, 2, 3, 20, 30).numpy(), white)
 
 
-def test_paint_drawing_falls_back_to_the_numpy_helpers(monkeypatch):
-    helper = painting.PaintingHelper(_NoPrepOps())
-    rgba = np.zeros((40, 50, 4), np.uint8)
-    rgba[8:12, :, 3] = 255
-    seen = {}
+def test_paint_drawing_on_the_oracle_ops_equals_the_host_route():
+    """``paint_drawing`` takes its one route -- ``_paint_padded`` -- on the oracle-backed ops and returns the bytes of
+    ``paint_image(prepare_geometry_image(rgba), ...)``, in every case of ``cr.ROUTE_CASES`` (1-2 s each)."""
+    geom = cr.route_geometry()
+    rgba = np.zeros(cr.ROUTE_SIZE + (4,), np.uint8)
+    rgba[geom[..., 0] == 0] = (0, 0, 0, 255)                          # the strokes, opaque black on a transparent sheet
+    assert np.array_equal(painting.prepare_geometry_image(rgba), geom)
+    for case in cr.ROUTE_CASES:
+        print("case (level, mode, on_white):", case)
+        cr.check_same_as_host_route(lambda helper, opts, **kw: helper.paint_drawing(rgba, opts, **kw), case)
 
-    def fake_paint_image(geom, opts, **kw):
-        seen.update(geom=geom, opts=opts, **kw)
-        return "painted"
-    monkeypatch.setattr(helper, "paint_image", fake_paint_image)
-    assert helper.paint_drawing(rgba, "opts", crop_margin=7, stitching_mode="stroke", on_white=True) == "painted"
-    assert np.array_equal(seen["geom"], painting.prepare_geometry_image(rgba))
-    assert (seen["opts"], seen["crop_margin"], seen["stitching_mode"], seen["on_white"], seen["return_full"]) == ("opts", 7, "stroke", True, False)
+
+def test_paint_drawing_refuses_other_than_uint8_drawings():
+    helper = cr.route_helper(0)
+    for bad in (np.zeros((40, 50, 4), np.float32), np.zeros((40, 50, 2), np.uint8), np.zeros((40,), np.uint8)):
+        with pytest.raises(ValueError):
+            helper.paint_drawing(bad, painting.GanBrushOptions())

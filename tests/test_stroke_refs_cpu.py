@@ -1,7 +1,7 @@
 """Vector strokes, the parts that need no GPU: the float64 restatements (tests/stroke_refs.py) against the reference's recorded
 spline samples, the numpy route of ``painting`` against them, ``StrokeList``, the host-side argument checks of the three entries of
-``csrc/nb_strokes.hip``, the ``--strokes`` arguments of ``paint_image_main`` -- and the band condition the device tests rely on,
-checked here on the reference alone."""
+``csrc/nb_strokes.hip``, ``paint_strokes`` on the oracle-backed ops against the host route ``paint_image``, the ``--strokes``
+arguments of ``paint_image_main`` -- and the band condition the device tests rely on, checked here on the reference alone."""
 import ctypes as C
 import json
 import os
@@ -9,7 +9,9 @@ import re
 
 import numpy as np
 import pytest
+import torch
 
+import compose_refs as cr
 import stroke_refs as sr
 from conftest import load_golden
 from brushstroke_engine_amd import _lib, build, paint_image_main, painting
@@ -237,31 +239,38 @@ def test_header_and_binding_agree_on_the_entries(library):
     common = open(os.path.join(REPO, "brushstroke_engine_amd", "csrc", "nb_common.h")).read()
     assert int(re.search(r"#define NB_ABI_VERSION (\d+)", common).group(1)) == _lib.ABI_VERSION >= 19
     assert "nb_strokes.hip" in build.SOURCES and "-fno-slp-vectorize" in build.FILE_FLAGS["nb_strokes.hip"]
-    assert not hasattr(painting.TileOpsBase, "raster_strokes") and hasattr(painting.TileOps, "raster_strokes")
+    # the CPU stand-ins inherit the numpy restatement; TileOps overrides it with the kernels
+    assert hasattr(painting.TileOpsBase, "raster_strokes") and painting.TileOps.raster_strokes is not painting.TileOpsBase.raster_strokes
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# paint_strokes without the kernels, and the command line
+# paint_strokes on the oracle-backed ops, and the command line
 # ---------------------------------------------------------------------------------------------------------------------
-class _NoKernelOps(painting.TileOpsBase):
-    """What the CPU stand-ins of TileOps look like to paint_strokes: no stroke kernels."""
-    patch_width = 128
+def test_base_raster_strokes_is_the_numpy_restatement():
+    strokes, ops = sr.e2e_strokes(), painting.TileOpsBase()
+    h, w = sr.E2E_SIZE[0] + 20, sr.E2E_SIZE[1] + 20
+    want = painting.raster_strokes_numpy(strokes, (h, w), (10, 10), subdiv=8)
+    got = ops.raster_strokes(strokes, (h, w), (10, 10))
+    assert got.dtype == torch.uint8 and np.array_equal(got.numpy(), want) and 0 < (want == 0).mean() < 0.2
+    # ``out`` given: darkened in place, every other byte as it was
+    base = np.random.RandomState(1).randint(1, 256, (h, w)).astype(np.uint8)
+    out = torch.from_numpy(base.copy())
+    assert ops.raster_strokes(strokes, offset=(10, 10), out=out) is out
+    assert np.array_equal(out.numpy(), np.where(want == 0, 0, base))
 
 
-def test_paint_strokes_falls_back_to_the_numpy_restatement(monkeypatch):
-    helper = painting.PaintingHelper(_NoKernelOps())
-    strokes = sr.e2e_strokes()
-    seen = {}
+def test_paint_strokes_on_the_oracle_ops_equals_the_host_route():
+    """``paint_strokes`` takes its one route -- raster, clear the padding, ``_paint_padded`` -- on the oracle-backed ops and returns the
+    bytes of ``paint_image(raster_strokes_numpy(strokes, size)[..., None], ...)``, in every case of ``cr.ROUTE_CASES`` (1-2 s each)."""
+    strokes = cr.session_strokes()[0]
+    for case in cr.ROUTE_CASES:
+        print("case (level, mode, on_white):", case)
+        cr.check_same_as_host_route(lambda helper, opts, **kw: helper.paint_strokes(strokes, cr.ROUTE_SIZE, opts, **kw), case)
 
-    def fake_paint_image(geom, opts, **kw):
-        seen.update(geom=geom, opts=opts, **kw)
-        return "painted"
-    monkeypatch.setattr(helper, "paint_image", fake_paint_image)
-    assert helper.paint_strokes(strokes, (90, 120), "opts", crop_margin=7, stitching_mode="stroke", on_white=True) == "painted"
-    assert np.array_equal(seen["geom"], painting.raster_strokes_numpy(strokes, (90, 120), (0, 0), 8)) and (seen["geom"] == 0).any()
-    assert (seen["opts"], seen["crop_margin"], seen["stitching_mode"], seen["on_white"], seen["return_full"]) == ("opts", 7, "stroke", True, False)
+
+def test_paint_strokes_refuses_an_empty_drawing():
     with pytest.raises(ValueError):
-        helper.paint_strokes(strokes, (0, 120), "opts")
+        cr.route_helper(0).paint_strokes(cr.session_strokes()[0], (0, 120), painting.GanBrushOptions())
 
 
 def test_parser_takes_strokes_or_a_drawing(capsys):
