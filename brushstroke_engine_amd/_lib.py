@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _lock = threading.Lock()
 _lib = None
@@ -163,6 +163,8 @@ PROTOTYPES = {
     "nb_over_tiles_u8": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, vp]),
     "nb_canvas_view_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    # masked selection (csrc/nb_select.hip): the k-th largest included value of every image
+    "nb_masked_kth_largest_f32": (C.c_int, [vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),

@@ -245,13 +245,19 @@ class LazyGeometry:
         return self._plain
 
     def encode_for(self, targets) -> List[Optional[torch.Tensor]]:
-        if self._plain is not None or not targets:
+        # (targets are honoured even when the plain features exist already -- somebody indexed the provider --: the generator has
+        # registered the operand tensors it expects the encoder to fill, and skips its own packing for them)
+        if not targets:
             return self.plain()
         return self.encoder.encode(self.geom, targets=targets)
 
     def sliced(self, a: int, b: int) -> "LazyGeometry":
         """The provider of samples a..b-1 (the generator runs a large batch as sub-batches on separate streams)."""
         return LazyGeometry(self.encoder, self.geom[a:b])
+
+    def repeated(self, times: int) -> "LazyGeometry":
+        """The provider of the whole batch ``times`` times over (sample t * n + i is sample i): the calibration drawings of several brushes."""
+        return LazyGeometry(self.encoder, self.geom.repeat(times, 1, 1, 1))
 
     def can_handoff(self, i: int) -> bool:
         return self.encoder.can_handoff(self.geom.shape[2], i)

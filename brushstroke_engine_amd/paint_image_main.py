@@ -29,10 +29,22 @@ from .networks import DEFAULT_CONV_MODE, Generator
 logger = logging.getLogger(__name__)
 
 
-def set_colors(color_mode: str, brush_options) -> None:
-    """``paint_image_main.py:66-85`` for explicit colors: 'r,g,b;r,g,b;r,g,b' (empty entries keep the style's color)."""
+def set_colors(color_mode: str, brush_options, library=None, mapper=None, style_id=None, style_id2=None) -> None:
+    """``paint_image_main.py:66-85``: '1' / '2' paint with the two stroke colours the generator gives ``style_id`` / ``style_id2``
+    (``mapper.get_colors_raw``); anything else is explicit colours 'r,g,b;r,g,b;r,g,b' (empty entries keep the style's color)."""
     if color_mode in ("1", "2"):
-        raise RuntimeError("color modes 1/2 (colors of another style) need StyleUVSMapper.get_colors_raw; pass explicit RGB")
+        if mapper is None:
+            raise RuntimeError(f"--color_mode {color_mode} (the colours of another style) renders that style on the calibration "
+                               f"drawings: it needs --uvs_calibration (and no --no_uvs_mapping)")
+        sid = style_id if color_mode == "1" else style_id2
+        if sid is None:
+            raise RuntimeError(f"--color_mode {color_mode} needs --style_id{'' if color_mode == '1' else '2'}")
+        other = painting.GanBrushOptions()
+        library.set_style(sid, other)
+        colors = mapper.get_colors_raw(other).detach().cpu()
+        brush_options.set_color(0, colors[0, :, 0] / 2 + 0.5)
+        brush_options.set_color(1, colors[0, :, 1] / 2 + 0.5)
+        return
     for i, cspec in enumerate(color_mode.split(";")):
         if cspec:
             rgb = [int(x) for x in cspec.split(",")]
@@ -112,7 +124,8 @@ def main(argv=None) -> str:
     opts = painting.GanBrushOptions()
     opts.enable_uvs_mapping = mapper is not None
     if args.color_mode is not None:
-        set_colors(args.color_mode, opts)
+        with torch.no_grad():
+            set_colors(args.color_mode, opts, library, mapper, args.style_id, args.style_id2)
     if args.style_id2 is None:
         library.set_style(args.style_id, opts)
     else:

@@ -110,33 +110,193 @@ class StyleUVSMapper:
     (``nb_torgb_triad_f32(sfactor=...)``).  The reference calibrates on five bundled drawings at two stroke widths
     (``*_rad016.png`` / ``*_rad025.png``); they are data files of the reference, so the caller supplies them."""
 
+    TOP_K = 15                   # the factor comes from the 15th largest background weight of a drawing (mapper.py:132)
+    DEFAULT_BATCH = 32           # samples per generator pass of ``calibrate`` / ``catalogue``: floor(batch / K) brushes x K drawings
+
     def __init__(self, ops, cal_medium: Optional[np.ndarray] = None, cal_thick: Optional[np.ndarray] = None):
         self.ops = ops
         self.sfactors: Dict = {}
         self.geom_feature = self.bmask = None
+        self._features: Dict = {}
         if cal_medium is not None:
             self.set_calibration(cal_medium, cal_thick)
 
     def set_calibration(self, cal_medium: np.ndarray, cal_thick: np.ndarray):
-        """[k,R,R] uint8 drawings, 0 = stroke: medium strokes are rendered, thick ones define "surely background"."""
-        geo = (self.ops.to_device(np.asarray(cal_medium, np.uint8)).to(torch.float32) / 255).unsqueeze(1)
+        """[k,R,R] uint8 drawings, 0 = stroke: medium strokes are rendered, thick ones define "surely background".  RuntimeError if
+        a thick drawing leaves fewer than ``TOP_K`` background pixels (checked here, on the host, once: ``calibrate`` never needs the
+        counts back from the device)."""
+        cal_medium, cal_thick = np.asarray(cal_medium, np.uint8), np.asarray(cal_thick, np.uint8)
+        background = (cal_thick.astype(np.float32) / np.float32(255) > np.float32(0.99)).reshape(cal_thick.shape[0], -1).sum(axis=1)
+        for i, cnt in enumerate(background.tolist()):
+            if cnt < self.TOP_K:
+                raise RuntimeError(f"StyleUVSMapper: thick calibration drawing {i} leaves {cnt} background pixels; the factor is taken "
+                                   f"from the {self.TOP_K} largest")
+        geo = (self.ops.to_device(cal_medium).to(torch.float32) / 255).unsqueeze(1)
         self.geom_feature = self.ops.encode(geo)
-        self.bmask = (self.ops.to_device(np.asarray(cal_thick, np.uint8)).to(torch.float32) / 255).unsqueeze(1) > 0.99
-        self.sfactors = {}
+        self.bmask = (self.ops.to_device(cal_thick).to(torch.float32) / 255).unsqueeze(1) > 0.99
+        self.sfactors, self._features = {}, {}
+
+    # -- rendering on the calibration drawings --
+    def _need_calibration(self):
+        if self.geom_feature is None:
+            raise RuntimeError("StyleUVSMapper: no calibration drawings set (set_calibration)")
+
+    def _geometry(self, nb: int, first_only: bool = False):
+        """Geometry features of ``nb`` brushes on all K drawings (brush-major: sample b * K + d is brush b on drawing d), or of one
+        brush on drawing 0 only (``[x[:1] for x in geom_feature]``, mapper.py:98).  Feature tensors are repeated; a provider the generator
+        evaluates itself (``encoder.LazyGeometry``) repeats its drawings, and the encoder hands its output over the way it does for tiles."""
+        if nb == 1 and not first_only:
+            return self.geom_feature
+        key = (nb, first_only)
+        if key not in self._features:
+            f = self.geom_feature
+            if first_only:
+                self._features[key] = f.sliced(0, 1) if hasattr(f, "sliced") else [x[:1] for x in f]
+            else:
+                self._features[key] = f.repeated(nb) if hasattr(f, "repeated") else [x.repeat(nb, 1, 1, 1) for x in f]
+        return self._features[key]
+
+    def _render(self, opts_list: Sequence, first_only: bool = False):
+        """(img, debug data) of one un-positioned generator pass: every brush of ``opts_list`` on all K drawings, or on drawing 0 only.
+        Without the brushes' noise buffers, as the reference (mapper.py:80-92)."""
+        self._need_calibration()
+        reps = 1 if first_only else self.bmask.shape[0]
+        ws = torch.cat([self.ops.map_style(z=o.style_z, ws=o.style_ws) for o in opts_list])
+        return self.ops.triad_debug(ws.repeat_interleave(reps, 0).contiguous(), self._geometry(len(opts_list), first_only))
+
+    def _pass_sfactors(self, uvs: torch.Tensor, nb: int) -> torch.Tensor:
+        """[nb] factors from the ``uvs`` [nb * K,3,R,R] of a pass: one selection launch on ``uvs[:, 2]`` in place, then the parent
+        formula's own operations (minimum over the drawings, reciprocal)."""
+        kth, _ = self.ops.masked_kth_largest(uvs[:, 2], self.bmask, self.TOP_K)
+        return 1 / kth.view(nb, self.bmask.shape[0]).min(dim=1)[0]
+
+    def _per_pass(self, batch: Optional[int]) -> int:
+        batch = self.DEFAULT_BATCH if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError(f"StyleUVSMapper: batch {batch} must be positive")
+        return max(1, batch // self.bmask.shape[0])
+
+    def calibrate(self, opts_list: Sequence, batch: Optional[int] = None) -> torch.Tensor:
+        """The factors [B] of the brushes ``opts_list`` on the device, ``floor(batch / K)`` brushes per generator pass (batch 32 and the
+        five drawings: six), the last pass ragged.  Nothing here waits for the device.  Fills the cache for every ``opts`` that has a
+        ``style_id``."""
+        self._need_calibration()
+        opts_list, per = list(opts_list), self._per_pass(batch)
+        parts = [self._pass_sfactors(self._render(opts_list[a:a + per])[1]["uvs"], len(opts_list[a:a + per]))
+                 for a in range(0, len(opts_list), per)]
+        sf = torch.cat(parts) if parts else torch.empty([0], dtype=torch.float32, device=self.bmask.device)
+        self._remember(opts_list, sf)
+        return sf
+
+    def _remember(self, opts_list, sf: torch.Tensor):
+        for i, o in enumerate(opts_list):
+            if o.style_id is not None:
+                self.sfactors[o.style_id] = sf[i]
 
     def get_sfactor(self, opts) -> torch.Tensor:
         if opts.style_id is not None and opts.style_id in self.sfactors:
             return self.sfactors[opts.style_id]
-        if self.geom_feature is None:
-            raise RuntimeError("StyleUVSMapper: no calibration drawings set (set_calibration)")
-        n = self.geom_feature[0].shape[0]
-        ws = self.ops.map_style(z=opts.style_z, ws=opts.style_ws).expand(n, -1, -1).contiguous()
-        S = self.ops.background_weight(ws, self.geom_feature)
-        val = torch.stack([torch.topk(S[i][self.bmask[i]], k=15)[0].min() for i in range(n)]).min()
-        sfactor = 1 / val
-        if opts.style_id is not None:
-            self.sfactors[opts.style_id] = sfactor
-        return sfactor
+        return self.calibrate([opts])[0]
+
+    # -- a brush's colours and icon (mapper.py:74-78, 94-115): the render on the first calibration drawing --
+    @staticmethod
+    def color_spec(colors) -> str:
+        """'rgb(r,g,b):rgb(r,g,b):rgb(r,g,b)' of ``colors`` [1,3(rgb),3(k)] in -1..1, truncated as the reference does."""
+        c = ((torch.as_tensor(colors)[0].detach().cpu() / 2 + 0.5) * 255).to(torch.uint8).numpy()
+        return ":".join("rgb(%s)" % ",".join(str(int(x)) for x in c[:, i]) for i in range(3))
+
+    @staticmethod
+    def _icons(img: torch.Tensor, uvs: torch.Tensor, on_white: bool) -> torch.Tensor:
+        """[n,R,R,3] uint8 where ``img`` is: the renders, over white by the background weight if asked, in the reference's operation order."""
+        if on_white:
+            img = img * (1 - uvs[:, 2:]) + uvs[:, 2:]
+        return ((img.permute(0, 2, 3, 1) / 2 + 0.5) * 255).to(torch.uint8)
+
+    def get_colors_raw(self, opts) -> torch.Tensor:
+        """[1,3(rgb),3(k)] in -1..1: the three colours the generator gives the brush."""
+        return self._render([opts], first_only=True)[1]["colors"]
+
+    def get_colors(self, opts) -> str:
+        return self.color_spec(self.get_colors_raw(opts))
+
+    def get_brush_icon(self, opts, on_white: bool = True) -> np.ndarray:
+        """[R,R,3] uint8: the brush on the first calibration drawing."""
+        img, dbg = self._render([opts], first_only=True)
+        return self.ops.to_host(self._icons(img, dbg["uvs"], on_white)[0].contiguous())
+
+    # -- a whole library --
+    def catalogue(self, library, style_ids: Optional[Sequence] = None, batch: Optional[int] = None, on_white: bool = True,
+                  icon_k: int = 1) -> "BrushCatalogue":
+        """Icon, colours and factor of every brush of ``library`` (of ``style_ids``, in that order, if given): one generator pass per
+        ``floor(batch / K)`` brushes serves all three -- sample b * K of a pass is brush b on drawing 0 (colours, icon), its K samples
+        give the factor.  ``icon_k`` in 1..16, a divisor of R, reduces the icons on the device (``ops.canvas_view`` on the icons stacked
+        as an opaque canvas); only the reduced icons, the colours and the factors are copied to the host.  Fills the factor cache like
+        ``calibrate``."""
+        self._need_calibration()
+        R, K, icon_k = self.ops.patch_width, self.bmask.shape[0], int(icon_k)
+        if not 1 <= icon_k <= 16 or R % icon_k:
+            raise ValueError(f"catalogue: icon_k {icon_k} must lie in 1..16 and divide the patch width {R}")
+        ids = list(library.get_style_ids() if style_ids is None else style_ids)
+        opts_list, per = [], self._per_pass(batch)
+        for sid in ids:
+            opts_list.append(GanBrushOptions())
+            library.set_style(sid, opts_list[-1])
+        sf, colors, icons = [], [], []
+        for a in range(0, len(ids), per):
+            nb = len(opts_list[a:a + per])
+            img, dbg = self._render(opts_list[a:a + per])
+            sf.append(self._pass_sfactors(dbg["uvs"], nb))
+            colors.append(dbg["colors"][::K])
+            icons.append(self._icons(img[::K], dbg["uvs"][::K], on_white))
+        dev, r = self.bmask.device, R // icon_k
+        if not ids:
+            return BrushCatalogue([], [], np.zeros([0, 3, 3], np.float32), [], np.zeros([0], np.float32), np.zeros([0, r, r, 3], np.uint8))
+        sf, colors, icons = torch.cat(sf), torch.cat(colors).contiguous(), torch.cat(icons)
+        self._remember(opts_list, sf)
+        if icon_k > 1:
+            small = []
+            for a in range(0, len(ids), 64):                       # (groups keep the view's window within its launch limits)
+                grp = icons[a:a + 64]
+                nb = grp.shape[0]
+                canvas = torch.cat([grp, torch.full([nb, R, R, 1], 255, dtype=torch.uint8, device=dev)], dim=3).reshape(nb * R, R, 4)
+                small.append(self.ops.canvas_view(canvas.contiguous(), 0, 0, nb * R, R, icon_k)[..., :3].reshape(nb, r, r, 3))
+            icons = torch.cat(small)
+        colors = self.ops.to_host(colors)
+        return BrushCatalogue(ids, opts_list, colors, [self.color_spec(colors[i:i + 1]) for i in range(len(ids))],
+                              self.ops.to_host(sf.contiguous()), self.ops.to_host(icons.contiguous()))
+
+
+@dataclasses.dataclass
+class BrushCatalogue:
+    """What a brush picker shows for a library (``StyleUVSMapper.catalogue``), on the host."""
+    ids: List
+    opts: List[GanBrushOptions]        # what ``library.set_style`` produced: paint with these (a ``rand<N>`` id cannot be drawn again)
+    colors_raw: np.ndarray             # [B,3(rgb),3(k)] float32 in -1..1
+    color_specs: List[str]             # 'rgb(r,g,b):rgb(r,g,b):rgb(r,g,b)' per brush
+    sfactors: np.ndarray               # [B] float32 clear-background factors
+    icons: np.ndarray                  # [B, R/icon_k, R/icon_k, 3] uint8
+
+    def to_json(self) -> str:
+        import json
+        return json.dumps({"ids": [str(i) for i in self.ids], "color_specs": list(self.color_specs),
+                           "sfactors": [float(s) for s in self.sfactors]})
+
+    def sheet(self, cols: int = 10) -> np.ndarray:
+        """The icons side by side, ``cols`` per row, on white: [rows * r, cols * r, 3] uint8."""
+        n, r = self.icons.shape[0], self.icons.shape[1]
+        cols = max(1, min(int(cols), max(n, 1)))
+        rows = max(1, -(-n // cols))
+        out = np.full((rows * r, cols * r, 3), 255, np.uint8)
+        for i in range(n):
+            y, x = (i // cols) * r, (i % cols) * r
+            out[y:y + r, x:x + r] = self.icons[i]
+        return out
+
+    def save_sheet(self, path: str, cols: int = 10) -> str:
+        from PIL import Image
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        Image.fromarray(self.sheet(cols)).save(path)
+        return path
 
 
 def crop_drawing(ops, canvas: torch.Tensor, m: int, size_hw, on_white: bool) -> np.ndarray:

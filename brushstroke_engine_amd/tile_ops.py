@@ -8,6 +8,7 @@ that has one.  The drivers call ``ops.<operation>`` and never ask which ops they
 from __future__ import annotations
 
 import contextlib
+import inspect
 import os
 import time
 from typing import Optional, Tuple
@@ -107,11 +108,24 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _select_shapes(x: torch.Tensor, mask: torch.Tensor, k: int) -> Tuple[int, int, int]:
+    """(n, count, m) of a ``masked_kth_largest`` call, or ValueError."""
+    if x.dtype != torch.float32 or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[1] != 1) or x.shape[0] < 1:
+        raise ValueError(f"masked_kth_largest: float32 [n,1,h,w] or [n,h,w] expected, got {x.dtype} {tuple(x.shape)}")
+    n, count = x.shape[0], x.shape[-2] * x.shape[-1]
+    if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() < 1 or mask.shape[0] < 1 or mask.numel() != mask.shape[0] * count:
+        raise ValueError(f"masked_kth_largest: bool / uint8 masks [m, ...] of {count} elements each expected, got {mask.dtype} "
+                         f"{tuple(mask.shape)}")
+    if int(k) < 1 or count < 1:
+        raise ValueError(f"masked_kth_largest: k = {k} and {count} elements per image: both must be at least 1")
+    return n, count, mask.shape[0]
+
+
 class TileOpsBase:
     """What ``PaintingHelper`` and ``PaintSession`` call on their ``ops``, as far as it can be said without a device: the scheduling
     hooks, with defaults that do nothing (one stream, no workspaces to prepare, no noise sets, no captured graphs), and the host
-    restatement of every operation that has one (drawing preparation, stroke raster, tile counts, on-white, compositing, view), on
-    host tensors.  ``TileOps`` overrides all of them; the CPU stand-ins of the tests derive from this class and define only what has
+    restatement of every operation that has one (drawing preparation, stroke raster, tile counts, on-white, compositing, view, the
+    masked selection and the un-positioned render of the brush calibration), on host tensors.  ``TileOps`` overrides all of them; the CPU stand-ins of the tests derive from this class and define only what has
     no restatement here (``to_device``, ``geom_tiles``, ``encode``, ``head`` / ``tail`` / ``full``, the feature-canvas operations, ``paste``)."""
     n_streams = 1
     stream_policy = 0
@@ -170,6 +184,35 @@ class TileOpsBase:
             raster_strokes_numpy(strokes, None, offset, subdiv, out.numpy())
             return out
         return torch.from_numpy(raster_strokes_numpy(strokes, (int(out_shape[0]), int(out_shape[1])), offset, subdiv))
+
+    # -- brush calibration: the torch restatements (``TileOps`` runs csrc/nb_select.hip and the HIP generator) --
+    def masked_kth_largest(self, x: torch.Tensor, mask: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(kth [n] float32, n_masked [n] int32): per image of ``x`` [n,1,h,w] or [n,h,w] (a strided view is fine) the ``k``-th largest
+        of the values that ``mask`` [m, ...] (bool or uint8; image i takes mask i % m) includes, in the order of
+        ``torch.topk(largest=True)``: NaN above +inf.  NaN where fewer than ``k`` values are included."""
+        n, count, m = _select_shapes(x, mask, k)
+        flat, inc = x.reshape(n, count), mask.reshape(m, count) != 0
+        kth = torch.full([n], float("nan"), dtype=torch.float32, device=x.device)
+        n_masked = torch.zeros([n], dtype=torch.int32, device=x.device)
+        for i in range(n):
+            v = flat[i][inc[i % m]]
+            n_masked[i] = v.numel()
+            if v.numel() >= k:
+                kth[i] = torch.topk(v, k)[0][k - 1]
+        return kth, n_masked
+
+    def triad_debug(self, ws: torch.Tensor, geom_feats):
+        """(img [n,3,R,R], debug data with ``uvs`` [n,3,R,R] and ``colors`` [n,3,3]) of an un-positioned render with the checkpoint's
+        constant noise and without brush noise buffers: what StyleUVSMapper renders (mapper.py:80-92).  This restatement renders
+        sample by sample: torch picks its matrix routines by batch size, and a sample's result must not depend on what else is in the
+        batch (the batched catalogue is held to the one-brush calls bit for bit on this route)."""
+        syn = getattr(self.G.synthesis, "forward", self.G.synthesis)
+        takes = any(p.name == "noise_mode" or p.kind is p.VAR_KEYWORD for p in inspect.signature(syn).parameters.values())
+        kw = {"noise_mode": "const"} if takes else {}
+        feats = list(geom_feats)
+        outs = [self.G.forward_pre_mapped(ws[i:i + 1], [f[i:i + 1] for f in feats], return_debug_data=True, **kw) for i in range(ws.shape[0])]
+        dbg = {k: torch.cat([d[k] for _, d in outs]) for k in ("uvs", "colors")}
+        return torch.cat([img for img, _ in outs]), dbg
 
     # -- compositing: the numpy restatements, on host tensors (``TileOps`` runs the kernels of csrc/nb_compose.hip) --
     def over_tiles(self, canvas, tiles_u8, dst_yx, crop, cell_off, cell_tiles, box=None, mode: int = 0, opacity: int = 255) -> None:
@@ -435,8 +478,31 @@ class TileOps(TileOpsBase):
 
     def background_weight(self, ws, geom_feats) -> torch.Tensor:
         """S = uvs[:, 2:3] of an un-positioned render (what StyleUVSMapper calibrates on, mapper.py:74-87)."""
-        _, dbg = self.G.forward_pre_mapped(ws, geom_feats, return_debug_data=True, noise_mode="const")
-        return dbg["uvs"][:, 2:3]
+        return self.triad_debug(ws, geom_feats)[1]["uvs"][:, 2:3]
+
+    def triad_debug(self, ws: torch.Tensor, geom_feats):
+        """(img, debug data with ``uvs`` and ``colors``) of ONE un-positioned generator pass over the batch, constant noise."""
+        return self.G.forward_pre_mapped(ws, geom_feats, return_debug_data=True, noise_mode="const")
+
+    # -- masked selection (csrc/nb_select.hip) --
+    def masked_kth_largest(self, x: torch.Tensor, mask: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(kth [n] float32, n_masked [n] int32) on the device, one launch (``nb_masked_kth_largest_f32``): per image of ``x``
+        [n,1,h,w] or [n,h,w] the ``k``-th largest of the values that ``mask`` [m, ...] (bool or uint8; image i takes mask i % m)
+        includes, NaN above +inf; NaN where fewer than ``k`` are included.  A view whose images are dense (``uvs[:, 2]``) is read in place."""
+        n, count, m = _select_shapes(x, mask, k)
+        if x.device != self.device or mask.device != self.device:
+            raise ValueError("masked_kth_largest: x and mask must be on the engine's device")
+        w = x.shape[-1]
+        if x.stride(-1) != 1 or x.stride(-2) != w or (n > 1 and x.stride(0) < count):
+            x = x.contiguous()
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        kth = torch.empty([n], dtype=torch.float32, device=self.device)
+        n_masked = torch.empty([n], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_masked_kth_largest_f32(_p(x), max(int(x.stride(0)), count), _p(mask), m, count, int(k), n, _p(kth),
+                                                            _p(n_masked), self._stream()), "masked_kth_largest")
+        return kth, n_masked
 
     # -- canvas kernels --
     def new_feature_canvas(self, c, hc, wc):

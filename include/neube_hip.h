@@ -641,6 +641,21 @@ int nb_over_tiles_u8(const uint8_t* tiles, int t, int r, const int32_t* dst_yx, 
 int nb_canvas_view_u8(const uint8_t* canvas, int ch, int cw, int y0, int x0, int h, int w, int k, int on_white, uint8_t* out,
                       void* stream);
 
+/* ---- masked selection: the k-th largest included value of every image (csrc/nb_select.hip) ---------------------------------------
+ * What StyleUVSMapper calibrates on (forger/ui/mapper.py:132: `torch.topk(S[i][bmask[i]], k=15)[0].min()` per drawing), for a batch
+ * of images in one launch.  Image i is the `count` floats at x + i * stride_n (stride_n >= count, so images never alias; a stride
+ * lets one channel of an NCHW tensor be read in place) and uses mask (i % n_masks): `count` bytes at mask + (i % n_masks) * count,
+ * non-zero = included.  n_masked[i] = the number of included elements.  kth[i] = the k-th largest included value in the order of
+ * torch.topk(largest=True) on the CPU: every NaN ranks above +inf (a selected NaN comes back as the quiet NaN 0x7fc00000), -0 and +0
+ * compare equal and the sign of a returned zero is unspecified.  Where n_masked[i] < k, kth[i] is a quiet NaN: the caller decides from
+ * n_masked.  Exact (a radix select on the values' bits, integer arithmetic only) and bit-identical from run to run.  No workspace, no
+ * allocation, no synchronisation: the entry only enqueues on `stream`.  x may start at any float; rows that are 16-byte aligned
+ * somewhere are read in 16-byte vectors from there on.  n == 0: NB_OK without a launch.
+ * NB_EINVAL (before any HIP call): a null pointer, k < 1, count < 1, n_masks < 1, n < 0, stride_n < count, x / kth / n_masked not
+ * 4-byte aligned. */
+int nb_masked_kth_largest_f32(const float* x, long long stride_n, const uint8_t* mask, int n_masks, int count, int k, int n,
+                              float* kth, int32_t* n_masked, void* stream);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
