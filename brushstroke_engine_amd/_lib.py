@@ -18,7 +18,7 @@ import torch  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libneube_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _lock = threading.Lock()
 _lib = None
@@ -165,6 +165,9 @@ PROTOTYPES = {
     "nb_canvas_view_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     # masked selection (csrc/nb_select.hip): the k-th largest included value of every image
     "nb_masked_kth_largest_f32": (C.c_int, [vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    # brush scores (csrc/nb_metrics.hip): evaluation masks of the drawings, the per-image sums of the colour and transparency metrics
+    "nb_eval_masks_f32": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "nb_brush_metrics_f32": (C.c_int, [vp, C.c_longlong, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -262,6 +265,7 @@ class NbPassPlan(C.Structure):
 
 NB_GEOM_PREP_WS_BYTES = 1040
 NB_SEG_PITCH = 8
+NB_BRUSH_METRICS_PARTS = 16
 
 NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3
 NB_CONV_MODES = {"f32": 0, "h3": 1, "f8": 2, "f6": 3, "f16": 4}

@@ -1,0 +1,82 @@
+"""Scores of a brush library -- LAB_E%, LAB_L2, BG_CLARITY_MEAN and FG_OPACITY_MEDIAN per brush, the numbers the reference's
+``paint_engine_metric_loop`` reports (forger/metrics/metric_main.py:105-236) -- computed in batches on the device
+(``metrics.BrushEvaluator``).
+
+    python -m brushstroke_engine_amd.brush_metrics_main --gan_checkpoint engine.npz --library rand100 --drawings drawings.npz \\
+        --output_dir out [--uvs_calibration cal.npz] [--rounds 1] [--batch 32] [--seed 0] [--lab_thresh 10] [--prefix ''] [--conv_mode h3]
+
+``--drawings`` is an .npz whose first array (or the one named ``drawings``) holds [K,R,R] uint8 guidance drawings, 0 = stroke.
+``--library`` is what ``paint_image_main`` takes.  Three files are written to ``--output_dir``: ``<prefix>style_metrics.txt`` and
+``<prefix>summary_metrics.txt`` in the reference's line format, and ``<prefix>brush_metrics.json``.  Single process.
+"""
+from __future__ import annotations
+
+import argparse
+import logging
+import os
+
+import numpy as np
+import torch
+
+from . import encoder, formats, launch, metrics, painting
+from .networks import DEFAULT_CONV_MODE, Generator
+
+logger = logging.getLogger(__name__)
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Colour and transparency scores of a brush library on MI355X.")
+    ap.add_argument("--gan_checkpoint", required=True, help=".npz engine container (generator + encoder)")
+    ap.add_argument("--library", default="rand100")
+    ap.add_argument("--drawings", required=True, help=".npz with [K,R,R] uint8 guidance drawings (0 = stroke)")
+    ap.add_argument("--uvs_calibration", default=None, help=".npz with 'medium' and 'thick' calibration drawings: render with the brushes' factors")
+    ap.add_argument("--output_dir", required=True)
+    ap.add_argument("--prefix", default="", help="prefix of the three file names")
+    ap.add_argument("--rounds", type=int, default=1, help="renders per brush, each with fresh primary colours")
+    ap.add_argument("--batch", type=int, default=32, help="samples per generator pass: floor(batch / K) brushes on every drawing")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the colour stream")
+    ap.add_argument("--lab_thresh", type=float, default=10)
+    ap.add_argument("--conv_mode", default=None, choices=["f8", "h3", "f32"],
+                    help="arithmetic of the conv layers (default: networks.DEFAULT_CONV_MODE)")
+    return ap
+
+
+def load_drawings(path: str) -> np.ndarray:
+    with np.load(path) as z:
+        return np.asarray(z["drawings"] if "drawings" in z.files else z[z.files[0]], np.uint8)
+
+
+def write_scores(scores: metrics.BrushScores, out_dir: str, prefix: str = ""):
+    """The two text files of ``BrushScores.write_reference_files`` and ``<prefix>brush_metrics.json``; returns the three paths."""
+    style, summary = scores.write_reference_files(out_dir, prefix)
+    info = os.path.join(out_dir, f"{prefix}brush_metrics.json")
+    with open(info, "w") as f:
+        f.write(scores.to_json())
+    return style, summary, info
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    _, _, device, _ = launch.init()                  # kernel library first, then the device
+    cfg, gen_sd, enc_sd, preproc, _ = formats.load_engine_snapshot(args.gan_checkpoint)
+    G = Generator(cfg, gen_sd, conv_mode=args.conv_mode or DEFAULT_CONV_MODE).to(device)
+    if not encoder.HipGeometryEncoder.supports(cfg.img_resolution):
+        raise RuntimeError(f"the geometry-encoder kernels tile patches of 32, 64 or 128 k pixels; this checkpoint paints {cfg.img_resolution}")
+    ops = painting.TileOps(G, encoder.HipGeometryEncoder(enc_sd, preproc_type=preproc, device=device))
+    mapper = None
+    if args.uvs_calibration:
+        with np.load(args.uvs_calibration) as z:
+            mapper = painting.StyleUVSMapper(ops, z["medium"], z["thick"])
+    library = formats.BrushLibrary.from_arg(args.library, z_dim=G.z_dim)
+    with torch.no_grad():
+        evaluator = metrics.BrushEvaluator(ops, load_drawings(args.drawings), seed=args.seed, uvs_mapper=mapper)
+        scores = evaluator.evaluate(library, rounds=args.rounds, batch=args.batch, lab_thresh=args.lab_thresh)
+    paths = write_scores(scores, args.output_dir, args.prefix)
+    logger.info(f"Scored {len(scores.ids)} brushes: {paths}")
+    for p in paths:
+        print(p)
+    return paths
+
+
+if __name__ == "__main__":
+    main()

@@ -5,7 +5,7 @@
 #include <cstdarg>
 #include "../../include/neube_hip.h"
 
-#define NB_ABI_VERSION 21
+#define NB_ABI_VERSION 22
 
 // Squared styles one styles workgroup keeps in LDS (nb_ops.hip).  nb_styles_fast_f32 needs every layer's c_aff <= NB_MAX_AFF;
 // nb_styles_f32 reads the squares of the entries past it back from the styles it has just written.  The planner picks the fast

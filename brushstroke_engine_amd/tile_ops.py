@@ -8,6 +8,7 @@ that has one.  The drivers call ``ops.<operation>`` and never ask which ops they
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import inspect
 import os
 import time
@@ -121,11 +122,73 @@ def _select_shapes(x: torch.Tensor, mask: torch.Tensor, k: int) -> Tuple[int, in
     return n, count, mask.shape[0]
 
 
+# ------------------------------------------------------------------------------------------------
+# brush scores (csrc/nb_metrics.hip): the reference's own operations, in its order, in float32 torch
+# ------------------------------------------------------------------------------------------------
+BG_THRESH, FG_THRESH = 0.999, 0.3          # compute_transparency_metrics (forger/metrics/geom_metric.py:156-157)
+
+
+@dataclasses.dataclass
+class EvalMasks:
+    """What ``eval_masks`` leaves for ``brush_metrics``, where the drawings are."""
+    geom: torch.Tensor               # [K,R,R] float32, 0 = stroke
+    blur: torch.Tensor               # [K,R,R] float32: the 5x5 Gaussian applied twice, zero padding at each application
+    mask: torch.Tensor               # [K,R,R] uint8: bit 0 = background (blur > 0.999), bit 1 = foreground (geom < 0.3)
+    n_bg: torch.Tensor               # [K] int32
+    n_fg: torch.Tensor               # [K] int32
+
+
+def gaussian_blur_torch(img: torch.Tensor) -> torch.Tensor:
+    """``default_gaussian_smoothing`` (geom_metric.py:73-129) on [n,1,h,w]: 5x5, sigma 1, normalised, zero padding 2."""
+    ax = torch.arange(5, dtype=torch.float32)
+    g = 1 / (1 * np.sqrt(2 * np.pi)) * torch.exp(-((ax - 2) / 1) ** 2 / 2)
+    kernel = g[:, None] * g[None, :]
+    kernel = (kernel / torch.sum(kernel)).view(1, 1, 5, 5).to(img.device)
+    return torch.nn.functional.conv2d(img, kernel, padding=2)
+
+
+def rgb2lab_torch(srgb: torch.Tensor) -> torch.Tensor:
+    """``rgb2lab`` (forger/util/color.py:52-140) on [..., 3] in the dtype of ``srgb``, operation by operation."""
+    t, dev = srgb.dtype, srgb.device
+    lin = (srgb / 12.92 * (srgb <= 0.04045).to(t)) + (((srgb + 0.055) / 1.055) ** 2.4) * (srgb > 0.04045).to(t)
+    xyz = torch.matmul(lin, torch.tensor([[0.412453, 0.212671, 0.019334], [0.357580, 0.715160, 0.119193],
+                                          [0.180423, 0.072169, 0.950227]], dtype=t, device=dev))
+    xyz = xyz * torch.tensor([1.0 / 0.95047, 1.0, 1.0 / 1.08883], dtype=t, device=dev)
+    delta = 6.0 / 29.0
+    f = (xyz * (1.0 / (3 * delta ** 2)) + 4.0 / 29) * (xyz < delta ** 3.0).to(t) + torch.pow(xyz + 1.0e-8, 1.0 / 3.0) * (xyz >= delta ** 3.0).to(t)
+    return torch.matmul(f, torch.tensor([[0.0, 500.0, 0.0], [116.0, -500.0, 200.0], [0.0, 0.0, -200.0]], dtype=t, device=dev)) + \
+        torch.tensor([-16.0, 0.0, 0.0], dtype=t, device=dev)
+
+
+def lab_deltas_torch(target_rgb: torch.Tensor, renders: torch.Tensor, ignore_transparency: bool = False) -> torch.Tensor:
+    """``compute_lab_deltas`` (forger/metrics/color_metric.py:29-49): [n,R,R] Lab distance of every pixel to its image's target."""
+    if ignore_transparency:
+        rgb = renders[:, :3]
+    else:
+        alpha = renders[:, 3].unsqueeze(1)
+        rgb = alpha * renders[:, :3] + (1 - alpha) * 1.0
+    lab = rgb2lab_torch(rgb.permute(0, 2, 3, 1).reshape(-1, 3)).reshape(rgb.shape[0], rgb.shape[2], rgb.shape[3], 3).permute(0, 3, 1, 2)
+    return torch.linalg.norm(lab - rgb2lab_torch(target_rgb).unsqueeze(-1).unsqueeze(-1), dim=1)
+
+
+def _metric_shapes(renders: torch.Tensor, target_rgb: torch.Tensor, masks: EvalMasks) -> Tuple[int, int, int]:
+    """(n, K, R) of a ``brush_metrics`` call, or ValueError."""
+    if renders.dtype != torch.float32 or renders.dim() != 4 or renders.shape[1] != 4 or renders.shape[2] != renders.shape[3]:
+        raise ValueError(f"brush_metrics: float32 renders [n,4,R,R] expected, got {renders.dtype} {tuple(renders.shape)}")
+    n, r = renders.shape[0], renders.shape[2]
+    if target_rgb.dtype != torch.float32 or tuple(target_rgb.shape) != (n, 3):
+        raise ValueError(f"brush_metrics: float32 target colours [{n},3] expected, got {target_rgb.dtype} {tuple(target_rgb.shape)}")
+    if masks.geom.dim() != 3 or masks.geom.shape[0] < 1 or tuple(masks.geom.shape[1:]) != (r, r):
+        raise ValueError(f"brush_metrics: masks of [K,{r},{r}] drawings expected, got {tuple(masks.geom.shape)}")
+    return n, masks.geom.shape[0], r
+
+
 class TileOpsBase:
     """What ``PaintingHelper`` and ``PaintSession`` call on their ``ops``, as far as it can be said without a device: the scheduling
     hooks, with defaults that do nothing (one stream, no workspaces to prepare, no noise sets, no captured graphs), and the host
     restatement of every operation that has one (drawing preparation, stroke raster, tile counts, on-white, compositing, view, the
-    masked selection and the un-positioned render of the brush calibration), on host tensors.  ``TileOps`` overrides all of them; the CPU stand-ins of the tests derive from this class and define only what has
+    masked selection and the un-positioned render of the brush calibration, the evaluation masks, metric sums and composited render
+    of the brush scores), on host tensors.  ``TileOps`` overrides all of them; the CPU stand-ins of the tests derive from this class and define only what has
     no restatement here (``to_device``, ``geom_tiles``, ``encode``, ``head`` / ``tail`` / ``full``, the feature-canvas operations, ``paste``)."""
     n_streams = 1
     stream_policy = 0
@@ -213,6 +276,53 @@ class TileOpsBase:
         outs = [self.G.forward_pre_mapped(ws[i:i + 1], [f[i:i + 1] for f in feats], return_debug_data=True, **kw) for i in range(ws.shape[0])]
         dbg = {k: torch.cat([d[k] for _, d in outs]) for k in ("uvs", "colors")}
         return torch.cat([img for img, _ in outs]), dbg
+
+    # -- brush scores: the torch restatements (``TileOps`` runs csrc/nb_metrics.hip and the HIP generator) --
+    def eval_masks(self, geom: torch.Tensor) -> EvalMasks:
+        """The evaluation masks of the drawings ``geom`` [K,R,R] float32 (0 = stroke): the Gaussian applied twice
+        (geom_metric.py:153) and the two masks of ``compute_transparency_metrics``, with their counts."""
+        if geom.dtype != torch.float32 or geom.dim() != 3 or geom.shape[1] != geom.shape[2]:
+            raise ValueError(f"eval_masks: float32 drawings [K,R,R] expected, got {geom.dtype} {tuple(geom.shape)}")
+        geom = geom.contiguous()
+        blur = gaussian_blur_torch(gaussian_blur_torch(geom.unsqueeze(1))).squeeze(1)
+        bg, fg = blur > BG_THRESH, geom < FG_THRESH
+        k = geom.shape[0]
+        return EvalMasks(geom, blur, bg.to(torch.uint8) | (fg.to(torch.uint8) << 1), bg.reshape(k, -1).sum(dim=1).to(torch.int32),
+                         fg.reshape(k, -1).sum(dim=1).to(torch.int32))
+
+    def brush_metrics(self, renders: torch.Tensor, target_rgb: torch.Tensor, masks: EvalMasks, lab_thresh: float = 10,
+                      ignore_transparency: bool = False, want_deltas: bool = False):
+        """(sums [n,4] float32, alpha [n, R*R] float32[, deltas [n,R,R]]) of ``renders`` [n,4,R,R] in 0..1 (a view is fine) against
+        ``target_rgb`` [n,3]; image i lies on drawing i % K of ``masks``.  With dE the Lab distance of a pixel to the target
+        (color_metric.py:29-49) and the float weight w = 1 - geom: sums = (sum w dE, sum w [dE > lab_thresh], sum w, sum of alpha over
+        the background pixels); ``alpha`` is every render's alpha plane, dense."""
+        n, k, r = _metric_shapes(renders, target_rgb, masks)
+        deltas = lab_deltas_torch(target_rgb, renders, ignore_transparency)
+        idx = torch.arange(n, device=renders.device) % k
+        w = (1 - masks.geom)[idx]
+        alpha = renders[:, 3]
+        bg = (masks.mask[idx] & 1).to(torch.float32)
+        sums = torch.stack([torch.sum(w * deltas, dim=(1, 2)), torch.sum((deltas > lab_thresh).to(torch.float32) * w, dim=(1, 2)),
+                            torch.sum(w, dim=(1, 2)), torch.sum(alpha * bg, dim=(1, 2))], dim=1)
+        out = (sums, alpha.reshape(n, r * r).contiguous())
+        return out + (deltas,) if want_deltas else out
+
+    def render_rgba(self, ws: torch.Tensor, geom_feats, user_colors=None, sfactor=None, noise_set=None) -> torch.Tensor:
+        """[n,4,R,R] float32 in 0..1: the un-positioned "clear" render of the paint engine (brush.py:763-792) with the checkpoint's
+        constant noise; ``user_colors`` [n,3,3] replace the generator's colours where they are not NaN, ``sfactor`` [n] stretches the
+        background weight (mapper.py:52-72).  This restatement composites ``triad_debug``'s weights and colours in torch."""
+        if noise_set is not None:
+            raise ValueError("render_rgba: this ops has no noise sets")
+        _, dbg = self.triad_debug(ws, geom_feats)
+        uvs, colors = dbg["uvs"], (dbg["colors"] + 1) / 2.0
+        if sfactor is not None:
+            sp = torch.clamp(torch.as_tensor(sfactor, dtype=uvs.dtype).reshape(-1, 1, 1, 1) * uvs[:, 2:3], max=1.0)
+            f = torch.where(1 - sp <= 0.000001, torch.zeros_like(sp), (1 - sp) / (uvs[:, 0:1] + uvs[:, 1:2]))
+            uvs = torch.cat([f * uvs[:, 0:1], f * uvs[:, 1:2], sp], dim=1)
+        if user_colors is not None:
+            colors = torch.where(torch.isnan(user_colors), colors, user_colors.to(colors.dtype))
+        stroke = torch.sum(uvs.unsqueeze(1) * colors.unsqueeze(-1).unsqueeze(-1), dim=2)
+        return torch.cat([stroke, torch.sum(uvs[:, 0:2], dim=1, keepdim=True)], dim=1)
 
     # -- compositing: the numpy restatements, on host tensors (``TileOps`` runs the kernels of csrc/nb_compose.hip) --
     def over_tiles(self, canvas, tiles_u8, dst_yx, crop, cell_off, cell_tiles, box=None, mode: int = 0, opacity: int = 255) -> None:
@@ -503,6 +613,47 @@ class TileOps(TileOpsBase):
             _lib.check(_lib.lib().nb_masked_kth_largest_f32(_p(x), max(int(x.stride(0)), count), _p(mask), m, count, int(k), n, _p(kth),
                                                             _p(n_masked), self._stream()), "masked_kth_largest")
         return kth, n_masked
+
+    # -- brush scores (csrc/nb_metrics.hip) --
+    def eval_masks(self, geom: torch.Tensor) -> EvalMasks:
+        """The evaluation masks of the drawings ``geom`` [K,R,R] float32 on the device, one launch (``nb_eval_masks_f32``)."""
+        if geom.dtype != torch.float32 or geom.dim() != 3 or geom.shape[1] != geom.shape[2] or geom.device != self.device:
+            raise ValueError(f"eval_masks: float32 drawings [K,R,R] on the engine's device expected, got {geom.dtype} {tuple(geom.shape)}")
+        geom = geom.contiguous()
+        k, r = geom.shape[0], geom.shape[1]
+        blur, mask = torch.empty_like(geom), torch.empty([k, r, r], dtype=torch.uint8, device=self.device)
+        n_bg, n_fg = (torch.empty([k], dtype=torch.int32, device=self.device) for _ in range(2))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_eval_masks_f32(_p(geom), k, r, _p(blur), _p(mask), _p(n_bg), _p(n_fg), self._stream()), "eval_masks")
+        return EvalMasks(geom, blur, mask, n_bg, n_fg)
+
+    def brush_metrics(self, renders: torch.Tensor, target_rgb: torch.Tensor, masks: EvalMasks, lab_thresh: float = 10,
+                      ignore_transparency: bool = False, want_deltas: bool = False):
+        """(sums [n,4], alpha [n, R*R][, deltas [n,R,R]]) on the device (``nb_brush_metrics_f32``: one pass over the renders and a
+        fixed-order finish; the same input gives the same bits).  A view whose samples are dense [4,R,R] blocks is read in place."""
+        n, k, r = _metric_shapes(renders, target_rgb, masks)
+        if renders.device != self.device or target_rgb.device != self.device or masks.geom.device != self.device:
+            raise ValueError("brush_metrics: renders, colours and masks must be on the engine's device")
+        count = r * r
+        if renders.stride(3) != 1 or renders.stride(2) != r or renders.stride(1) != count or (n > 1 and renders.stride(0) < 4 * count):
+            renders = renders.contiguous()
+        target_rgb = target_rgb.contiguous()
+        sums = torch.empty([n, 4], dtype=torch.float32, device=self.device)
+        alpha = torch.empty([n, count], dtype=torch.float32, device=self.device)
+        deltas = torch.empty([n, r, r], dtype=torch.float32, device=self.device) if want_deltas else None
+        partials = torch.empty([n, _lib.NB_BRUSH_METRICS_PARTS, 4], dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_brush_metrics_f32(_p(renders), max(int(renders.stride(0)), 4 * count), _p(target_rgb), _p(masks.geom),
+                                                       _p(masks.mask), k, r, n, float(lab_thresh), int(bool(ignore_transparency)), _p(sums),
+                                                       _p(alpha), _p(deltas), _p(partials), self._stream()), "brush_metrics")
+        return (sums, alpha, deltas) if want_deltas else (sums, alpha)
+
+    def render_rgba(self, ws: torch.Tensor, geom_feats, user_colors=None, sfactor=None, noise_set=None) -> torch.Tensor:
+        """[n,4,R,R] float32 in 0..1: ONE un-positioned "clear" generator pass, composited in the ToRGB launch."""
+        kw = {} if noise_set is None else {"noise_set": noise_set}
+        _, rgba, _ = self.G.render_triad(ws=ws, geom_feature=geom_feats, want_u8=False, want_f32=True, render_mode="clear", positions=None,
+                                         user_colors=user_colors, sfactor=sfactor, **kw)
+        return rgba
 
     # -- canvas kernels --
     def new_feature_canvas(self, c, hc, wc):

@@ -656,6 +656,41 @@ int nb_canvas_view_u8(const uint8_t* canvas, int ch, int cw, int y0, int x0, int
 int nb_masked_kth_largest_f32(const float* x, long long stride_n, const uint8_t* mask, int n_masks, int count, int k, int n,
                               float* kth, int32_t* n_masked, void* stream);
 
+/* ---- brush scores: the reference's colour and transparency metrics (csrc/nb_metrics.hip) -----------------------------------------
+ * Evaluation masks of K drawings, once per set of drawings.  geom [k,r,r] fp32, 0 = stroke.  blur [k,r,r] =
+ * default_gaussian_smoothing applied twice (forger/metrics/geom_metric.py:126-129, 153): a 5x5 Gaussian, sigma 1, normalised to sum 1,
+ * zero padding 2 at EACH application, so what the first application would put outside the image is zero for the second.  mask
+ * [k,r,r] bytes: bit 0 = background, blur > 0.999f; bit 1 = foreground, geom < 0.3f (geom_metric.py:156-159).  n_bg[k] / n_fg[k] =
+ * the set bits of each drawing's mask (cleared and counted on `stream`, integer arithmetic).  One launch, 25 taps per pass in fp32:
+ * within 4e-6 of float64 on values in 0..1.  Values outside 0..1, infinities and NaN do not fault; what they give is unspecified.
+ * k == 0: NB_OK without a launch.  NB_EINVAL: a null pointer, k outside 0..65535, r outside 1..8192, a float / int pointer not 4-byte
+ * aligned. */
+int nb_eval_masks_f32(const float* geom, int k, int r, float* blur, uint8_t* mask, int32_t* n_bg, int32_t* n_fg, void* stream);
+
+/* Workgroups that share one image in nb_brush_metrics_f32: `partials` holds n * NB_BRUSH_METRICS_PARTS * 4 floats. */
+#define NB_BRUSH_METRICS_PARTS 16
+
+/* The per-image sums behind LAB_E%, LAB_L2 (compute_lab_metrics, forger/metrics/color_metric.py:29-70, with rgb2lab of
+ * forger/util/color.py:52-140) and BG_CLARITY_MEAN (compute_transparency_metrics, geom_metric.py:152-158) of n renders, in one pass.
+ * Render i is four dense planes r, g, b, alpha of r * r floats at renders + i * stride_n (stride_n >= 4 * r * r; a view into a larger
+ * tensor is read in place), in 0..1; its target colour is target_rgb[3 i .. 3 i + 2]; it uses drawing i % k of geom [k,r,r] and of
+ * mask [k,r,r] (nb_eval_masks_f32; only bit 0 is read).  Per pixel: rgb = alpha * rgb + (1 - alpha) unless ignore_transparency,
+ * sRGB -> linear (split at 0.04045, exponent 2.4), XYZ, f() with its linear branch below (6/29)^3 and 1e-8 added inside the cube
+ * root, Lab, dE = |Lab - Lab(target)|_2 (the target's Lab computed once per workgroup).  With the float weight w = 1 - geom:
+ *   sums[4 i + 0] = sum w dE      sums[4 i + 1] = sum w [dE > lab_thresh]      sums[4 i + 2] = sum w      sums[4 i + 3] = sum of alpha
+ *                                                                                                          over background pixels
+ * alpha [n, r*r] receives every render's alpha plane, dense, so that nb_masked_kth_largest_f32 can pool the images of a brush;
+ * deltas [n, r*r] (may be null) receives dE.  NB_BRUSH_METRICS_PARTS workgroups share an image and leave partial sums in `partials`;
+ * a second small launch of the same call adds them in a fixed order: no float atomics, the same input gives the same bits.  Planes
+ * are read in 16-byte vectors when r * r and stride_n are multiples of four and renders, geom, alpha and deltas are 16-byte aligned,
+ * otherwise pixel by pixel (any float may start a plane).  Only enqueues on `stream`: no allocation, no host wait, capturable.
+ * Values outside 0..1, infinities and NaN do not fault; what they give is unspecified.  n == 0: NB_OK without a launch.
+ * NB_EINVAL: a null pointer (deltas excepted), k < 1, r outside 1..8192, n outside 0..2^24, stride_n < 4 r r, a float pointer not
+ * 4-byte aligned. */
+int nb_brush_metrics_f32(const float* renders, long long stride_n, const float* target_rgb, const float* geom, const uint8_t* mask,
+                         int k, int r, int n, float lab_thresh, int ignore_transparency, float* sums, float* alpha, float* deltas,
+                         float* partials, void* stream);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
