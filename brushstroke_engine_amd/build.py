@@ -16,11 +16,13 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libneube_hip.so")
-# (the four files that take longest to compile come first: the pool of four starts with them)
+# (the four files that take longest to compile come first: the pool of four starts with them.  The C generator is nb_generator.hip and
+# the three files behind it, of which nb_gen_plan.hip and nb_gen_encoder.hip are host code only; they keep the .hip suffix, by which
+# build() tells the objects of the tree's sources from stale ones)
 SOURCES = ["nb_modconv_up1_h3.hip", "nb_modconv_up2_h3.hip", "nb_modconv_up2v.hip", "nb_encoder.hip", "nb_ops.hip", "nb_modconv.hip", "nb_pack_h2.hip",
-           "nb_modconv_small.hip", "nb_grad.hip", "nb_canvas.hip", "nb_calib.hip", "nb_generator.hip", "nb_geomprep.hip", "nb_noise_seeded.hip", "nb_brush_noise.hip",
+           "nb_modconv_small.hip", "nb_grad.hip", "nb_canvas.hip", "nb_calib.hip", "nb_generator.hip", "nb_weight_pack.hip", "nb_gen_plan.hip", "nb_gen_encoder.hip", "nb_geomprep.hip", "nb_noise_seeded.hip", "nb_brush_noise.hip",
            "nb_strokes.hip", "nb_compose.hip", "nb_select.hip", "nb_metrics.hip"]
-HEADERS = ["nb_common.h", "nb_h3_common.h", "nb_h3_launch.h", "nb_torgb.h", os.path.join("..", "..", "include", "neube_hip.h")]
+HEADERS = ["nb_common.h", "nb_h3_common.h", "nb_h3_launch.h", "nb_torgb.h", "nb_gen_internal.h", os.path.join("..", "..", "include", "neube_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall",
@@ -40,8 +42,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-fn
 # nb_compose.hip: integer arithmetic with one scalar fp32 quotient estimate per channel, four pixels per thread: the same case.
 # nb_select.hip: integer arithmetic on the bits of four floats per thread; no fp32 arithmetic at all, kept with the scalar files.
 # nb_metrics.hip: scalar fp32 per pixel (the Lab chain of four pixels per thread, 25-tap sums): the same case.
+# nb_generator.hip, nb_weight_pack.hip: the generator's small set-up kernels and weight packers, scalar fp32 per element, were one file.
 FILE_FLAGS = {"nb_modconv.hip": ["-fno-slp-vectorize"], "nb_ops.hip": ["-fno-slp-vectorize"],
-              "nb_modconv_up2v.hip": ["-fno-slp-vectorize"], "nb_generator.hip": ["-fno-slp-vectorize"],
+              "nb_modconv_up2v.hip": ["-fno-slp-vectorize"], "nb_generator.hip": ["-fno-slp-vectorize"], "nb_weight_pack.hip": ["-fno-slp-vectorize"],
               "nb_geomprep.hip": ["-fno-slp-vectorize"], "nb_noise_seeded.hip": ["-fno-slp-vectorize"],
               "nb_brush_noise.hip": ["-fno-slp-vectorize"], "nb_strokes.hip": ["-fno-slp-vectorize"],
               "nb_compose.hip": ["-fno-slp-vectorize"], "nb_select.hip": ["-fno-slp-vectorize"],

@@ -761,7 +761,7 @@ int nb_enc_upsample2x_h2_ex(const float* x, void* y_h2, int out_fmt, int n, int 
  * wpk[ceil8(c_in)][9][ceil32(c_out)] and wsq[c_in][c_out] = sum_k W^2.  Either output may be NULL. */
 int nb_pack_conv_weight(const float* w, int c_out, int c_in, float* wpk, float* wsq);
 
-/* ---- device weight packers (csrc/nb_generator.hip): the packed forms the generator layers take, built from the fp32 weight
+/* ---- device weight packers (csrc/nb_weight_pack.hip): the packed forms the generator layers take, built from the fp32 weight
  * W[c_out,c_in,3,3] on the DEVICE (w and every output are device pointers; enqueue only).  Bit for bit what the package's torch
  * packers (ops.py) produce. */
 
@@ -775,7 +775,7 @@ int nb_pack_conv_weight_h3f8_dev(const float* w, int c_out, int c_in, void* out,
  * float64 and rounded to fp32), each in the nb_pack_conv_weight_h3 format, back to back. */
 int nb_pack_conv_weight_h3_up2_dev(const float* w, const float* resample_filter, int c_out, int c_in, void* out, void* stream);
 
-/* ---- the whole generator behind one handle (csrc/nb_generator.hip) -------------------------------------------------------
+/* ---- the whole generator behind one handle (csrc/nb_generator.hip; tables and planner: nb_gen_plan.hip, encoder: nb_gen_encoder.hip) ----
  * For C / C++ hosts: create a generator from its fp32 weights once, then enqueue whole forward passes (mapping, styles, noise,
  * every synthesis layer, the fused ToRGB + compositing) with one call.  The per-batch kernel choices are those of the package's
  * Python pass (SynthesisNetwork) at the same batch size, and so are the results, bit for bit.

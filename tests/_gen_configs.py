@@ -1,5 +1,5 @@
 """Generator configurations that reach the per-batch kernel decisions the shipped style1 shapes never take, shared by the CPU and GPU
-tests.  The decisions live once, in the library's planner (nb_synthesis_plan, csrc/nb_generator.hip), which SynthesisNetwork
+tests.  The decisions live once, in the library's planner (nb_synthesis_plan, csrc/nb_gen_plan.hip), which SynthesisNetwork
 (networks.py) and the C entry's gen_walk both follow.  These nets have ragged channel counts (c_in not a multiple of 8 or 16, partial
 64-channel c_out slices), no conv_clamp, a w_dim that is not a multiple of 16 and geometry layouts other than the default two features.
 

@@ -86,6 +86,13 @@ def test_set_entries_reject_null_handles(library):
     assert library.nb_brush_noise_load(None, None, None, 1.0, None) == _lib.NB_EINVAL and "null set" in library.nb_last_error().decode()
     assert library.nb_generator_bind_brush_noise(None, None) == _lib.NB_EINVAL and "null generator" in library.nb_last_error().decode()
     assert library.nb_brush_noise_destroy(None) == _lib.NB_OK
+    # the whole text of one failing call per set entry
+    assert library.nb_brush_noise_create(None, None, ctypes.byref(out)) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"brush_noise_create: null generator"
+    assert library.nb_brush_noise_load(None, None, None, 1.0, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"brush_noise_load: null set"
+    assert library.nb_generator_bind_brush_noise(None, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator_bind_brush_noise: null generator"
 
 
 def test_gpu_shapes_reach_the_rows_the_feature_exists_for():

@@ -112,6 +112,21 @@ def test_unsupported_modes_and_bad_arguments_fail_without_gpu(library):
     assert library.nb_generator_param_info(ctypes.byref(c), 10 ** 6, None, 0, None, None) == _lib.NB_EINVAL
 
 
+def test_error_texts_of_the_table_describe_and_forward_entries(library):
+    """The whole nb_last_error text of one failing call per entry (the entries share their helpers: the texts are each entry's own)."""
+    c = _cfg()
+    count = library.nb_generator_param_count(ctypes.byref(c))
+    assert library.nb_generator_param_info(ctypes.byref(c), count, None, 0, None, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator: parameter index %d out of range [0, %d)" % (count, count)
+    assert library.nb_generator_param_info(ctypes.byref(c), 0, ctypes.create_string_buffer(4), 4, None, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator: name buffer too short (4 bytes for \"mapping.fc0.weight\")"
+    assert library.nb_generator_describe(None, 1, ctypes.create_string_buffer(16), 16) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator_describe: bad arguments"
+    ins, outs = _lib.NbGeneratorInputs(), _lib.NbGeneratorOutputs()
+    assert library.nb_generator_forward(None, ctypes.byref(ins), ctypes.byref(outs), 1, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator_forward: null pointer"
+
+
 def test_c_example_builds(library, tmp_path):
     cmd = ["cc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(REPO, "include"), "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
            os.path.join(REPO, "examples", "capi", "generate.c"), "-o", str(tmp_path / "generate"), "-L/opt/rocm/lib", "-lamdhip64",

@@ -67,6 +67,17 @@ def test_bad_arguments_fail_without_gpu(library):
     assert b"null pointer" in library.nb_last_error()
 
 
+def test_error_texts_of_the_encoder_table_and_forward_entries(library):
+    """The whole nb_last_error text of one failing call per entry."""
+    assert library.nb_encoder_param_info(42, None, 0, None, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"encoder: parameter index 42 out of range [0, 42)"
+    assert library.nb_encoder_param_info(0, ctypes.create_string_buffer(4), 4, None, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator: name buffer too short (4 bytes for \"encoder.model.0.conv.0.weight\")"
+    ins, outs = _lib.NbGeneratorInputs(), _lib.NbGeneratorOutputs()
+    assert library.nb_generator_forward_geom(None, ctypes.byref(ins), None, ctypes.byref(outs), 1, None) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator_forward_geom: null pointer"
+
+
 def test_paint_example_builds(library, tmp_path):
     cmd = ["cc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(REPO, "include"), "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
            os.path.join(REPO, "examples", "capi", "paint.c"), "-o", str(tmp_path / "paint"), "-L/opt/rocm/lib", "-lamdhip64",

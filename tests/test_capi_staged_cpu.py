@@ -112,6 +112,13 @@ def test_staged_argument_errors_without_gpu(library):
         assert msg in library.nb_last_error()
     assert library.nb_generator_describe_staged(None, 1, 64, 0, buf, 64) == _lib.NB_EINVAL and b"bad arguments" in library.nb_last_error()
     assert ctypes.sizeof(_lib.NbGeneratorStage) == 24      # two int32, two pointers
+    # the whole text of one failing call per entry
+    assert forward(None, _lib.NbGeneratorStage(64, 0, 16, None)) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator_forward_staged: null pointer"
+    assert library.nb_generator_describe_staged(None, 1, 64, 0, buf, 64) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator_describe_staged: bad arguments"
+    assert library.nb_generator_describe_staged(fake, 1, 24, 0, buf, 64) == _lib.NB_EINVAL
+    assert library.nb_last_error() == b"generator_describe_staged: 24 is not a block resolution (a power of two in [4, R])"
 
 
 def test_dirty_area_alpha_argument_errors_without_gpu(library):

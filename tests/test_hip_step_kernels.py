@@ -1,5 +1,5 @@
 """GPU: the small kernels at the head and tail of every step (csrc/nb_ops.hip) and the device weight packers
-(csrc/nb_generator.hip), each through its C entry point on tensors built here, against a float64 restatement
+(csrc/nb_weight_pack.hip), each through its C entry point on tensors built here, against a float64 restatement
 (oracle/neube_oracle.py where it has one) or, for the packers, bit for bit against the package's torch packers.
 
 Layer tables (NbLayerDesc[]) are built with ctypes as networks._Plan does, so that one launch mixes conv layers with
