@@ -168,6 +168,14 @@ PROTOTYPES = {
     # brush scores (csrc/nb_metrics.hip): evaluation masks of the drawings, the per-image sums of the colour and transparency metrics
     "nb_eval_masks_f32": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "nb_brush_metrics_f32": (C.c_int, [vp, C.c_longlong, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
+    # clarity optimisation (csrc/nb_clarity.hip): the fused loss and its gradient, the noise regulariser, the Adam + renormalise step
+    "nb_clarity_scratch_floats": (C.c_longlong, [vp, C.c_int, C.c_longlong, C.c_int]),
+    "nb_clarity_loss_f32": (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      C.c_float, C.c_float, vp, vp, vp, vp]),
+    "nb_clarity_loss_bwd_f32": (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                          C.c_float, vp, vp, vp]),
+    "nb_noise_reg_f32": (C.c_int, [vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_int, C.c_float, vp, C.c_longlong, vp, vp, C.c_longlong, vp]),
+    "nb_clarity_step_f32": (C.c_int, [vp, vp, vp, vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_int, C.c_float, C.c_int, vp, C.c_longlong, vp]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -266,6 +274,12 @@ class NbPassPlan(C.Structure):
 NB_GEOM_PREP_WS_BYTES = 1040
 NB_SEG_PITCH = 8
 NB_BRUSH_METRICS_PARTS = 16
+NB_CLARITY_MAX_PLANES, NB_CLARITY_LOSS_PARTS, NB_CLARITY_CHUNK = 32, 8, 1024
+
+
+class NbClarityPlanes(C.Structure):
+    """``struct NbClarityPlanes`` of include/neube_hip.h: side and offset of every noise plane of an arena row (a host struct)."""
+    _fields_ = [("n", C.c_int32), ("res", C.c_int32 * NB_CLARITY_MAX_PLANES), ("off", C.c_int32 * NB_CLARITY_MAX_PLANES)]
 
 NB_OK, NB_EINVAL, NB_ELAUNCH, NB_EUNSUPPORTED = 0, -1, -2, -3
 NB_CONV_MODES = {"f32": 0, "h3": 1, "f8": 2, "f6": 3, "f16": 4}

@@ -97,17 +97,18 @@ class TrainableGenerator(torch.nn.Module):
         return x
 
     # -- SynthesisLayer.forward, networks.py:362-391 --
-    def _layer(self, spec, x, w, norm_pos, noise_mode):
+    def _layer(self, spec, x, w, norm_pos, noise_mode, input_noise=None):
         name = spec.name
         styles = self._fc(w, name + ".affine")
         noise = None
         if noise_mode == "random":
             noise = torch.randn([x.shape[0], 1, spec.block_res, spec.block_res], device=x.device) * self.p(name + ".noise_strength")
         elif noise_mode == "const":
-            nc = self.p(name + ".noise_const")
+            nc = self.p(name + ".noise_const") if input_noise is None else input_noise.to(torch.float32)
             if norm_pos is not None:
                 grid = (self.p(name + ".noise_grid") + norm_pos.unsqueeze(1).unsqueeze(1)) % 1 * 2 - 1
-                nc = F.grid_sample(nc[None, None].expand(x.shape[0], -1, -1, -1), grid, padding_mode="reflection", align_corners=True)
+                src = nc[None, None].expand(x.shape[0], -1, -1, -1) if nc.ndim == 2 else nc
+                nc = F.grid_sample(src, grid, padding_mode="reflection", align_corners=True)
             noise = nc * self.p(name + ".noise_strength")
             if noise.ndim == 2:
                 noise = noise[None, None]
@@ -131,10 +132,21 @@ class TrainableGenerator(torch.nn.Module):
         return img, {"colors": colors, "uvs": uvs}
 
     # -- SynthesisNetwork.forward, networks_modified.py:123-223 ('orig' architecture, triad colours) --
-    def synthesis(self, ws, geom_feature, norm_noise_positions=None, noise_mode="random", return_debug_data=False):
+    def synthesis(self, ws, geom_feature, norm_noise_positions=None, noise_mode="random", return_debug_data=False, noise_buffers=None):
         """``noise_mode`` defaults to 'random' like ``SynthesisLayer.forward`` (networks.py:362): training draws fresh
-        per-layer noise every step; 'const' is what inference (and the golden-vector tests) pass explicitly."""
+        per-layer noise every step; 'const' is what inference (and the golden-vector tests) pass explicitly.
+        ``noise_buffers`` = {"b<res>.conv<i>.noise_const": [r,r] or [N,1,r,r] tensor} (the keys of ``OracleGenerator.synthesis`` and
+        ``SynthesisNetwork.brush_noise()``) replaces those layers' ``noise_const`` under ``noise_mode='const'``; gradients reach
+        the tensors (``ops._ModulatedConv2d`` returns ``dnoise``), which is what the clarity optimisation differentiates."""
         cfg = self.cfg
+        nb = noise_buffers or {}
+        unknown = sorted(set(nb) - {l.name[len("synthesis."):] + ".noise_const" for l in cfg.layers})
+        if unknown:
+            raise KeyError(f"noise_buffers: no such layers: {unknown}")
+        for k, v in nb.items():
+            r = int(k[1:k.index(".")])
+            if tuple(v.shape) not in ((r, r), (ws.shape[0], 1, r, r)):
+                raise ValueError(f"noise_buffers[{k!r}]: shape {tuple(v.shape)}, expected ({r}, {r}) or ({ws.shape[0]}, 1, {r}, {r})")
         ws = ws.to(torch.float32)
         n = ws.shape[0]
         geom_feature = list(geom_feature) if isinstance(geom_feature, (list, tuple)) else [geom_feature]
@@ -148,9 +160,9 @@ class TrainableGenerator(torch.nn.Module):
                 x = self.p(b + ".const").unsqueeze(0).repeat([n, 1, 1, 1])
             else:
                 sp = layers[b + ".conv0"]
-                x = self._layer(sp, x, ws[:, sp.w_index], norm_noise_positions, noise_mode)
+                x = self._layer(sp, x, ws[:, sp.w_index], norm_noise_positions, noise_mode, nb.get(f"b{res}.conv0.noise_const"))
             sp = layers[b + ".conv1"]
-            x = self._layer(sp, x, ws[:, sp.w_index], norm_noise_positions, noise_mode)
+            x = self._layer(sp, x, ws[:, sp.w_index], norm_noise_positions, noise_mode, nb.get(f"b{res}.conv1.noise_const"))
             if res == cfg.img_resolution:
                 img, triad = self._torgb(x, ws[:, cfg.torgb_w_index])
             if res in cfg.geom_feature_resolutions:

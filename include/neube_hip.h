@@ -691,6 +691,68 @@ int nb_brush_metrics_f32(const float* renders, long long stride_n, const float* 
                          int k, int r, int n, float lab_thresh, int ignore_transparency, float* sums, float* alpha, float* deltas,
                          float* partials, void* stream);
 
+/* ---- clarity optimisation of brushes (csrc/nb_clarity.hip): what one step of run_one_clarity_opt (scripts/opt_clarity_main.py:93-167)
+ * does around the generator, for k brushes at once.  The state of k brushes is an arena [k, p] of floats (row stride given per call):
+ * a row is W+ (nw floats) followed by noise planes.  NbClarityPlanes lists the planes in the order of their offsets: side (a power of
+ * two in 4..256) and offset in floats from the start of a row.  It is a HOST struct: every entry checks it against nw and p before any
+ * HIP call (NB_EINVAL: more than NB_CLARITY_MAX_PLANES, a side that is unsupported, planes that overlap, precede nw or leave the row)
+ * and hands it to its kernels by value, so no launch can index outside a row.  fp32 throughout; no float atomics: partial sums are
+ * left in caller-supplied scratch and added in a fixed order, so the same input gives the same bits, and row i of a k-row call equals
+ * the one-row call on that row.  The entries only enqueue on `stream`: no allocation, no host wait.  k == 0: NB_OK without a launch. */
+#define NB_CLARITY_MAX_PLANES 32
+#define NB_CLARITY_LOSS_PARTS 8       /* workgroups that share one sample in nb_clarity_loss_f32 */
+#define NB_CLARITY_CHUNK 1024         /* floats of a row one workgroup of nb_clarity_step_f32 updates */
+typedef struct NbClarityPlanes {
+    int32_t n;
+    int32_t res[NB_CLARITY_MAX_PLANES];
+    int32_t off[NB_CLARITY_MAX_PLANES];
+} NbClarityPlanes;
+
+/* Floats of scratch that nb_noise_reg_f32 and nb_clarity_step_f32 need for k rows of this layout (the larger of the two); -1 with
+ * nb_last_error set if the layout is invalid or k is outside 0..65535. */
+long long nb_clarity_scratch_floats(const NbClarityPlanes* planes, int nw, long long p, int k);
+
+/* The loss 'w_iou_inv*iou_inv(uvs)+w_iou*iou(u)+w_l1*l1(fake_orig)' (forger/train/losses.py:453-474, 501-530; compute_iou in its
+ * per-sample form, :649-666, eps 1e-8; l1_loss with mean reduction) of k brushes on b drawings each.  Sample n = brush * b + drawing:
+ * uvs / img / target are three dense planes of r * r floats at <base> + n * <stride_n> (stride_n >= 3 r r: views are read in place);
+ * geom [b,r,r] is the truth, 1 = background, shared by the brushes.  With s = uvs[2], u = uvs[0], g = geom, t = 1 - g, per sample
+ *   I_s = sum s g,  U_s = sum (s + g) - I_s + eps,  I_u = sum u t,  U_u = sum (u + t) - I_u + eps,  L = sum |img - target|
+ * sums [k*b, 8] receives {I_s, U_s, I_u, U_u, L, 0, 0, 0} (what the backward entry reads), out [k, 4] per brush
+ *   {1 - mean_b I_s / U_s,  1 - mean_b I_u / U_u,  sum_b L / (3 b r r),  the weighted sum of the three}.
+ * partials: k * b * NB_CLARITY_LOSS_PARTS * 8 floats.  Two launches.  NB_EINVAL: a null pointer, k < 0, b < 1, r outside 1..4096,
+ * k * b > 65535, a stride below 3 r r, a pointer not 4-byte aligned. */
+int nb_clarity_loss_f32(const float* uvs, long long uvs_stride_n, const float* img, long long img_stride_n, const float* target,
+                        long long target_stride_n, const float* geom, int k, int b, int r, float w_iou_inv, float w_iou, float w_l1,
+                        float* out, float* sums, float* partials, void* stream);
+
+/* Gradient of out[brush, 3] (times gscale[brush]; gscale NULL = 1) from the sums of nb_clarity_loss_f32, dense outputs
+ * d_uvs [k*b,3,r,r] and d_img [k*b,3,r,r]:
+ *   d_uvs[2] = -w_iou_inv / b * (g U_s - I_s (1 - g)) / U_s^2      d_uvs[0] = -w_iou / b * (t U_u - I_u (1 - t)) / U_u^2      d_uvs[1] = 0
+ *   d_img = w_l1 * sign(img - target) / (3 b r r), sign(0) = 0.
+ * One launch.  NB_EINVAL as for the forward entry. */
+int nb_clarity_loss_bwd_f32(const float* img, long long img_stride_n, const float* target, long long target_stride_n, const float* geom,
+                            const float* sums, const float* gscale, int k, int b, int r, float w_iou_inv, float w_iou, float w_l1,
+                            float* d_uvs, float* d_img, void* stream);
+
+/* The noise regulariser of opt_clarity_main.py:127-137 over all planes of k rows, value and gradient.  Per plane and level l (sides
+ * res, res / 2, ... down to 8; one level for res <= 8): n_l = the 2x2 mean of n_(l-1), a_l = mean(n_l * roll_x n_l), b_l likewise in
+ * y, and the value is the sum of a_l^2 + b_l^2.  reg [k] receives the value of each row (summed over planes in their order).  The
+ * gradient at a level-0 pixel, sum_l 4^-l [2 a_l / N_l (left + right) + 2 b_l / N_l (up + down)] of n_l around (y >> l, x >> l) with
+ * wrap-around, is ADDED times `weight` (regularize_noise_weight) to grad [k, p] (grad NULL: the value only).  Two launches: the sums
+ * per tile with the pyramid written to scratch, then the gradient.  scratch: nb_clarity_scratch_floats.  NB_EINVAL: a null pointer
+ * (grad excepted), an invalid layout, k outside 0..65535, a row stride below p, a pointer not 4-byte aligned, scratch too small. */
+int nb_noise_reg_f32(const float* arena, long long row_stride, long long p, int nw, const NbClarityPlanes* planes, int k, float weight,
+                     float* grad, long long grad_stride, float* reg, float* scratch, long long scratch_floats, void* stream);
+
+/* One optimiser step on the arena: Adam with torch.optim.Adam's defaults and arithmetic (betas 0.9 / 0.999, eps 1e-8, bias-corrected;
+ * opt_clarity_main.py:86, 159-161) over all k * p floats -- arena, grad, m, v share the layout and row_stride; lr and the step count
+ * t >= 1 are host scalars -- then, per noise plane, n -= mean(n); n *= rsqrt(mean(n^2)) (opt_clarity_main.py:163-167).  W+ is not
+ * normalised.  Two launches: the update with each chunk's sums of n and n^2, then the normalisation.  scratch:
+ * nb_clarity_scratch_floats.  NB_EINVAL: a null pointer, an invalid layout, k outside 0..65535, t < 1, row_stride < p, a pointer not
+ * 4-byte aligned, scratch too small. */
+int nb_clarity_step_f32(float* arena, const float* grad, float* m, float* v, long long row_stride, long long p, int nw,
+                        const NbClarityPlanes* planes, int k, float lr, int t, float* scratch, long long scratch_floats, void* stream);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
