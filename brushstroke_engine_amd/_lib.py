@@ -176,6 +176,12 @@ PROTOTYPES = {
                                           C.c_float, vp, vp, vp]),
     "nb_noise_reg_f32": (C.c_int, [vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_int, C.c_float, vp, C.c_longlong, vp, vp, C.c_longlong, vp]),
     "nb_clarity_step_f32": (C.c_int, [vp, vp, vp, vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_int, C.c_float, C.c_int, vp, C.c_longlong, vp]),
+    # brush projection (csrc/nb_projection.hip): the conservative masks and background colour, the fused loss and its gradient
+    "nb_projection_masks_f32": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "nb_projection_loss_f32": (C.c_int, [vp, C.c_longlong, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp]),
+    "nb_projection_loss_bwd_f32": (C.c_int, [vp, C.c_longlong, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -275,6 +281,7 @@ NB_GEOM_PREP_WS_BYTES = 1040
 NB_SEG_PITCH = 8
 NB_BRUSH_METRICS_PARTS = 16
 NB_CLARITY_MAX_PLANES, NB_CLARITY_LOSS_PARTS, NB_CLARITY_CHUNK = 32, 8, 1024
+NB_PROJECTION_PARTS = 8
 
 
 class NbClarityPlanes(C.Structure):

@@ -397,7 +397,10 @@ class TileOps(TileOpsBase):
 
     def map_style(self, z=None, ws=None) -> torch.Tensor:
         if ws is not None:
-            return ws.to(self.device, torch.float32)
+            ws = ws.to(self.device, torch.float32)
+            if ws.dim() == 3 and ws.shape[1] == 1 and self.cfg.num_ws > 1:     # a brush projected into W, not W+ (project_main.py:460)
+                ws = ws.expand(ws.shape[0], self.cfg.num_ws, ws.shape[2]).contiguous()
+            return ws
         return self.G.mapping(z.to(self.device), None)
 
     # -- generator halves --

@@ -753,6 +753,56 @@ int nb_noise_reg_f32(const float* arena, long long row_stride, long long p, int 
 int nb_clarity_step_f32(float* arena, const float* grad, float* m, float* v, long long row_stride, long long p, int nw,
                         const NbClarityPlanes* planes, int k, float lr, int t, float* scratch, long long scratch_floats, void* stream);
 
+/* ---- brush projection (csrc/nb_projection.hip): the loss that project() (scripts/project_main.py:38-224) computes around the
+ * generator, for k exemplars of b patches each.  Sample n = exemplar * b + patch; every exemplar has its own drawings.  Tensors of
+ * samples are three dense planes of r * r floats at <base> + n * <stride_n> (stride_n >= 3 r r: views are read in place).  Planes are
+ * read in 16-byte vectors when r * r and every stride are multiples of four and every plane pointer is 16-byte aligned (mask: 4-byte),
+ * otherwise pixel by pixel (any float may start a plane).  fp32 throughout; no float atomics: NB_PROJECTION_PARTS workgroups share a
+ * sample and leave partial sums in caller-supplied `partials`, a small second launch adds them in a fixed order, so the same input
+ * gives the same bits, and row i of a k-row call equals the one-row call on that row.  The entries only enqueue on `stream`: no
+ * allocation, no host wait.  k == 0: NB_OK without a launch.  NB_EINVAL for all three: a null pointer (the optional ones excepted),
+ * k < 0, b < 1, r outside 1..4096, k * b > 65535, a stride below 3 r r, a float / int pointer not 4-byte aligned. */
+#define NB_PROJECTION_PARTS 8         /* workgroups that share one sample */
+
+/* Once per pass.  blur [k*b,r,r] dense: the drawings (0 = stroke) under the 5x5 sigma-1 Gaussian applied twice with zero padding
+ * (what nb_eval_masks_f32 writes); target: the exemplar patches.  mask [k*b,r,r] bytes: bit 0 = background, blur >= 0.999f; bit 1 =
+ * foreground, blur < 0.1f (get_conservative_fg_bg, forger/metrics/geom_metric.py:132-140; note >= and 0.1, which differ from
+ * nb_eval_masks_f32's).  counts [k,2] int32 = {n_fg, n_bg} over an exemplar's b patches; bg_color [k,3] = per channel the mean of
+ * target over the exemplar's background pixels (compute_masked_color, project_main.py:248-250), zeros where n_bg == 0.
+ * partials: k * b * NB_PROJECTION_PARTS * 8 floats.  Two launches. */
+int nb_projection_masks_f32(const float* blur, const float* target, long long target_stride_n, int k, int b, int r, uint8_t* mask,
+                            int32_t* counts, float* bg_color, float* partials, void* stream);
+
+/* The forward.  colors [k*b,3,3] dense, indexed [c][j] as in compose_stroke (forger/viz/visualize.py:315-323).  With composite != 0
+ * (composite_with_bg_color / composite_with_bg_image, project_main.py:227-245):
+ *   stroke[c] = sum_j uvs[j] colors[c][j],   synth[c] = stroke[c] (1 - uvs[2]) + bg[c] uvs[2],
+ * bg = bg_image (samples of stride bg_stride_n) if it is not NULL, else the exemplar's bg_color [k,3]; synth [k*b,3,r,r] is written,
+ * dense; img is not read and may be NULL.  With composite == 0: synth = img, nothing is written; colors, bg_image, bg_color and synth
+ * are not read and may be NULL.  out [k,3] per exemplar (project_main.py:164-168, with mask and counts of nb_projection_masks_f32):
+ *   l1 = sum over foreground pixels and 3 channels of |target - synth| / (3 n_fg),   bg = sum over background pixels of
+ *   (1 - uvs[2]) / n_bg,   w_l1 l1 + w_bg bg;   an item whose count is zero is 0.
+ * partials: k * b * NB_PROJECTION_PARTS * 4 floats.  Two launches. */
+int nb_projection_loss_f32(const float* uvs, long long uvs_stride_n, const float* colors, const float* img, long long img_stride_n,
+                           const float* target, long long target_stride_n, const float* bg_image, long long bg_stride_n,
+                           const float* bg_color, const uint8_t* mask, const int32_t* counts, int k, int b, int r, int composite,
+                           float w_l1, float w_bg, float* synth, float* out, float* partials, void* stream);
+
+/* The backward: the forward's inputs, an optional upstream gradient d_synth [k*b,3,r,r] (dense; NULL = none) of synth and an optional
+ * gscale [k] (NULL = 1) that multiplies the gradient of out[exemplar, 2].  With
+ *   G[c] = d_synth[c] + gscale w_l1 [fg] sign(synth[c] - target[c]) / (3 n_fg),   sign(0) = 0,   a = 1 - uvs[2]:
+ * composite:     d_uvs[j] = sum_c G[c] colors[c][j] a  for j = 0, 1
+ *                d_uvs[2] = sum_c G[c] (colors[c][2] a - stroke[c] + bg[c]) - gscale w_bg [bg] / n_bg
+ *                d_colors [k*b,3,3]: d_colors[n][c][j] = sum over pixels of G[c] uvs[j] a   (through partials, in a fixed order)
+ * no composite:  d_img = G,   d_uvs[2] = -gscale w_bg [bg] / n_bg,   d_uvs[0] = d_uvs[1] = 0.
+ * A count of zero gives its item the gradient 0.  d_uvs [k*b,3,r,r] dense is always written; d_img [k*b,3,r,r] dense only without
+ * composite (else it may be NULL); d_colors and partials (k * b * NB_PROJECTION_PARTS * 16 floats) only with composite.  One launch,
+ * plus the finishing launch for d_colors. */
+int nb_projection_loss_bwd_f32(const float* uvs, long long uvs_stride_n, const float* colors, const float* img, long long img_stride_n,
+                               const float* target, long long target_stride_n, const float* bg_image, long long bg_stride_n,
+                               const float* bg_color, const uint8_t* mask, const int32_t* counts, const float* d_synth, const float* gscale,
+                               int k, int b, int r, int composite, float w_l1, float w_bg, float* d_uvs, float* d_img, float* d_colors,
+                               float* partials, void* stream);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
