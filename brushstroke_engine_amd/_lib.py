@@ -182,6 +182,13 @@ PROTOTYPES = {
                                          C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp]),
     "nb_projection_loss_bwd_f32": (C.c_int, [vp, C.c_longlong, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    # LPIPS network (csrc/nb_lpips.hip): scaling layer, bias + ReLU + tap + pool and its backward, the head and its backward
+    "nb_lpips_scale_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, vp]),
+    "nb_lpips_relu_pool_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "nb_lpips_relu_pool_bwd_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "nb_lpips_head_parts": (C.c_longlong, [C.c_int, C.c_int]),
+    "nb_lpips_head_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "nb_lpips_head_bwd_f32": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     # the per-batch layer plan (host only)
     "nb_plan_options_default": (C.c_int, [vp]),
     "nb_synthesis_plan": (C.c_int, [vp, vp, C.c_int, vp]),
@@ -282,6 +289,7 @@ NB_SEG_PITCH = 8
 NB_BRUSH_METRICS_PARTS = 16
 NB_CLARITY_MAX_PLANES, NB_CLARITY_LOSS_PARTS, NB_CLARITY_CHUNK = 32, 8, 1024
 NB_PROJECTION_PARTS = 8
+NB_LPIPS_SPLIT_MAX_HW, NB_LPIPS_SPLIT_MIN_C = 1024, 64
 
 
 class NbClarityPlanes(C.Structure):

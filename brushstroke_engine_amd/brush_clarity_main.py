@@ -4,7 +4,11 @@ written into a W library that ``paint_image_main`` / ``brush_metrics_main`` / ``
 
     python -m brushstroke_engine_amd.brush_clarity_main --gan_checkpoint engine.npz --library rand100 --drawings drawings.npz \\
         --out_library default --output_dir out [--brush_id ID] [--batch_size 20] [--num_steps 1000] [--losses STRING] [--seed N]
-        [--brushes_per_pass 4] [--uvs_calibration cal.npz]
+        [--brushes_per_pass 4] [--uvs_calibration cal.npz] [--lpips_weights lpips_vgg.npz]
+
+``--lpips_weights`` (the file ``tools/convert_lpips_weights.py`` writes; no weights ship) loads ``perceptual.LPIPS`` and allows
+``lpips(<component>)`` in ``--losses``, e.g. the reference's default ``0.5*iou_inv(uvs)+0.5*iou(u)+50*lpips(fake_orig)+50*l1(fake_orig)``;
+the default string here stays without the item.
 
 ``--drawings`` is the .npz of ``brush_metrics_main.load_drawings`` ([K,R,R] uint8, 0 = stroke): the conditioning and the truth of the
 loss, and the drawings the before / after scores are taken on.  ``--out_library default`` writes ``OPT_<library name>`` beside the
@@ -44,6 +48,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--brushes_per_pass", type=int, default=4, help="brushes that share an encoder pass and a generator batch")
     ap.add_argument("--uvs_calibration", default=None, help=".npz with 'medium' and 'thick' calibration drawings: score with the brushes' factors")
+    ap.add_argument("--lpips_weights", default=None, help=".npz of tools/convert_lpips_weights.py: allows lpips(<component>) in --losses")
     return ap
 
 
@@ -112,7 +117,11 @@ def main(argv=None):
     with torch.no_grad():
         evaluator = metrics.BrushEvaluator(ops, drawings, seed=args.seed or 0, uvs_mapper=mapper)
         before = evaluator.evaluate(library, style_ids=ids)
-    opt = clarity.ClarityOptimizer(TrainableGenerator(cfg, gen_sd, device), enc.encode, drawings, losses=args.losses)
+    lpips = None
+    if args.lpips_weights is not None:
+        from .perceptual import LPIPS
+        lpips = LPIPS(args.lpips_weights, device=device)
+    opt = clarity.ClarityOptimizer(TrainableGenerator(cfg, gen_sd, device), enc.encode, drawings, losses=args.losses, lpips=lpips)
     result = opt.optimize(library, style_ids=ids, num_steps=args.num_steps, batch_size=args.batch_size, brushes_per_pass=args.brushes_per_pass,
                           seed=args.seed)
     with torch.no_grad():

@@ -12,8 +12,10 @@ passes of ``--brushes_per_pass``.  ``--patches file.npz`` (``target`` [B,3,R,R] 
 [B,2] and ``target_bg``) bypasses the patch samplers; the brush is named by ``--output_style_id`` or the file.  Written into
 ``--output_dir``: ``ALL_projected_<suffix>.pkl`` (merged with an existing file as ``brush_clarity_main.merge_into_library`` does; what
 ``formats.WBrushLibrary`` reads), ``<id>_projected_<suffix>.npz`` per brush and ``projection.json`` with the loss items at the first step
-and at the step a brush finished at.  The reference's perceptual item needs the LPIPS network, which is not shipped: on the command line at least one of
-``--l1_fg_weight`` and ``--bg_weight`` must be positive.  No video or visualisation output.  Single process.
+and at the step a brush finished at.  ``--lpips_weights file.npz`` (written by ``tools/convert_lpips_weights.py`` from a user's weight
+files; none ship) switches the reference's perceptual item on (``perceptual.LPIPS``; best state and early stop then go by its value, as
+in the reference, and ``--l1_fg_weight`` / ``--bg_weight`` may both be 0); without it at least one of the two must be positive.  No
+video or visualisation output.  Single process.
 """
 from __future__ import annotations
 
@@ -63,6 +65,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--l1_fg_weight", type=float, default=0)
     ap.add_argument("--bg_weight", type=float, default=0)
     ap.add_argument("--brushes_per_pass", type=int, default=4, help="exemplars that share a generator batch")
+    ap.add_argument("--lpips_weights", default=None, help=".npz of tools/convert_lpips_weights.py: switches the perceptual item on")
     return ap
 
 
@@ -151,7 +154,11 @@ def main(argv=None, engine=None):
         return all_pkl, None
     if args.seed is not None:
         torch.manual_seed(args.seed)
-    proj = projection.BrushProjector(gen, encode, device=device, num_steps=args.num_steps, w_plus=args.w_plus, optimize_noise=not args.no_noise,
+    lpips = None
+    if args.lpips_weights is not None:                                     # project_main.py:158: the item the reference optimises first of all
+        from .perceptual import LPIPS
+        lpips = LPIPS(args.lpips_weights, device=device)
+    proj = projection.BrushProjector(gen, encode, device=device, perceptual=lpips, num_steps=args.num_steps, w_plus=args.w_plus, optimize_noise=not args.no_noise,
                                      with_positions=args.with_positions, with_composite=args.with_composite, l1_fg_weight=args.l1_fg_weight,
                                      bg_weight=args.bg_weight, resume_from=existing if args.resume else None)
     result = proj.project(exemplars, brushes_per_pass=args.brushes_per_pass, seed=args.seed)

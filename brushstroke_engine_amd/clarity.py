@@ -25,6 +25,7 @@ from .forger_losses import ForgerLosses
 
 DEFAULT_LOSSES = "0.5*iou_inv(uvs)+0.5*iou(u)+50*l1(fake_orig)"
 _FUSED_ITEMS = ("iou_inv_uvs", "iou_u", "l1_fake_orig")
+_LPIPS_ITEM = "lpips_fake_orig"
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
 
 
@@ -272,12 +273,15 @@ class ClarityOptimizer:
     noise_buffers=..., return_debug_data=True)`` -- ``training.TrainableGenerator`` on the GPU.  ``encode``: [B,1,R,R] float drawings
     (1 = background) -> the list of geometry features.  ``drawings_u8`` [N,R,R] uint8, 0 = stroke: the conditioning AND the truth
     (the reference's ``__main__`` passes ``geom_input_channel`` for both).  ``losses``: a :mod:`forger_losses` string; the three items
-    of :data:`DEFAULT_LOSSES` (any weights) run fused with ``route="hip"``, any other string goes through ``ForgerLosses.compute``."""
+    of :data:`DEFAULT_LOSSES` (any weights) run fused with ``route="hip"``, any other string goes through ``ForgerLosses.compute``.
+    ``lpips``: a :class:`perceptual.LPIPS` (any callable ``(target, source) -> [N]``), which allows ``lpips(<component>)`` in the
+    string; the three fused items plus ``lpips(fake_orig)`` -- the reference's default -- stay on the fused kernels, with the
+    perceptual term added per brush and reported as a fourth item."""
 
     def __init__(self, gen, encode: Callable, drawings_u8, losses: str = DEFAULT_LOSSES, regularize_noise_weight: float = 10,
                  initial_learning_rate: float = 0.1, initial_noise_factor: float = 0.05, lr_rampdown_length: float = 0.25,
                  lr_rampup_length: float = 0.05, noise_ramp_length: float = 0.75, route: Optional[str] = None, device=None,
-                 w_std: Optional[float] = None, w_avg_samples: int = 10000, draws: Optional[ClarityDraws] = None):
+                 w_std: Optional[float] = None, w_avg_samples: int = 10000, draws: Optional[ClarityDraws] = None, lpips: Optional[Callable] = None):
         drawings_u8 = np.asarray(drawings_u8)
         r = gen.cfg.img_resolution
         if drawings_u8.dtype != np.uint8 or drawings_u8.ndim != 3 or drawings_u8.shape[0] < 1 or drawings_u8.shape[1:] != (r, r):
@@ -292,11 +296,16 @@ class ClarityOptimizer:
             from ._lib import NeubeHipError
             raise NeubeHipError("route='hip' needs a GPU (there is no CPU fallback for the clarity kernels)")
         self.losses_string = losses
-        self.losses = ForgerLosses.create_from_string(losses)              # 'lpips' raises here
+        self.lpips = lpips
+        self.losses = ForgerLosses.create_from_string(losses, lpips)       # without a network 'lpips' raises here
         names = [l.full_name() for l in self.losses.losses]
-        self.fused = sorted(names) == sorted(_FUSED_ITEMS) and not any(l.partial_loss_with_triband_input for l in self.losses.losses)
+        # the three fused items, with or without lpips(fake_orig) beside them: the perceptual term is added per brush to the fused total
+        with_lpips = lpips is not None and _LPIPS_ITEM in names
+        self.fused = sorted(n for n in names if not (with_lpips and n == _LPIPS_ITEM)) == sorted(_FUSED_ITEMS) and \
+            not any(l.partial_loss_with_triband_input for l in self.losses.losses)
         self.fused_weights = tuple(float(self.losses.weights[names.index(n)]) for n in _FUSED_ITEMS) if self.fused else None
-        self.item_names = list(_FUSED_ITEMS) if self.fused else names
+        self.lpips_weight = float(self.losses.weights[names.index(_LPIPS_ITEM)]) if (self.fused and with_lpips) else None
+        self.item_names = (list(_FUSED_ITEMS) + ([_LPIPS_ITEM] if self.lpips_weight is not None else [])) if self.fused else names
         self.drawings = torch.from_numpy(drawings_u8).to(self.device)
         self.layout = ArenaLayout.from_config(gen.cfg)
         self.reg_weight = float(regularize_noise_weight)
@@ -335,7 +344,10 @@ class ClarityOptimizer:
         elif self.fused:
             out = loss_torch(raw["uvs"], img, target, geom, k, self.fused_weights)
             total, items = out[:, 3], out[:, :3].detach()
-        else:
+        if self.fused and self.lpips_weight is not None:                   # the target changes every step: nothing to bind
+            perc = self.lpips(target, img).reshape(k, b).mean(dim=1)
+            total, items = total + self.lpips_weight * perc, torch.cat([items, perc.detach().unsqueeze(1)], dim=1)
+        if not self.fused:
             total, items = [], []
             for i in range(k):                                             # brushes are independent: ForgerLosses.compute on each one's samples
                 sl = slice(i * b, (i + 1) * b)

@@ -91,7 +91,7 @@ extern "C" int nb_conv2d_f32(const float* x, const float* w, const float* in_sca
                              int c_in, int h, int wd, int c_out, int kh, int kw, int stride, int pad, void* stream) {
     NB_REQUIRE(x && w && y, "conv2d: null pointer");
     NB_REQUIRE(n >= 1 && n <= 65535 && c_in >= 1 && c_out >= 1 && h >= 1 && wd >= 1, "conv2d: bad sizes");
-    NB_REQUIRE(kh >= 1 && kw >= 1 && kh <= 7 && kw <= 7 && stride >= 1 && pad >= 0, "conv2d: kernel 1..7, stride >= 1, pad >= 0");
+    NB_REQUIRE(kh >= 1 && kw >= 1 && kh <= 11 && kw <= 11 && stride >= 1 && pad >= 0, "conv2d: kernel 1..11, stride >= 1, pad >= 0");
     ConvParams p{x, w, in_scale, out_scale, y, n, c_in, h, wd, c_out, kh, kw, stride, pad, 0, 0};
     p.ho = (h + 2 * pad - kh) / stride + 1; p.wo = (wd + 2 * pad - kw) / stride + 1;
     NB_REQUIRE(p.ho >= 1 && p.wo >= 1, "conv2d: empty output");

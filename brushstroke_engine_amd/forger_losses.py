@@ -6,7 +6,9 @@
   ``--geom_phase_losses='1.0*iou_inv(uvs)'`` / ``--geom_warmstart_losses='1.0*iou_inv(uvs)+1.0*iou(u)'``
   (``train_flags.txt:10-11``): ``forger/train/losses.py:37-233`` (container, string grammar) and the items ``iou``,
   ``iou_inv``, ``dice``, ``dice_inv``, ``l1``, ``gan``, ``rgb`` (``:341-377, 453-546, 634-666``).  The perceptual items
-  (``lpips``, ``plpips``) need the LPIPS network, which neither the reference tree nor this build carries: they raise.
+  (``lpips``, ``plpips``) need the LPIPS network, which neither the reference tree nor this build carries: they raise, unless
+  a network (:class:`perceptual.LPIPS`, which a user loads from weight files) is handed in -- then ``lpips(<component>)`` is built
+  (``:546-565``); ``plpips`` (random crops) keeps raising.
 * :class:`CropHelper`, :class:`RandomStitcher` -- ``forger/train/stitching.py:28-267``: two overlapping crops of one
   drawing are generated with consistent noise positions and composited into each other.
 
@@ -136,6 +138,17 @@ class LossItem:
             shp[1 if len(shp) > 1 else 0] = 3
             tgt = self.rgb.to(x.device, x.dtype).reshape(*shp).expand_as(x)
             return torch.nn.functional.l1_loss(x, tgt) if self.loss_name == "L1" else torch.nn.functional.mse_loss(x, tgt)
+        if n == "lpips":                                             # losses.py:551-565
+            c = self.component
+            if c == "fake_composite":
+                tgt, src = d["fake"], d["fake_composite"]
+            elif c == "fake_orig":
+                tgt, src = d["fake_orig"].detach(), d["fake_img"]
+            elif c == "patch":
+                tgt, src = d["patch1"], d["patch2"]
+            else:
+                self._unsupported()
+            return self.args["net"](tgt, src).mean()
         raise RuntimeError(f"Loss {n} not found in registered losses: " + ", ".join(sorted(_ITEMS)))
 
 
@@ -143,8 +156,9 @@ _ITEMS = {"iou", "iou_inv", "dice", "dice_inv", "l1", "gan", "rgb"}
 _NEEDS_LPIPS = {"lpips", "plpips"}
 
 
-def parse_loss_item(config: str) -> Tuple[float, LossItem]:
-    """``<float>*<loss_name>(<component>[,arg=val...])`` (losses.py:146-233)."""
+def parse_loss_item(config: str, lpips=None) -> Tuple[float, LossItem]:
+    """``<float>*<loss_name>(<component>[,arg=val...])`` (losses.py:146-233).  ``lpips``: a callable ``(target, source) -> [N]``
+    (:class:`perceptual.LPIPS`) for the item ``lpips(<component>)``; without one the item raises."""
     parts = _split(config, "*")
     if len(parts) == 1:
         weight = 1.0
@@ -156,6 +170,12 @@ def parse_loss_item(config: str) -> Tuple[float, LossItem]:
     if m is None:
         raise RuntimeError(f"Mis-configured loss string {config}; expected pattern <float>*<loss_name>(<component>)")
     name, component, argstr = m.group(1), m.group(2), m.group(3)
+    if name == "lpips" and lpips is not None:
+        if component not in _COMPONENTS:
+            raise RuntimeError(f'Component "{component}" not in valid values: ' + ", ".join(sorted(_COMPONENTS)))
+        if argstr:
+            raise RuntimeError(f"Loss lpips takes no arguments, got {argstr}")
+        return weight, LossItem(name, component, net=lpips)
     if name in _NEEDS_LPIPS:
         raise RuntimeError(f"Loss {name} needs the LPIPS network, which is not part of this build (nor of the reference tree)")
     if name not in _ITEMS:
@@ -182,8 +202,8 @@ class ForgerLosses:
                 raise RuntimeError(f"Loss with identifier {nm} defined more than once")
 
     @staticmethod
-    def create_from_string(config: str) -> "ForgerLosses":
-        items = [parse_loss_item(x) for x in _split(config or "", "+")]
+    def create_from_string(config: str, lpips=None) -> "ForgerLosses":
+        items = [parse_loss_item(x, lpips) for x in _split(config or "", "+")]
         return ForgerLosses([i[1] for i in items], [i[0] for i in items])
 
     def set_partial_loss_with_triband_input(self, val: bool):

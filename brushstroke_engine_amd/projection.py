@@ -9,7 +9,8 @@ generator -- conservative masks, mean background colour, composite, L1 over the 
 ``route="hip"``, on the three entries of ``csrc/nb_projection.hip`` and, with ``route="torch"``, as the reference's operations in
 float32 torch (what CPU tests run and what the GPU tests and ``tools/bench_projection.py`` compare against).
 
-The reference's perceptual item needs the LPIPS network, which is not shipped: ``perceptual`` is the plug for it.
+The reference's perceptual item is the LPIPS network: ``perceptual`` takes a :class:`perceptual.LPIPS` (no weights are shipped) or
+any callable.
 """
 from __future__ import annotations
 
@@ -183,7 +184,8 @@ class BrushProjector:
     run); a step is one generator batch of K*B samples, the loss, the noise regulariser and the Adam step with renormalisation.
 
     ``perceptual``: any differentiable callable ``(target, synth) -> [N]`` on images in -1..1 (the plug for the reference's
-    ``lpips_batched_vgg``; no network is shipped), averaged over an exemplar's patches and weighted ``perceptual_weight``.
+    ``lpips_batched_vgg``: a :class:`perceptual.LPIPS` loaded from a user's weight files; none ship), averaged over an exemplar's
+    patches and weighted ``perceptual_weight``.  One that has ``bind(target)`` is bound to the pass's fixed target in ``prepare``.
 
     Departures from the reference.  (1) The best state (project_main.py:159-162) is kept by the perceptual value when there is a
     perceptual item, as there; WITHOUT one the criterion is ``l1_fg_weight * l1 + bg_weight * bg``.  (2) The early stop (:187-207)
@@ -280,6 +282,8 @@ class BrushProjector:
                 fix = dict(fg=fg, bg=bg)
                 counts_host = np.stack([fg.reshape(k, -1).sum(dim=1).cpu().numpy(), bg.reshape(k, -1).sum(dim=1).cpu().numpy()], axis=1)
         fix.update(k=k, b=b, target=target, geom=geom, target_bg=target_bg, norm_pos=norm_pos, feats=feats, bg_color=bg_color, counts_host=counts_host)
+        # a perceptual item that can bind (perceptual.LPIPS) takes the fixed target through its trunk once per pass, here
+        fix["perceptual"] = self.perceptual.bind(target) if hasattr(self.perceptual, "bind") else self.perceptual
         return fix
 
     def check_counts(self, ids, counts_host, has_bg_image: bool) -> None:
@@ -302,7 +306,7 @@ class BrushProjector:
             total, items = out[:, 2], out[:, :2].detach()
         crit = total.detach()
         if self.perceptual is not None:
-            perc = self.perceptual(fix["target"], synth).reshape(k, b).mean(dim=1)
+            perc = fix.get("perceptual", self.perceptual)(fix["target"], synth).reshape(k, b).mean(dim=1)
             total = total + self.perceptual_weight * perc
             crit = perc.detach()
             items = torch.cat([items, crit.unsqueeze(1)], dim=1)

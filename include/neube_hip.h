@@ -803,6 +803,50 @@ int nb_projection_loss_bwd_f32(const float* uvs, long long uvs_stride_n, const f
                                int k, int b, int r, int composite, float w_l1, float w_bg, float* d_uvs, float* d_img, float* d_colors,
                                float* partials, void* stream);
 
+/* ---- LPIPS network (csrc/nb_lpips.hip; perceptual.LPIPS): what surrounds the trunk's convolutions.  All tensors fp32, NCHW, dense.
+ * No float atomics: the same input gives the same bits, and sample i of an n-sample call equals the one-sample call on it.  The entries
+ * only enqueue on `stream`: no allocation, no host wait.  n == 0: NB_OK without a launch.  NB_EINVAL for all: a null pointer (the
+ * optional ones excepted), n outside 0..65535 (nb_lpips_scale_f32: n < 0), a size below 1, c * h * w of 2^31 or more, a pointer not
+ * 4-byte aligned. */
+#define NB_LPIPS_SPLIT_MAX_HW 1024    /* nb_lpips_head_f32 splits the channels over a workgroup for maps of h * w <= this ... */
+#define NB_LPIPS_SPLIT_MIN_C  64      /* ... with at least this many channels; one thread per pixel otherwise */
+
+/* The scaling layer: y[n,c,:] = (x[n,c,:] - shift[c]) / scale[c] over hw pixels per plane; shift NULL = 0, which is the layer's
+ * backward (dx = dy / scale). */
+int nb_lpips_scale_f32(const float* x, const float* shift, const float* scale, float* y, int n, int c, long long hw, void* stream);
+
+/* Bias + ReLU + tap + max-pool behind a convolution, one launch: tap [n,c,h,w] = max(x + bias[c], 0) and, with window 2 or 3,
+ * pooled [n,c,ph,pw] = the maximum of tap over windows of that side, stride 2, no padding, floor mode (ph = (h - window) / 2 + 1).
+ * window 0: no pool, pooled is not written and may be NULL.  One add and maxima, each exactly rounded.  NB_EINVAL also for another
+ * window, or one above h or w. */
+int nb_lpips_relu_pool_f32(const float* x, const float* bias, float* tap, float* pooled, int n, int c, int h, int w, int window, void* stream);
+
+/* Its backward, one launch: d_x [n,c,h,w] from tap (the forward's) and the gradients d_tap [n,c,h,w] and d_pooled [n,c,ph,pw], either of
+ * which may be NULL.  A window's gradient goes to its FIRST maximum in row-major order; a pixel takes d_tap, then its windows in their
+ * order.  d_x = 0 where tap == 0.  NB_EINVAL also for d_pooled with window 0. */
+int nb_lpips_relu_pool_bwd_f32(const float* tap, const float* d_tap, const float* d_pooled, float* d_x, int n, int c, int h, int w, int window,
+                               void* stream);
+
+/* Workgroups that share one sample in nb_lpips_head_f32 for maps of c channels and hw pixels (the floats of `partials` per sample); -1
+ * with nb_last_error set for sizes below 1. */
+long long nb_lpips_head_parts(int c, int hw);
+
+/* One level of the head.  f0, f1 [n,c,hw] raw feature maps, w [c] (any sign).  Per pixel, in one pass over the channels, the sums
+ *   A = sum f0^2,  B = sum f1^2,  P = sum w f0^2,  Q = sum w f1^2,  X = sum w f0 f1      (carried in fp64),
+ * then with i0 = 1 / (sqrt(A) + 1e-10), i1 = 1 / (sqrt(B) + 1e-10), each 0 where its sum is 0:
+ *   d = P i0^2 + Q i1^2 - 2 X i0 i1  =  sum_c w_c (f0_c i0 - f1_c i1)^2.
+ * kept [3, n, hw] receives i0, sqrt(B) and Q i1 - X i0 = sum_c w_c e_c f1_c (e = u1 - u0), which the backward reads.  partials
+ * [n * nb_lpips_head_parts(c, hw)] receives the workgroups' sums of d; the finishing launch adds them in their order and ADDS
+ * sum / hw into acc [n] (the caller zeroes acc before the first level).  Two launches. */
+int nb_lpips_head_f32(const float* f0, const float* f1, const float* w, int n, int c, int hw, float* kept, float* partials, float* acc,
+                      void* stream);
+
+/* Gradient of sum_n g[n] * mean_pixels d with respect to f1 (f0 takes none): with s = kept[1], n1 = s + 1e-10, e_k = f1_k / n1 - f0_k i0,
+ *   d_f1_k = g[n] / hw * (2 w_k e_k / n1 - f1_k * 2 kept[2] / (n1^2 s)),   0 where s == 0
+ * (the package's sqrt gives NaN there).  accumulate != 0: added to what d_f1 [n,c,hw] holds.  One launch. */
+int nb_lpips_head_bwd_f32(const float* f0, const float* f1, const float* w, const float* kept, const float* g, int n, int c, int hw, int accumulate,
+                          float* d_f1, void* stream);
+
 /* ---- geometry encoder (forger/experimental/autoenc/simple_autoencoder.py:88-121, 155-199,
  * 251-261).  Every layer is conv(reflect padding) + bias + LeakyReLU(slope) with eval-mode BatchNorm folded into
  * the weights and bias by the caller.  Activations between layers travel in the H2 format of the split-f16 convs. */
