@@ -12,6 +12,7 @@ import torch.nn.functional as F
 import clarity_refs as cr
 import lpips_refs as lr
 import projection_refs as pr
+import split_branches
 from brushstroke_engine_amd import _lib, clarity, config as cfgmod, ops, perceptual, projection, weights as wmod
 
 pytestmark = pytest.mark.gpu
@@ -221,7 +222,8 @@ _NETWORK = {}
 
 
 def _network_reference(arch):
-    """Once per arch: the case, the float64 statement with its kink margins (CPU), and the float32 torch route on the device."""
+    """Once per case (lpips_refs.SLIM): the case, the float64 statement with its kink margins and the sign pattern of its five taps
+    (CPU), and the float32 torch route on the device."""
     if arch not in _NETWORK:
         w, x0, x1 = lr.network_case(arch)
         rec64, rec32 = [], []
@@ -233,25 +235,35 @@ def _network_reference(arch):
         a32 = _dev(x1).requires_grad_(True)
         v32 = net32(_dev(x0), a32)
         g32, = torch.autograd.grad(v32.sum(), a32)
-        _NETWORK[arch] = dict(w=w, x0=x0, x1=x1, margins=lr.kink_margins(rec64, rec32), v64=v64.detach().numpy(), g64=g64.numpy(),
+        live64 = [pre > 0 for (pre, _win), lay in zip(rec64, lr.layout(lr.SLIM[arch].get("arch", arch))) if lay[4] is not None]
+        _NETWORK[arch] = dict(w=w, x0=x0, x1=x1, margins=lr.kink_margins(rec64, rec32), v64=v64.detach().numpy(), g64=g64.numpy(), live64=live64,
                               v32=v32.detach().cpu().numpy(), g32=g32.cpu().numpy())
     return _NETWORK[arch]
 
 
 @pytest.mark.parametrize("split_f16", [False, True], ids=["fp32", "split_f16"])
-@pytest.mark.parametrize("arch", ["vgg", "alex"])
+@pytest.mark.parametrize("arch", ["vgg", "alex", "vgg64"])
 def test_network_routes_against_float64(arch, split_f16, monkeypatch):
+    """"vgg" and "alex" are below ops.TRAIN_SPLIT_F16_MIN_PIXELS: no split-path branch runs with either setting.  "vgg64" runs its two
+    64 x 64 layers on the split-f16 up = 1 kernel, with the device ``tf`` weight pack in the backward (lpips_refs.NETWORK_BRANCHES)."""
     ref = _network_reference(arch)
     min_pre, min_gap, err = ref["margins"]
     print(f"[lpips] {arch}: smallest |pre-activation| {min_pre:.3g}, smallest pool gap {min_gap:.3g}, float32 pre-activation error {err:.3g}")
     assert min_pre >= lr.KINK_MARGIN * err and min_gap >= lr.KINK_MARGIN * err          # no ReLU / pool decision within reach of rounding
     monkeypatch.setattr(ops, "TRAIN_SPLIT_F16", split_f16)
+    rec = split_branches.record(monkeypatch)
     net = perceptual.LPIPS(ref["w"], device=DEV)
     assert net.route == "hip"
     x0, a = _dev(ref["x0"]), _dev(ref["x1"]).requires_grad_(True)
     got = net(x0, a)
     assert got.shape == (x0.shape[0],)
     g, = torch.autograd.grad(got.sum(), a)
+    torch.cuda.synchronize()
+    print(f"[lpips] {arch} split_f16={split_f16}: branches {sorted(rec)}")
+    split_branches.check(split_f16, rec, lr.NETWORK_BRANCHES[arch], f"{arch} network")
+    # no ReLU decision flipped: the taps of the second image are positive exactly where the float64 statement's are
+    taps = net.target_taps(_dev(ref["x1"]))
+    assert len(taps) == 5 and all(torch.equal((t > 0).cpu(), l64) for t, l64 in zip(taps, ref["live64"])), f"{arch}: a ReLU decision differs from float64"
     factor = lr.SPLIT_F16_FACTOR / cr.BOUND_FACTOR if split_f16 else 1.0
     for name, mine, t32, f64 in (("value", got.detach().cpu().numpy(), ref["v32"], ref["v64"]), ("gradient", g.cpu().numpy(), ref["g32"], ref["g64"])):
         e32, e = float(np.abs(t32.astype(np.float64) - f64).max()), float(np.abs(mine.astype(np.float64) - f64).max())

@@ -2,9 +2,10 @@
 ops.conv2d_down2) at the sizes where they run on the split-f16 kernels, and on the exact-fp32 kernels (TRAIN_SPLIT_F16 =
 WGRAD_SPLIT_F16 = False), against float64 autograd on the CPU (oracle.conv2d_resample / upfirdn2d).
 
-Every case declares the split-path branches it exists for; wrappers around ops._split_f16_eligible, ops._conv2d_s2_valid_h3,
-ops._s2_valid_h3_supported and ops.pack_conv_weight_h3_dev record the branches that ran, and the two sets must agree (no
-split-path branch at all on the exact-fp32 path), so a moved threshold cannot take a case off its path unnoticed.
+Every case declares the split-path branches it exists for; the wrappers of tests/split_branches.py (around ops._conv2d_launch,
+ops._split_f16_eligible, ops._conv2d_s2_valid_h3, ops._s2_valid_h3_supported, ops.pack_conv_weight_h3_dev and the split
+weight-gradient entry) record the branches that ran, and the two sets must agree (no split-path branch at all on the exact-fp32
+path), so a moved threshold cannot take a case off its path unnoticed.
 
 Bounds (tests/test_hip_train_kernels.py): a contraction of L terms is within (L + k + c) U S, S = the float64 sum of |terms|
 -- obtained by running the same linear map on |operands| -- with c = 14 per split-f16 product (0 on the fp32 kernels).  The
@@ -18,6 +19,7 @@ operands ds and the path-length gradient would be random-signed sums of ~sqrt(L)
 import pytest
 import torch
 
+import split_branches
 from brushstroke_engine_amd import ops
 from oracle import neube_oracle as orc
 from test_hip_step_kernels import U, within
@@ -25,7 +27,7 @@ from test_hip_step_kernels import U, within
 pytestmark = pytest.mark.gpu
 C_SPLIT = 14
 F_ACT, F_W, F_WG = 2.0 ** -37, 2.0 ** -25, 2.0 ** -33
-SPLIT_TOKENS = {"split_up1", "split_canvas", "split_up2_w32", "split_up2_w16", "s2v_wide", "s2v_narrow", "tf_pack", "wgrad_h3"}
+SPLIT_TOKENS = split_branches.SPLIT_TOKENS
 FIR = orc.setup_filter(dtype=torch.float64)
 
 
@@ -37,63 +39,19 @@ def dev():
 
 @pytest.fixture(params=[True, False], ids=["split_f16", "fp32"])
 def mode(request, monkeypatch):
-    """Sets TRAIN_SPLIT_F16 = WGRAD_SPLIT_F16 and records the split-path branches that run; flags restored in finally."""
+    """Sets TRAIN_SPLIT_F16 = WGRAD_SPLIT_F16 and records the split-path branches that run (tests/split_branches.py); flags restored
+    on the way out."""
     split = request.param
-    rec = set()
-    elig, s2ok, s2run, pack = ops._split_f16_eligible, ops._s2_valid_h3_supported, ops._conv2d_s2_valid_h3, ops.pack_conv_weight_h3_dev
-    lib = ops._lib.lib()
-    wg = lib.nb_conv2d_wgrad_h3_ws
-
-    def w_elig(n, h, w_, up):
-        r = elig(n, h, w_, up)
-        if r:
-            rec.add(("split_up1" if ops._pow2(h) and ops._pow2(w_) else "split_canvas") if up == 1 else
-                    ("split_up2_w16" if w_ == 16 else "split_up2_w32"))
-        else:
-            rec.add("off_split")                                         # (a convolution that stays on the fp32 kernels)
-        return r
-
-    def w_wgrad(*args):
-        rec.add("wgrad_h3")
-        return wg(*args)
-
-    def w_s2ok(n, ci, h, wd, kh, kw, stride, padding):
-        r = s2ok(n, ci, h, wd, kh, kw, stride, padding)
-        if not r and stride == 2:
-            rec.add("s2_generic")
-        return r
-
-    def w_s2run(x, w, in_scale, out_scale):
-        rec.add("s2v_wide" if ((x.shape[3] - 1) // 2) % 32 == 0 else "s2v_narrow")
-        return s2run(x, w, in_scale, out_scale)
-
-    def w_pack(weight, co_align=64, tf=False):
-        if tf:
-            rec.add("tf_pack")
-        return pack(weight, co_align, tf)
-
-    monkeypatch.setattr(ops, "_split_f16_eligible", w_elig)
-    monkeypatch.setattr(ops, "_s2_valid_h3_supported", w_s2ok)
-    monkeypatch.setattr(ops, "_conv2d_s2_valid_h3", w_s2run)
-    monkeypatch.setattr(ops, "pack_conv_weight_h3_dev", w_pack)
-    monkeypatch.setattr(lib, "nb_conv2d_wgrad_h3_ws", w_wgrad)
-    saved = ops.TRAIN_SPLIT_F16, ops.WGRAD_SPLIT_F16
-    try:
-        ops.TRAIN_SPLIT_F16 = ops.WGRAD_SPLIT_F16 = split
+    rec = split_branches.record(monkeypatch)
+    with split_branches.flags(split):
         yield split, rec
-    finally:
-        ops.TRAIN_SPLIT_F16, ops.WGRAD_SPLIT_F16 = saved
 
 
 def branches_ok(mode, declared, what):
     """Split mode: the branches that ran are the declared ones plus the split weight-gradient kernel (WGRAD_SPLIT_F16 holds at
     every size; every case here computes a weight gradient).  fp32 mode: no split-path branch at all."""
     split, rec = mode
-    if split:
-        ran = rec - {"off_split"}
-        assert ran == set(declared) | {"wgrad_h3"}, f"{what}: declared branches {sorted(set(declared) | {'wgrad_h3'})}, ran {sorted(ran)}"
-    else:
-        assert not (rec & SPLIT_TOKENS), f"{what}: split-f16 branches ran with the flags off: {sorted(rec & SPLIT_TOKENS)}"
+    split_branches.check(split, rec, set(declared) | {"wgrad_h3"}, what)
 
 
 def vjp(fn, args, i, cot):

@@ -20,7 +20,7 @@ def slim_vgg():
     return perceptual.LPIPS(lr.slim_weights("vgg", (4, 6, 8, 8, 8), 1), route="torch", device="cpu")
 
 
-@pytest.mark.parametrize("arch", ["vgg", "alex"])
+@pytest.mark.parametrize("arch", ["vgg", "alex", "vgg64"])
 def test_torch_route_against_float64_statement(arch):
     """Values and the gradient of the second image.  The float32 route differs from the statement by rounding, 13 (5) layers deep:
     asserted at 1e-4 of the value and 1e-3 of the largest gradient on cases whose ReLU and pool decisions are the same in both
@@ -37,7 +37,7 @@ def test_torch_route_against_float64_statement(arch):
     want = want.detach()
     assert float(want.min()) > 0 and float(g64.abs().max()) > 0
     net = perceptual.LPIPS(w, route="torch", device="cpu")
-    assert net.arch == arch and net.route == "torch"
+    assert net.arch == lr.SLIM[arch].get("arch", arch) and net.route == "torch"
     a = torch.from_numpy(x1).requires_grad_(True)
     got = net(torch.from_numpy(x0), a)
     g, = torch.autograd.grad(got.sum(), a)
@@ -47,6 +47,87 @@ def test_torch_route_against_float64_statement(arch):
     bound = net.bind(torch.from_numpy(x0))
     assert torch.equal(bound(torch.from_numpy(x0), a.detach()), got.detach())
     assert float(net(torch.from_numpy(x0), torch.from_numpy(x0)).abs().max()) == 0.0
+
+
+def test_the_split_path_network_case_reaches_the_threshold_at_its_first_two_layers_only():
+    """"vgg64": n h w of the two 64 x 64 layers is ops.TRAIN_SPLIT_F16_MIN_PIXELS itself; every later layer is below it."""
+    from brushstroke_engine_amd import ops
+    c = lr.SLIM["vgg64"]
+    assert c["arch"] == "vgg" and c["channels"] == (4, 8, 12, 12, 16) and c["seed"] == 52 and sorted(lr.NETWORK_BRANCHES) == sorted(lr.SLIM)
+    sizes, side = [], c["size"]
+    for _i, _k, _s, _p, _lvl, win in lr.layout("vgg"):
+        sizes.append(c["n"] * side * side)
+        side = side // 2 if win else side
+    assert sizes[:2] == [ops.TRAIN_SPLIT_F16_MIN_PIXELS] * 2 and max(sizes[2:]) < ops.TRAIN_SPLIT_F16_MIN_PIXELS
+    # the older cases: below it at every 3 x 3 layer (alex's 11 x 11 stride-4 and 5 x 5 layers are on the generic kernel at any size)
+    assert lr.SLIM["vgg"]["n"] * lr.SLIM["vgg"]["size"] ** 2 < ops.TRAIN_SPLIT_F16_MIN_PIXELS
+    assert lr.SLIM["alex"]["n"] * lr.layer_out_size(lr.SLIM["alex"]["size"], 11, 4, 2) ** 2 < ops.TRAIN_SPLIT_F16_MIN_PIXELS
+
+
+@pytest.mark.parametrize("case", lr.LAYER_CASES, ids=lr.LAYER_IDS)
+def test_layer_case_operands_are_what_the_trunk_feeds_its_convolutions(case):
+    """The stated properties of tests/test_hip_lpips_trunk_f64.py's operands, and that its bounds can catch an error."""
+    name, n, ci, co, h, w_, k, s, p, fwd, bwd = case
+    ref = lr.layer_reference(case)
+    x, w, d = ref["x"], ref["w"], ref["d"]
+    ho, wo = lr.layer_out_size(h, k, s, p), lr.layer_out_size(w_, k, s, p)
+    assert tuple(x.shape) == (n, ci, h, w_) and tuple(w.shape) == (co, ci, k, k) and tuple(d.shape) == (n, co, ho, wo)
+    assert all(t.dtype == torch.float32 and bool(torch.isfinite(t).all()) for t in (x, w, d))
+    if ci == 3:                                                            # the scaled image: both signs, within (+-1 - shift) / scale
+        lim = max((1 + abs(sh)) / sc for sh, sc in zip(lr.SHIFT, lr.SCALE))
+        assert float(x.min()) < -1 and float(x.max()) > 1 and float(x.abs().max()) <= lim
+    else:                                                                  # ReLU outputs: a third of zeros, per-sample scales 1, 2^-6
+        assert float(x.min()) == 0.0 and 0.3 <= float((x == 0).float().mean()) <= 0.4
+        assert all(float(x[i].max()) < 2.0 ** -6 * 8 for i in range(1, n, 2)) and all(float(x[i].max()) > 2 for i in range(0, n, 2))
+    # the gradient: one survivor per 2 x 2 window, 1 / (h w), per-sample scales with an all-zero sample where n >= 4
+    scales = [float(d[i].abs().max()) for i in range(n)]
+    zero = [i for i in range(n) if scales[i] == 0.0]
+    assert zero == ([i for i in range(n) if i % 4 == 3] if n >= 4 else [])
+    live = d[[i for i in range(n) if i not in zero]]
+    per_window = torch.nn.functional.avg_pool2d((live != 0).float(), 2, 2, ceil_mode=True, divisor_override=1)
+    assert float(per_window.max()) <= 1.0
+    frac = float((live == 0).float().mean())
+    assert frac == 0.75 if (ho % 2 == 0 and wo % 2 == 0) else 0.70 <= frac <= 0.80, (name, frac)
+    assert scales[0] <= 6.0 / (ho * wo) and scales[0] >= 1.0 / (ho * wo) and (n == 1 or scales[1] <= scales[0] * 2.0 ** -5)
+    # the declared routes follow from the shapes (ops.conv2d's thresholds)
+    from brushstroke_engine_amd import ops
+    pow2 = ops._pow2(h) and ops._pow2(w_)
+    big = n * ho * wo >= ops.TRAIN_SPLIT_F16_MIN_PIXELS
+    want = set() if (k, s, p) != (3, 1, 1) or not big or min(ho, wo) < 16 else ({"split_up1"} if pow2 else {"split_canvas"})
+    assert fwd == want and bwd == (want | {"tf_pack"} if want == {"split_up1"} else want)
+    # zeroing one channel moves the float64 results by >= 20 bounds, in either mode's bound
+    for split in (False, True):
+        t_y, t_dx = lr.layer_bounds(case, ref, split)
+        assert t_y.shape == ref["y"].shape and t_dx.shape == ref["dx"].shape
+        assert float((ref["y"] - ref["y_bad"]).abs().max()) >= lr.CATCH_FACTOR * float(t_y.max())
+        assert float((ref["dx"] - ref["dx_bad"]).abs().max()) >= lr.CATCH_FACTOR * float(t_dx.max())
+    # the reference is float64 F.conv2d and its autograd: checked against a direct sum at one output and one input element
+    x64, w64, d64 = x.double(), w.double(), d.double()
+    xp = torch.nn.functional.pad(x64, (p, p, p, p))
+    i, o, r, c_ = n - 1 - (1 if zero and (n - 1) in zero else 0), co - 1, ho - 1, wo // 2
+    direct = float((xp[i, :, r * s:r * s + k, c_ * s:c_ * s + k] * w64[o]).sum())
+    assert abs(direct - float(ref["y"][i, o, r, c_])) <= 1e-12 * float(ref["y_abs"][i, o, r, c_])
+    a, rr, cc = ci - 1, h - 1, w_ - 1                                      # the last row and column: what the remainder padding yields
+    tot = 0.0
+    for u in range(ho):
+        for v in range(wo):
+            kr, kc = rr + p - u * s, cc + p - v * s
+            if 0 <= kr < k and 0 <= kc < k:
+                tot += float((d64[i, :, u, v] * w64[:, a, kr, kc]).sum())
+    assert abs(tot - float(ref["dx"][i, a, rr, cc])) <= 1e-12 * max(float(ref["dx_abs"][i, a, rr, cc]), 1e-300)
+
+
+def test_stride4_layer_cases_have_every_remainder():
+    """alex's 11 x 11 stride-4 layer at image sides 63 .. 67: remainders 0, 1, 2, 3, 0 of perceptual._conv_input_grad's right / bottom
+    padding (the slim whole-network case has 1 only)."""
+    sides = sorted({c[4] for c in lr.LAYER_CASES if c[7] == 4})
+    assert sides == [63, 64, 65, 66, 67] and {c[3] for c in lr.LAYER_CASES if c[7] == 4} == {8, 64}
+    assert [lr.stride_remainder(sd, 11, 4, 2) for sd in sides] == [0, 1, 2, 3, 0] == [lr.STRIDE4_REMAINDERS[sd] for sd in sides]
+    assert lr.stride_remainder(lr.SLIM["alex"]["size"], 11, 4, 2) == 1
+    for sd in sides:                                                       # the remainder is what the zero-stuffed gradient lacks
+        ho = lr.layer_out_size(sd, 11, 4, 2)
+        stuffed = (ho - 1) * 4 + 1
+        assert stuffed + lr.stride_remainder(sd, 11, 4, 2) + 2 * (11 - 1 - 2) - 11 + 1 == sd
 
 
 def test_zero_norm_pixels_give_a_finite_zero_gradient():
