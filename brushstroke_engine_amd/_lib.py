@@ -168,6 +168,10 @@ PROTOTYPES = {
     # brush scores (csrc/nb_metrics.hip): evaluation masks of the drawings, the per-image sums of the colour and transparency metrics
     "nb_eval_masks_f32": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "nb_brush_metrics_f32": (C.c_int, [vp, C.c_longlong, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp]),
+    # inputs of the perceptual brush scores (csrc/nb_metric_patches.hip): the once-blurred guidance, masked mean colours, the patch pairs
+    "nb_bg_guidance_f32": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+    "nb_bg_mean_colors_f32": (C.c_int, [vp, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "nb_metric_pairs_f32": (C.c_int, [vp, C.c_longlong, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     # clarity optimisation (csrc/nb_clarity.hip): the fused loss and its gradient, the noise regulariser, the Adam + renormalise step
     "nb_clarity_scratch_floats": (C.c_longlong, [vp, C.c_int, C.c_longlong, C.c_int]),
     "nb_clarity_loss_f32": (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_float,
@@ -287,6 +291,8 @@ class NbPassPlan(C.Structure):
 NB_GEOM_PREP_WS_BYTES = 1040
 NB_SEG_PITCH = 8
 NB_BRUSH_METRICS_PARTS = 16
+NB_BG_MEAN_PARTS = 16
+NB_METRIC_PAIRS_TRANSPOSE, NB_METRIC_PAIRS_MASKED = 1, 2
 NB_CLARITY_MAX_PLANES, NB_CLARITY_LOSS_PARTS, NB_CLARITY_CHUNK = 32, 8, 1024
 NB_PROJECTION_PARTS = 8
 NB_LPIPS_SPLIT_MAX_HW, NB_LPIPS_SPLIT_MIN_C = 1024, 64

@@ -1,9 +1,11 @@
 """Scores of a brush library -- LAB_E%, LAB_L2, BG_CLARITY_MEAN and FG_OPACITY_MEDIAN per brush, the numbers the reference's
 ``paint_engine_metric_loop`` reports (forger/metrics/metric_main.py:105-236) -- computed in batches on the device
-(``metrics.BrushEvaluator``).
+(``metrics.BrushEvaluator``).  With ``--lpips_weights`` the three perceptual numbers LPIPS_ACROSS_GEO, LPIPS_UNIFORM_BG and
+LPIPS_UNIFORM_BG_multicolor join them, and the files carry seven columns.
 
     python -m brushstroke_engine_amd.brush_metrics_main --gan_checkpoint engine.npz --library rand100 --drawings drawings.npz \\
-        --output_dir out [--uvs_calibration cal.npz] [--rounds 1] [--batch 32] [--seed 0] [--lab_thresh 10] [--prefix ''] [--conv_mode h3]
+        --output_dir out [--uvs_calibration cal.npz] [--rounds 1] [--batch 32] [--seed 0] [--lab_thresh 10] [--prefix ''] [--conv_mode h3] \\
+        [--lpips_weights alex.npz] [--lpips_net alex] [--patch_width P]
 
 ``--drawings`` is an .npz whose first array (or the one named ``drawings``) holds [K,R,R] uint8 guidance drawings, 0 = stroke.
 ``--library`` is what ``paint_image_main`` takes.  Three files are written to ``--output_dir``: ``<prefix>style_metrics.txt`` and
@@ -38,6 +40,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lab_thresh", type=float, default=10)
     ap.add_argument("--conv_mode", default=None, choices=["f8", "h3", "f32"],
                     help="arithmetic of the conv layers (default: networks.DEFAULT_CONV_MODE)")
+    ap.add_argument("--lpips_weights", default=None,
+                    help=".npz written by tools/convert_lpips_weights.py: also report LPIPS_ACROSS_GEO, LPIPS_UNIFORM_BG and "
+                         "LPIPS_UNIFORM_BG_multicolor (the reference scores with the 'alex' network)")
+    ap.add_argument("--lpips_net", default=None, choices=["alex", "vgg"], help="the network of --lpips_weights (default: the file's 'arch' entry)")
+    ap.add_argument("--patch_width", type=int, default=None,
+                    help="side of the windows of the LPIPS_UNIFORM_BG scores (default: R / 4, R / 2 or 0.8 R, the first of at least 64)")
     return ap
 
 
@@ -70,7 +78,11 @@ def main(argv=None):
     library = formats.BrushLibrary.from_arg(args.library, z_dim=G.z_dim)
     with torch.no_grad():
         evaluator = metrics.BrushEvaluator(ops, load_drawings(args.drawings), seed=args.seed, uvs_mapper=mapper)
-        scores = evaluator.evaluate(library, rounds=args.rounds, batch=args.batch, lab_thresh=args.lab_thresh)
+        kw = {}
+        if args.lpips_weights:
+            from .perceptual import LPIPS
+            kw = dict(lpips=LPIPS(args.lpips_weights, net=args.lpips_net, device=device), patch_width=args.patch_width)
+        scores = evaluator.evaluate(library, rounds=args.rounds, batch=args.batch, lab_thresh=args.lab_thresh, **kw)
     paths = write_scores(scores, args.output_dir, args.prefix)
     logger.info(f"Scored {len(scores.ids)} brushes: {paths}")
     for p in paths:

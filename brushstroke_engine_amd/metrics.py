@@ -1,4 +1,4 @@
-"""Brush scores: the four numbers the reference reports per brush (``paint_engine_metric_loop``, forger/metrics/metric_main.py:105-236),
+"""Brush scores: the numbers the reference reports per brush (``paint_engine_metric_loop``, forger/metrics/metric_main.py:105-236),
 computed where the renders are.
 
     LAB_E%, LAB_L2                       how well the stroke takes the user's primary colour, in CIE Lab
@@ -9,12 +9,27 @@ computed where the renders are.
 The three functions keep the reference's signatures and keys, so a caller of the reference can switch; ``BrushEvaluator`` scores a
 whole library in batches: ``floor(batch / K)`` brushes share a generator pass on the K drawings, ``ops.brush_metrics`` reduces the
 pass's renders to four sums per image in one launch, and the pooled median is ``ops.masked_kth_largest`` on the alpha planes it
-leaves.  Nothing is copied to the host until the ``BrushScores`` are assembled.  The reference's LPIPS-based items (``BG_LPIPS*``,
-``STITCH_*``, ``LPIPS_ACROSS_GEO``) need a pretrained network and are not part of this module.
+leaves.  Nothing is copied to the host until the ``BrushScores`` are assembled.
+
+With an LPIPS network (``perceptual.LPIPS``; the reference uses ``alex``) three perceptual numbers join them:
+
+    LPIPS_UNIFORM_BG_multicolor          whether the background is uniform: LPIPS between two random windows of a render (the second
+    LPIPS_UNIFORM_BG                     transposed) with everything but the common background filled with the background's mean colour
+                                         (``compute_uniform_bg_lpips_metric``, forger/metrics/geom_metric.py:207-262) -- on the render with
+                                         random primary colours, and on a second render with the brush's own colours, pairs permuted
+    LPIPS_ACROSS_GEO                     whether the brush looks the same on different drawings: LPIPS between the K own-colour
+                                         renders and a permutation of them (``compute_lpips_across_geo``, geom_metric.py:190-204)
+
+``ops.bg_mean_colors`` and ``ops.metric_pairs`` (csrc/nb_metric_patches.hip) write the network's input of both sides of all pairs of
+a pass into one buffer, and ``LPIPS.pair_distance`` runs the trunk once over it.  The random windows and permutations come from a
+seeded plan (``default_crops``): the reference draws them from the process-global stream, so no seed reproduces ITS draws; the
+distribution is the same.  ``STITCH_LPIPS`` / ``STITCH_L1`` (metric_main.py:181-200: two positioned renders of overlapping crops of
+full-size drawings, which the reference itself skips for W+ brushes) and ``BG_LPIPS*`` are not part of this module.
 """
 from __future__ import annotations
 
 import dataclasses
+import inspect
 import json
 import os
 from typing import Callable, Dict, List, Optional, Sequence
@@ -25,7 +40,9 @@ import torch
 from .tile_ops import EvalMasks, TileOpsBase, lab_deltas_torch
 
 KEYS = ("BG_CLARITY_MEAN", "FG_OPACITY_MEDIAN", "LAB_E%", "LAB_L2")          # sorted, the column order of the reference's files
-_HIGHER_IS_BETTER = {"BG_CLARITY_MEAN": True, "FG_OPACITY_MEDIAN": True, "LAB_E%": False, "LAB_L2": False}
+PERCEPTUAL_KEYS = ("LPIPS_ACROSS_GEO", "LPIPS_UNIFORM_BG", "LPIPS_UNIFORM_BG_multicolor")          # sorted likewise; they sort behind KEYS
+_HIGHER_IS_BETTER = {"BG_CLARITY_MEAN": True, "FG_OPACITY_MEDIAN": True, "LAB_E%": False, "LAB_L2": False, "LPIPS_ACROSS_GEO": False,
+                     "LPIPS_UNIFORM_BG": False, "LPIPS_UNIFORM_BG_multicolor": False}
 
 
 def _fg_pool(masks: EvalMasks):
@@ -88,6 +105,56 @@ def compute_transparency_metrics(renders, geom, ops=None):
     return {"BG_CLARITY_MEAN": s[0, 0].item(), "FG_OPACITY_MEDIAN": s[0, 1].item()}
 
 
+def default_patch_width(r: int) -> int:
+    """The window of ``compute_uniform_bg_lpips_metric`` for renders of side ``r`` (geom_metric.py:224-229): a quarter, else half
+    where that stays at 64 or above, else 0.8 r."""
+    p = r // 4
+    if p < 64:
+        p = r // 2
+        if p < 64:
+            p = int(0.8 * r)
+    return p
+
+
+def _i32(device, a) -> torch.Tensor:
+    return torch.as_tensor(np.asarray(a, np.int32)).to(device)
+
+
+def compute_uniform_bg_lpips_metric(renders, geom, lpips, patch_width=None, same_style=False, key_suffix=None, crops=None, ops=None):
+    """({'LPIPS_UNIFORM_BG[_<key_suffix>]': value}, None) of ``renders`` [B,4,W,W] on the guidance ``geom`` [B,1,W,W], every image
+    on its own drawing (geom_metric.py:207-262; the None stands for the debug image, which is not made).  ``lpips``: a
+    ``perceptual.LPIPS``.  ``crops`` = (offset of the first window (row, column), of the second, permutation [B] or None): the
+    draws of the call; None draws them as the reference does, from torch's global stream (one window pair per call, a permutation
+    with ``same_style``).  ``ops``: whose ``bg_guidance`` / ``bg_mean_colors`` / ``metric_pairs`` prepare the pairs (``TileOps``:
+    three launches); None: the torch restatement where the tensors are."""
+    ops = TileOpsBase() if ops is None else ops
+    key = "LPIPS_UNIFORM_BG" if key_suffix is None else f"LPIPS_UNIFORM_BG_{key_suffix}"
+    b, r = renders.shape[0], renders.shape[-1]
+    p = default_patch_width(r) if patch_width is None else int(patch_width)
+    if crops is None:
+        off0, off1 = (torch.randint(0, r - p + 1, (2,)).tolist() for _ in range(2))
+        perm = torch.randperm(b).tolist() if same_style else None
+    else:
+        off0, off1, perm = crops
+    guidance = ops.bg_guidance(geom.squeeze(1).to(torch.float32).contiguous())
+    mean = ops.bg_mean_colors(renders, guidance)
+    dev = renders.device
+    x = ops.metric_pairs(renders, guidance, mean, _i32(dev, [list(off0)] * b).reshape(b, 2), _i32(dev, [list(off1)] * b).reshape(b, 2),
+                         None if perm is None else _i32(dev, perm), p, True, True)
+    return {key: lpips.pair_distance(x).mean().item()}, None
+
+
+def compute_lpips_across_geo(renders, lpips, perm=None, ops=None):
+    """{'LPIPS_ACROSS_GEO': value} of the renders [B,4,W,W] of ONE brush and colour (geom_metric.py:190-204): LPIPS between
+    the on-white renders and a permutation of them (``perm`` [B]; None draws ``torch.randperm`` from the global stream)."""
+    ops = TileOpsBase() if ops is None else ops
+    b, r, dev = renders.shape[0], renders.shape[-1], renders.device
+    perm = torch.randperm(b).tolist() if perm is None else perm
+    zero = torch.zeros([b, 2], dtype=torch.int32, device=dev)
+    x = ops.metric_pairs(renders, None, None, zero, zero, _i32(dev, perm), r, False, False)
+    return {"LPIPS_ACROSS_GEO": lpips.pair_distance(x).mean().item()}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # a whole library
 # ---------------------------------------------------------------------------------------------------------------------
@@ -100,37 +167,47 @@ def file_line(values, strip=True) -> str:
     return " ".join("{:>8}".format(c) for c in cells) + "\n"
 
 
-def value_cells(values: Dict[str, float]) -> List[str]:
-    """The values in the order of ``KEYS``, four decimals, each as wide as its key (``ordered_dict_values``, metric_main.py:48-57)."""
-    return [("{:>%d.4f}" % len(k)).format(values[k]) for k in KEYS]
+def value_cells(values: Dict[str, float], keys: Sequence[str] = KEYS) -> List[str]:
+    """The values in the order of ``keys``, four decimals, each as wide as its key (``ordered_dict_values``, metric_main.py:48-57)."""
+    return [("{:>%d.4f}" % len(k)).format(values[k]) for k in keys]
 
 
 @dataclasses.dataclass
 class BrushScores:
-    """The scores of a library's brushes (``BrushEvaluator.evaluate``), on the host: four float32 arrays [B] in the order of ``ids``."""
+    """The scores of a library's brushes (``BrushEvaluator.evaluate``), on the host: four float32 arrays [B] in the order of ``ids``,
+    and, from a run with an LPIPS network, ``perceptual``: {key of ``PERCEPTUAL_KEYS``: float32 [B]}."""
     ids: List
     lab_e_percent: np.ndarray          # LAB_E%: share (in %) of the stroke's weight whose Lab distance to the picked colour exceeds lab_thresh
     lab_l2: np.ndarray                 # LAB_L2: mean over ALL pixels of weight * Lab distance
     bg_clarity_mean: np.ndarray        # BG_CLARITY_MEAN: 1 - mean alpha on sure background; NaN without background
     fg_opacity_median: np.ndarray      # FG_OPACITY_MEDIAN: lower median of alpha on the strokes; NaN without foreground
+    perceptual: Optional[Dict[str, np.ndarray]] = None          # the three LPIPS numbers (lower = more uniform); None: not computed
+
+    def keys(self) -> tuple:
+        """The columns, sorted as the reference's files: ``KEYS``, and ``PERCEPTUAL_KEYS`` behind them when they were computed."""
+        return KEYS if self.perceptual is None else KEYS + PERCEPTUAL_KEYS
 
     def as_dict(self) -> Dict[str, np.ndarray]:
-        return {"BG_CLARITY_MEAN": self.bg_clarity_mean, "FG_OPACITY_MEDIAN": self.fg_opacity_median, "LAB_E%": self.lab_e_percent,
-                "LAB_L2": self.lab_l2}
+        d = {"BG_CLARITY_MEAN": self.bg_clarity_mean, "FG_OPACITY_MEDIAN": self.fg_opacity_median, "LAB_E%": self.lab_e_percent,
+             "LAB_L2": self.lab_l2}
+        if self.perceptual is not None:
+            d.update({k: self.perceptual[k] for k in PERCEPTUAL_KEYS})
+        return d
 
     def summary(self) -> Dict[str, float]:
         """The mean over the brushes, as the reference's summary file (a NaN brush makes the mean NaN, as there)."""
         return {k: (float(np.mean(v.astype(np.float64))) if len(v) else float("nan")) for k, v in self.as_dict().items()}
 
     def rank(self, key: str) -> List:
-        """The ids, best brush first: ascending for LAB_E% and LAB_L2, descending for the clarity and the opacity; NaN last."""
+        """The ids, best brush first: ascending for LAB_E%, LAB_L2 and the LPIPS numbers, descending for the clarity and the opacity;
+        NaN last."""
         v = self.as_dict()[key].astype(np.float64)
         order = np.argsort(np.where(np.isnan(v), np.inf, -v if _HIGHER_IS_BETTER[key] else v), kind="stable")
         return [self.ids[i] for i in order.tolist()]
 
     def to_json(self) -> str:
         d = self.as_dict()
-        return json.dumps({"ids": [str(i) for i in self.ids], "metrics": {k: [float(x) for x in d[k]] for k in KEYS},
+        return json.dumps({"ids": [str(i) for i in self.ids], "metrics": {k: [float(x) for x in d[k]] for k in self.keys()},
                            "summary": self.summary()})
 
     def write_reference_files(self, out_dir: str, prefix: str = ""):
@@ -138,14 +215,14 @@ class BrushScores:
         (metric_main.py:203-228): keys sorted, every cell right-aligned in at least eight characters.  Returns both paths."""
         os.makedirs(out_dir, exist_ok=True)
         style, summary = os.path.join(out_dir, f"{prefix}style_metrics.txt"), os.path.join(out_dir, f"{prefix}summary_metrics.txt")
-        d = self.as_dict()
+        d, keys = self.as_dict(), self.keys()
         with open(style, "w") as f:
-            f.write("SEED            " + file_line(KEYS))
+            f.write("SEED            " + file_line(keys))
             for i, sid in enumerate(self.ids):
-                f.write("{:<15}".format(sid) + " " + file_line(value_cells({k: float(d[k][i]) for k in KEYS}), strip=False))
+                f.write("{:<15}".format(sid) + " " + file_line(value_cells({k: float(d[k][i]) for k in keys}, keys), strip=False))
         with open(summary, "w") as f:
-            f.write(file_line(KEYS))
-            f.write(file_line(value_cells(self.summary()), strip=False))
+            f.write(file_line(keys))
+            f.write(file_line(value_cells(self.summary(), keys), strip=False))
         return style, summary
 
 
@@ -158,6 +235,44 @@ def default_colors(seed: int, n_brushes: int, rounds: int, k: int) -> np.ndarray
         for r in range(rounds):
             out[b, r] = torch.rand((k, 3), dtype=torch.float32, generator=gen).numpy()
     return out
+
+
+def default_crops(seed: int, n_brushes: int, rounds: int, k: int, r: int, p: int) -> Dict[str, np.ndarray]:
+    """The random plan of the perceptual scores for every (brush, round), from a CPU ``torch.Generator`` seeded ``seed + 2``.  Per
+    unit, brush-major, in THIS order of draws:
+
+        multi_off0, multi_off1   [B, rounds, 2] int32   the two windows (row, column) of LPIPS_UNIFORM_BG_multicolor, ``randint(0, r - p + 1, (2,))`` each
+        same_off0, same_off1     [B, rounds, 2] int32   the two windows of LPIPS_UNIFORM_BG, likewise
+        same_perm                [B, rounds, K] int32   its permutation of the K samples, ``randperm(k)`` (geom_metric.py:252)
+        geo_perm                 [B, rounds, K] int32   the permutation of LPIPS_ACROSS_GEO, ``randperm(k)`` (geom_metric.py:201)
+
+    One window pair serves the K samples of a unit: the reference's ``RandomCrop`` draws once per batched call (geom_metric.py:48-56,
+    247-248).  Stated departure: the reference draws from the process-global streams, so no seed reproduces its draws; the
+    distribution is the same."""
+    if not 1 <= int(p) <= int(r):
+        raise ValueError(f"default_crops: patch width {p} outside 1..{r}")
+    gen = torch.Generator().manual_seed(int(seed) + 2)
+    out = {name: np.zeros([n_brushes, rounds, 2], np.int32) for name in ("multi_off0", "multi_off1", "same_off0", "same_off1")}
+    out.update({name: np.zeros([n_brushes, rounds, k], np.int32) for name in ("same_perm", "geo_perm")})
+    for b in range(n_brushes):
+        for j in range(rounds):
+            for name in ("multi_off0", "multi_off1", "same_off0", "same_off1"):
+                out[name][b, j] = torch.randint(0, r - p + 1, (2,), generator=gen).numpy()
+            for name in ("same_perm", "geo_perm"):
+                out[name][b, j] = torch.randperm(k, generator=gen).numpy()
+    return out
+
+
+CROP_KEYS = ("multi_off0", "multi_off1", "same_off0", "same_off1", "same_perm", "geo_perm")
+
+
+def _takes_keyword(fn, name: str) -> bool:
+    """Whether the callback ``fn`` accepts the keyword ``name`` (by name or through ``**kwargs``)."""
+    try:
+        params = inspect.signature(fn).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return any(q.name == name or q.kind is q.VAR_KEYWORD for q in params)
 
 
 class BrushEvaluator:
@@ -177,6 +292,7 @@ class BrushEvaluator:
         self.fg_mask, self.n_fg = _fg_pool(self.masks)
         self._features: Dict = {}
         self._noise_set, self._noise_src = None, None
+        self._guidance = None
 
     @property
     def k(self) -> int:
@@ -207,6 +323,33 @@ class BrushEvaluator:
             self._noise_src = bufs
         return bn
 
+    @property
+    def guidance(self):
+        """The once-blurred guidance of the drawings (``ops.bg_guidance``), built at the first perceptual score."""
+        if self._guidance is None:
+            self._guidance = self.ops.bg_guidance(self.masks.geom)
+        return self._guidance
+
+    def perceptual_scores(self, lpips, renders: torch.Tensor, p: int, off0: torch.Tensor, off1: torch.Tensor,
+                          perm: Optional[torch.Tensor] = None, geo_perm: Optional[torch.Tensor] = None):
+        """(LPIPS_UNIFORM_BG [nu], LPIPS_ACROSS_GEO [nu] or None) on the device, of ``renders`` [nu*K,4,R,R], brush-major: each the
+        mean over a unit's K pairs.  ``off0``, ``off1`` [nu,2] int32: a unit's two windows; ``perm`` [nu,K] int32: the unit's
+        permutation of the second patches (None: none, the multicolour form); ``geo_perm`` [nu,K]: also score the across-drawing
+        pairs.  Per metric: one launch for the pairs and one trunk pass over all 2 nu K images."""
+        ops, k = self.ops, self.k
+        nu = renders.shape[0] // k
+        base = (torch.arange(nu, dtype=torch.int32, device=renders.device) * k).unsqueeze(1)
+        src = lambda q: None if q is None else (base + q).reshape(-1).contiguous()
+        mean = ops.bg_mean_colors(renders, self.guidance)
+        x = ops.metric_pairs(renders, self.guidance, mean, off0.repeat_interleave(k, 0).contiguous(), off1.repeat_interleave(k, 0).contiguous(),
+                             src(perm), p, True, True)
+        uniform = lpips.pair_distance(x).view(nu, k).mean(dim=1)
+        if geo_perm is None:
+            return uniform, None
+        zero = torch.zeros([nu * k, 2], dtype=torch.int32, device=renders.device)
+        x = ops.metric_pairs(renders, None, None, zero, zero, src(geo_perm), renders.shape[-1], False, False)
+        return uniform, lpips.pair_distance(x).view(nu, k).mean(dim=1)
+
     def score_renders(self, renders: torch.Tensor, targets: torch.Tensor, lab_thresh: float = 10) -> torch.Tensor:
         """[nu, 4] in the order of ``KEYS``, on the device: ``renders`` [nu*K,4,R,R] of nu brushes on the K drawings, brush-major,
         against the per-sample colours ``targets`` [nu*K,3].  Two launches (the sums, the median)."""
@@ -214,12 +357,19 @@ class BrushEvaluator:
         return pooled_scores(self.ops, sums, alpha, self.masks, self.fg_mask, self.n_fg)
 
     def evaluate(self, library, style_ids: Optional[Sequence] = None, rounds: int = 1, batch: int = 32, lab_thresh: float = 10,
-                 colors=None, on_pass: Optional[Callable] = None) -> BrushScores:
+                 colors=None, on_pass: Optional[Callable] = None, lpips=None, patch_width: Optional[int] = None, crops=None) -> BrushScores:
         """The scores of every brush of ``library`` (of ``style_ids``, in that order, if given), each the mean over ``rounds`` renders
         of the K drawings with fresh primary colours.  A unit is one brush in one round, K samples; ``floor(batch / K)`` units share a
         generator pass, brush-major; a brush that carries noise buffers gets passes of its own, with its noise set.  ``colors``
         [B, rounds, K, 3] in 0..1 replace the default stream (``default_colors(seed, ...)``, the reference's).  ``on_pass(units,
-        renders, targets)`` (tests) sees every pass's [(brush index, round)], renders and colours before they are reduced."""
+        renders, targets)`` (tests) sees every pass's [(brush index, round)], renders and colours before they are reduced.
+
+        ``lpips`` (a ``perceptual.LPIPS``; the reference uses ``alex``): every pass is additionally scored for
+        LPIPS_UNIFORM_BG_multicolor on the render it already makes, rendered once more with all-NaN user colours -- the brush's own
+        colours (metric_main.py:172-173) -- and scored on that render for LPIPS_UNIFORM_BG and LPIPS_ACROSS_GEO; the scores carry
+        ``perceptual``.  ``patch_width``: the windows' side (``default_patch_width(R)``); ``crops``: the plan of every unit
+        (``default_crops(seed, ...)``).  A callback that takes the keyword ``own_renders`` (or ``**kwargs``) also sees the second
+        render."""
         ops, k = self.ops, self.k
         ids = list(library.get_style_ids() if style_ids is None else style_ids)
         rounds, per = int(rounds), max(1, int(batch) // k)
@@ -233,8 +383,16 @@ class BrushEvaluator:
         colors = default_colors(self.seed, len(ids), rounds, k) if colors is None else np.asarray(colors, np.float32)
         if colors.shape != (len(ids), rounds, k, 3):
             raise ValueError(f"evaluate: colours [{len(ids)},{rounds},{k},3] expected, got {colors.shape}")
+        r_img = self.masks.geom.shape[-1]
+        if lpips is not None:
+            p = default_patch_width(r_img) if patch_width is None else int(patch_width)
+            crops = default_crops(self.seed, len(ids), rounds, k, r_img, p) if crops is None else crops
+            want = {name: (len(ids), rounds, k if name.endswith("perm") else 2) for name in CROP_KEYS}
+            if any(name not in crops or tuple(np.shape(crops[name])) != shape for name, shape in want.items()):
+                raise ValueError(f"evaluate: the crop plan needs {want}")
         if not ids:
-            return BrushScores([], *(np.zeros([0], np.float32) for _ in range(4)))
+            return BrushScores([], *(np.zeros([0], np.float32) for _ in range(4)),
+                               perceptual=None if lpips is None else {key: np.zeros([0], np.float32) for key in PERCEPTUAL_KEYS})
         sf = self.uvs_mapper.calibrate(opts_list, batch) if self.uvs_mapper is not None else None
         ws = [ops.map_style(z=o.style_z, ws=o.style_ws) for o in opts_list]
         noisy = [bool(o.style_ws is not None and o.custom_args and o.custom_args.get("noise_buffers")) for o in opts_list]
@@ -247,7 +405,10 @@ class BrushEvaluator:
                 cur.append((b, r))
         passes.append(cur)
         col_dev = ops.to_device(colors)                                   # [B, rounds, K, 3]
-        scores = []
+        if lpips is not None:                                             # the plan, unit-major: unit (b, r) is row b * rounds + r
+            plan = {name: ops.to_device(np.ascontiguousarray(np.asarray(crops[name], np.int32).reshape(len(ids) * rounds, -1))) for name in CROP_KEYS}
+            also_own = on_pass is not None and _takes_keyword(on_pass, "own_renders")
+        scores, perc = [], []
         for units in passes:
             nu = len(units)
             bi = torch.tensor([b for b, _ in units], dtype=torch.int64)
@@ -258,9 +419,24 @@ class BrushEvaluator:
             sfac = None if sf is None else sf[bi.to(sf.device)].repeat_interleave(k, 0).contiguous()
             noise = self._brush_noise(opts_list[units[0][0]]) if noisy[units[0][0]] else None
             renders = ops.render_rgba(w, self._geometry(nu), user, sfac, noise)
+            if lpips is None:
+                if on_pass is not None:
+                    on_pass(units, renders, targets)
+                scores.append(self.score_renders(renders, targets, lab_thresh))
+                continue
+            rows = torch.tensor([b * rounds + r for b, r in units], dtype=torch.int64, device=plan["multi_off0"].device)
+            pl = {name: t[rows] for name, t in plan.items()}
+            own = ops.render_rgba(w, self._geometry(nu), torch.full_like(user, float("nan")), sfac, noise)       # the brush's own colours
             if on_pass is not None:
-                on_pass(units, renders, targets)
+                on_pass(units, renders, targets, **({"own_renders": own} if also_own else {}))
             scores.append(self.score_renders(renders, targets, lab_thresh))
+            multi, _ = self.perceptual_scores(lpips, renders, p, pl["multi_off0"], pl["multi_off1"])
+            same, geo = self.perceptual_scores(lpips, own, p, pl["same_off0"], pl["same_off1"], pl["same_perm"], pl["geo_perm"])
+            perc.append(torch.stack([geo, same, multi], dim=1))            # (the order of PERCEPTUAL_KEYS)
         s = ops.to_host(torch.cat(scores).view(len(ids), rounds, 4).mean(dim=1).contiguous())
+        perceptual = None
+        if lpips is not None:
+            q = ops.to_host(torch.cat(perc).view(len(ids), rounds, 3).mean(dim=1).contiguous())
+            perceptual = {key: q[:, j].copy() for j, key in enumerate(PERCEPTUAL_KEYS)}
         return BrushScores(ids, lab_e_percent=s[:, 2].copy(), lab_l2=s[:, 3].copy(), bg_clarity_mean=s[:, 0].copy(),
-                           fg_opacity_median=s[:, 1].copy())
+                           fg_opacity_median=s[:, 1].copy(), perceptual=perceptual)

@@ -19,6 +19,9 @@ Channel counts come from the weight arrays, so slim networks of the same layer l
 everything else -- scaling, bias + ReLU + tap + pool, the head, and their backward -- runs on the entries of ``csrc/nb_lpips.hip``
 inside one ``torch.autograd.Function`` that returns ``[N]`` and differentiates the second image only.  ``route="torch"`` is the same
 definition in float32 torch operations; it runs on the CPU and is what the tests compare against.
+
+``LPIPS.pair_distance(x)`` serves the perceptual brush scores (``metrics``): ``x`` holds the first images of n pairs in rows ``:n`` and
+the second in rows ``n:`` (what ``ops.metric_pairs`` writes), the trunk runs once over all 2n, and no gradient is kept.
 """
 from __future__ import annotations
 
@@ -50,6 +53,23 @@ class _Layer:
 def layer_plan(arch: str) -> List[_Layer]:
     a = ARCHS[arch]
     return [_Layer(i, s, p, a["taps"].index(i + 1) if i + 1 in a["taps"] else None, a["pools"].get(i + 2, 0)) for i, (s, p) in sorted(a["convs"].items())]
+
+
+def _sizes_ok(arch: str, side: int) -> bool:
+    """Whether an image of ``side`` pixels passes every convolution and pool of the trunk with at least one output pixel."""
+    kernels = ARCHS[arch]["kernels"]
+    for lay in layer_plan(arch):
+        side = (side + 2 * lay.padding - kernels.get(lay.index, 3)) // lay.stride + 1
+        if side < 1 or (lay.window and side < lay.window):
+            return False
+        if lay.window:
+            side = (side - lay.window) // 2 + 1
+    return True
+
+
+def min_size(arch: str) -> int:
+    """The smallest image side the trunk of ``arch`` accepts, from ``ARCHS`` (alex 31, vgg 16): below it a pool has no window."""
+    return next(s for s in range(1, 1 << 12) if _sizes_ok(arch, s))
 
 
 def unit(f: torch.Tensor) -> torch.Tensor:
@@ -296,6 +316,28 @@ class LPIPS:
         """[N]; differentiable with respect to ``synth`` (the target is a constant)."""
         self._check(target, synth)
         return self._with_taps(self.target_taps(target), synth)
+
+    def pair_distance(self, x: torch.Tensor) -> torch.Tensor:
+        """[n] for ``x`` [2n,3,H,W] in -1..1: LPIPS(x[i], x[n + i]), without a gradient.  ONE trunk pass over all 2n images (the batch
+        that ``ops.metric_pairs`` writes, no concatenation); per level the head runs between ``tap[:n]`` and ``tap[n:]``."""
+        if x.ndim != 4 or x.shape[1] != 3 or x.shape[0] % 2:
+            raise ValueError(f"LPIPS.pair_distance: images [2n,3,H,W] expected, got {tuple(x.shape)}")
+        need = min_size(self.arch)
+        if min(x.shape[2], x.shape[3]) < need:
+            raise ValueError(f"LPIPS.pair_distance ({self.arch}): images of {x.shape[2]} x {x.shape[3]} are below the trunk's minimum side {need}")
+        n = x.shape[0] // 2
+        x = x.detach().to(self.device)
+        with torch.no_grad():
+            if self.route == "hip":
+                acc = torch.zeros([n], dtype=torch.float32, device=self.device)
+                if n:
+                    for tap, w in zip(self._taps_hip(x), self.lins):       # (tap[:n], tap[n:]: dense halves of a dense tensor)
+                        _HipKernels.head(tap[:n], tap[n:], w, acc)
+                return acc
+            out = torch.zeros([n], dtype=torch.float32, device=self.device)
+            for tap, w in zip(self._taps_torch(x), self.lins):
+                out = out + head_torch(tap[:n], tap[n:], w)
+            return out
 
     def bind(self, target: torch.Tensor):
         """A callable ``(target, synth) -> [N]`` for a FIXED target: its scaled image goes through the trunk once, here, and the five tap

@@ -183,6 +183,51 @@ def _metric_shapes(renders: torch.Tensor, target_rgb: torch.Tensor, masks: EvalM
     return n, masks.geom.shape[0], r
 
 
+BG_THRESH_PATCHES = 0.99                   # compute_uniform_bg_lpips_metric (geom_metric.py:238), on the guidance blurred ONCE
+
+
+@dataclasses.dataclass
+class BgGuidance:
+    """What ``bg_guidance`` leaves for ``bg_mean_colors`` and ``metric_pairs``, where the drawings are."""
+    geom: torch.Tensor               # [K,R,R] float32, 0 = stroke
+    blur1: torch.Tensor              # [K,R,R] float32: the 5x5 Gaussian applied once, zero padding
+    n_bg: torch.Tensor               # [K] int32: pixels with blur1 > 0.99
+
+
+def _render_shapes(what: str, renders: torch.Tensor, guidance: Optional[BgGuidance]) -> Tuple[int, int, int]:
+    """(n, K, R) of a ``bg_mean_colors`` / ``metric_pairs`` call (K = 1 without a guidance), or ValueError."""
+    if renders.dtype != torch.float32 or renders.dim() != 4 or renders.shape[1] != 4 or renders.shape[2] != renders.shape[3]:
+        raise ValueError(f"{what}: float32 renders [n,4,R,R] expected, got {renders.dtype} {tuple(renders.shape)}")
+    n, r = renders.shape[0], renders.shape[2]
+    if guidance is None:
+        return n, 1, r
+    g = guidance.blur1
+    if g.dtype != torch.float32 or g.dim() != 3 or g.shape[0] < 1 or tuple(g.shape[1:]) != (r, r) or tuple(guidance.n_bg.shape) != (g.shape[0],):
+        raise ValueError(f"{what}: the guidance of [K,{r},{r}] drawings expected, got blur1 {tuple(g.shape)}, n_bg {tuple(guidance.n_bg.shape)}")
+    return n, g.shape[0], r
+
+
+def _pair_shapes(renders, guidance, mean, off0, off1, src1, p, masked) -> Tuple[int, int, int]:
+    """(n, K, R) of a ``metric_pairs`` call, or ValueError."""
+    n, k, r = _render_shapes("metric_pairs", renders, guidance if masked else None)
+    if not 1 <= int(p) <= r:
+        raise ValueError(f"metric_pairs: patch width {p} outside 1..{r}")
+    for name, off in (("off0", off0), ("off1", off1)):
+        if off.dtype != torch.int32 or tuple(off.shape) != (n, 2):
+            raise ValueError(f"metric_pairs: int32 {name} [{n},2] expected, got {off.dtype} {tuple(off.shape)}")
+    if src1 is not None and (src1.dtype != torch.int32 or tuple(src1.shape) != (n,)):
+        raise ValueError(f"metric_pairs: int32 src1 [{n}] expected, got {src1.dtype} {tuple(src1.shape)}")
+    if masked and (guidance is None or mean is None or mean.dtype != torch.float32 or tuple(mean.shape) != (n, 3)):
+        raise ValueError(f"metric_pairs: masked pairs need the guidance and float32 mean colours [{n},3]")
+    return n, k, r
+
+
+def on_white_f32(renders: torch.Tensor) -> torch.Tensor:
+    """[n,3,R,R]: ``alpha * rgb + (1 - alpha) * 1.0`` (geom_metric.py:197-198, 232-233)."""
+    alpha = renders[:, 3].unsqueeze(1)
+    return alpha * renders[:, :3] + (1 - alpha) * 1.0
+
+
 class TileOpsBase:
     """What ``PaintingHelper`` and ``PaintSession`` call on their ``ops``, as far as it can be said without a device: the scheduling
     hooks, with defaults that do nothing (one stream, no workspaces to prepare, no noise sets, no captured graphs), and the host
@@ -306,6 +351,49 @@ class TileOpsBase:
                             torch.sum(w, dim=(1, 2)), torch.sum(alpha * bg, dim=(1, 2))], dim=1)
         out = (sums, alpha.reshape(n, r * r).contiguous())
         return out + (deltas,) if want_deltas else out
+
+    # -- inputs of the perceptual brush scores: the torch restatements (``TileOps`` runs csrc/nb_metric_patches.hip) --
+    def bg_guidance(self, geom: torch.Tensor) -> BgGuidance:
+        """The guidance of the background metrics for the drawings ``geom`` [K,R,R] float32 (0 = stroke): the Gaussian applied ONCE
+        (geom_metric.py:235) and the number of pixels above 0.99 (geom_metric.py:238-239)."""
+        if geom.dtype != torch.float32 or geom.dim() != 3 or geom.shape[1] != geom.shape[2]:
+            raise ValueError(f"bg_guidance: float32 drawings [K,R,R] expected, got {geom.dtype} {tuple(geom.shape)}")
+        geom = geom.contiguous()
+        blur1 = gaussian_blur_torch(geom.unsqueeze(1)).squeeze(1)
+        return BgGuidance(geom, blur1, (blur1 > BG_THRESH_PATCHES).reshape(geom.shape[0], -1).sum(dim=1).to(torch.int32))
+
+    def bg_mean_colors(self, renders: torch.Tensor, guidance: BgGuidance) -> torch.Tensor:
+        """[n,3] float32: the mean on-white colour of every render [n,4,R,R] over its drawing's background, image i on drawing i % K
+        (geom_metric.py:232-241); zeros where a drawing has no background."""
+        n, k, _ = _render_shapes("bg_mean_colors", renders, guidance)
+        rgb = on_white_f32(renders)
+        bg_mask = (guidance.blur1[torch.arange(n, device=renders.device) % k].unsqueeze(1) > BG_THRESH_PATCHES).to(torch.float32)
+        return torch.sum(rgb * bg_mask, dim=(2, 3)) / torch.clamp(torch.sum(bg_mask, dim=(2, 3)), min=1.0)
+
+    def metric_pairs(self, renders: torch.Tensor, guidance: Optional[BgGuidance], mean: Optional[torch.Tensor], off0: torch.Tensor,
+                     off1: torch.Tensor, src1: Optional[torch.Tensor], p: int, transpose: bool = True, masked: bool = True) -> torch.Tensor:
+        """[2n,3,p,p] float32 in -1..1, the LPIPS input of n pairs: rows :n the ``p`` x ``p`` window of image i at ``off0[i]`` = (row,
+        column), rows n: the window of image ``src1[i]`` (None: i) at ``off1[i]``, transposed with ``transpose``; with ``masked``
+        every pixel that is not background (blurred guidance above 0.99) in BOTH patches takes ``mean[i]`` in both
+        (geom_metric.py:244-259).  Unmasked, with ``p`` = R and zero offsets: the pairs of ``compute_lpips_across_geo``."""
+        n, k, r = _pair_shapes(renders, guidance, mean, off0, off1, src1, p, masked)
+        p = int(p)
+        rgb = on_white_f32(renders)
+        idx = torch.arange(n, device=renders.device)
+        if masked:
+            rgb = torch.cat([rgb, guidance.blur1[idx % k].unsqueeze(1)], dim=1)
+        o0, o1 = off0.clamp(0, r - p).tolist(), off1.clamp(0, r - p).tolist()
+        src = idx.tolist() if src1 is None else src1.clamp(0, n - 1).tolist()
+        patches0 = torch.stack([rgb[i, :, o0[i][0]:o0[i][0] + p, o0[i][1]:o0[i][1] + p] for i in range(n)]) if n else rgb[:, :, :p, :p]
+        patches1 = torch.stack([rgb[j, :, o1[i][0]:o1[i][0] + p, o1[i][1]:o1[i][1] + p] for i, j in enumerate(src)]) if n else rgb[:, :, :p, :p]
+        if transpose:
+            patches1 = patches1.permute(0, 1, 3, 2)
+        if masked:
+            bg_mask = torch.logical_and(patches0[:, 3] > BG_THRESH_PATCHES, patches1[:, 3] > BG_THRESH_PATCHES).to(torch.float32).unsqueeze(1)
+            mc = mean.unsqueeze(-1).unsqueeze(-1)
+            patches0 = bg_mask * patches0[:, :3] + (1 - bg_mask) * mc
+            patches1 = bg_mask * patches1[:, :3] + (1 - bg_mask) * mc
+        return torch.cat([patches0 * 2 - 1.0, patches1 * 2 - 1.0]).contiguous()
 
     def render_rgba(self, ws: torch.Tensor, geom_feats, user_colors=None, sfactor=None, noise_set=None) -> torch.Tensor:
         """[n,4,R,R] float32 in 0..1: the un-positioned "clear" render of the paint engine (brush.py:763-792) with the checkpoint's
@@ -650,6 +738,57 @@ class TileOps(TileOpsBase):
                                                        _p(masks.mask), k, r, n, float(lab_thresh), int(bool(ignore_transparency)), _p(sums),
                                                        _p(alpha), _p(deltas), _p(partials), self._stream()), "brush_metrics")
         return (sums, alpha, deltas) if want_deltas else (sums, alpha)
+
+    # -- inputs of the perceptual brush scores (csrc/nb_metric_patches.hip) --
+    def _dense_renders(self, renders: torch.Tensor, r: int) -> torch.Tensor:
+        """``renders`` as it is where its samples are dense [4,R,R] blocks (a view is read in place), else a dense copy."""
+        count, n = r * r, renders.shape[0]
+        if renders.stride(3) != 1 or renders.stride(2) != r or renders.stride(1) != count or (n > 1 and renders.stride(0) < 4 * count):
+            return renders.contiguous()
+        return renders
+
+    def bg_guidance(self, geom: torch.Tensor) -> BgGuidance:
+        """The once-blurred guidance of the drawings ``geom`` [K,R,R] float32 and its background counts, one launch
+        (``nb_bg_guidance_f32``)."""
+        if geom.dtype != torch.float32 or geom.dim() != 3 or geom.shape[1] != geom.shape[2] or geom.device != self.device:
+            raise ValueError(f"bg_guidance: float32 drawings [K,R,R] on the engine's device expected, got {geom.dtype} {tuple(geom.shape)}")
+        geom = geom.contiguous()
+        k, r = geom.shape[0], geom.shape[1]
+        blur1, n_bg = torch.empty_like(geom), torch.empty([k], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_bg_guidance_f32(_p(geom), k, r, _p(blur1), _p(n_bg), self._stream()), "bg_guidance")
+        return BgGuidance(geom, blur1, n_bg)
+
+    def bg_mean_colors(self, renders: torch.Tensor, guidance: BgGuidance) -> torch.Tensor:
+        """[n,3] on the device (``nb_bg_mean_colors_f32``: one pass over the renders and a fixed-order finish)."""
+        n, k, r = _render_shapes("bg_mean_colors", renders, guidance)
+        if renders.device != self.device or guidance.blur1.device != self.device:
+            raise ValueError("bg_mean_colors: renders and guidance must be on the engine's device")
+        renders = self._dense_renders(renders, r)
+        mean = torch.empty([n, 3], dtype=torch.float32, device=self.device)
+        partials = torch.empty([n, _lib.NB_BG_MEAN_PARTS, 3], dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_bg_mean_colors_f32(_p(renders), max(int(renders.stride(0)), 4 * r * r), _p(guidance.blur1.contiguous()),
+                                                        _p(guidance.n_bg), k, r, n, _p(partials), _p(mean), self._stream()), "bg_mean_colors")
+        return mean
+
+    def metric_pairs(self, renders: torch.Tensor, guidance: Optional[BgGuidance], mean: Optional[torch.Tensor], off0: torch.Tensor,
+                     off1: torch.Tensor, src1: Optional[torch.Tensor], p: int, transpose: bool = True, masked: bool = True) -> torch.Tensor:
+        """[2n,3,p,p] on the device, one launch (``nb_metric_pairs_f32``): both sides of every pair in one buffer."""
+        n, k, r = _pair_shapes(renders, guidance, mean, off0, off1, src1, p, masked)
+        tensors = [renders, off0, off1] + ([src1] if src1 is not None else []) + ([guidance.blur1, mean] if masked else [])
+        if any(t.device != self.device for t in tensors):
+            raise ValueError("metric_pairs: renders, guidance, colours and the plan must be on the engine's device")
+        renders = self._dense_renders(renders, r)
+        out = torch.empty([2 * n, 3, int(p), int(p)], dtype=torch.float32, device=self.device)
+        flags = (_lib.NB_METRIC_PAIRS_TRANSPOSE if transpose else 0) | (_lib.NB_METRIC_PAIRS_MASKED if masked else 0)
+        blur1 = guidance.blur1.contiguous() if masked else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_metric_pairs_f32(_p(renders), max(int(renders.stride(0)), 4 * r * r), _p(blur1),
+                                                      _p(mean.contiguous()) if masked else None, _p(off0.contiguous()), _p(off1.contiguous()),
+                                                      None if src1 is None else _p(src1.contiguous()), k, r, int(p), n, flags, _p(out),
+                                                      self._stream()), "metric_pairs")
+        return out
 
     def render_rgba(self, ws: torch.Tensor, geom_feats, user_colors=None, sfactor=None, noise_set=None) -> torch.Tensor:
         """[n,4,R,R] float32 in 0..1: ONE un-positioned "clear" generator pass, composited in the ToRGB launch."""

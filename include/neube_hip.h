@@ -691,6 +691,53 @@ int nb_brush_metrics_f32(const float* renders, long long stride_n, const float* 
                          int k, int r, int n, float lab_thresh, int ignore_transparency, float* sums, float* alpha, float* deltas,
                          float* partials, void* stream);
 
+/* ---- inputs of the perceptual brush scores (csrc/nb_metric_patches.hip): what compute_uniform_bg_lpips_metric
+ * (forger/metrics/geom_metric.py:207-262) and compute_lpips_across_geo (geom_metric.py:190-204) do to a batch of renders before the
+ * LPIPS network sees it.  Renders are read in place as nb_brush_metrics_f32 reads them: four dense planes r, g, b, alpha of r * r
+ * floats at renders + i * stride_n (stride_n >= 4 r r), in 0..1; image i lies on drawing i % k.  fp32 throughout, no float atomics:
+ * the same input gives the same bits.  The entries only enqueue on `stream`: no allocation, no host wait.  Values outside 0..1,
+ * infinities and NaN do not fault; what they give is unspecified.
+ *
+ * The guidance of the background metrics, once per set of drawings.  geom [k,r,r] fp32, 0 = stroke.  blur1 [k,r,r] =
+ * default_gaussian_smoothing applied ONCE (geom_metric.py:126-129, 235): the 5x5 Gaussian, sigma 1, normalised to sum 1, zero padding
+ * 2, with the weights of nb_eval_masks_f32; within 2e-6 of float64 on values in 0..1.  n_bg[k] = the pixels with blur1 > 0.99f
+ * (BG_THRESH of geom_metric.py:238-239; NOT the 0.999 on the twice-blurred guidance of nb_eval_masks_f32), cleared and counted on
+ * `stream` in integer arithmetic.  k == 0: NB_OK without a launch.  NB_EINVAL: a null pointer, k outside 0..65535, r outside
+ * 1..8192, a pointer not 4-byte aligned. */
+int nb_bg_guidance_f32(const float* geom, int k, int r, float* blur1, int32_t* n_bg, void* stream);
+
+/* Workgroups that share one image in nb_bg_mean_colors_f32: `partials` holds n * NB_BG_MEAN_PARTS * 3 floats. */
+#define NB_BG_MEAN_PARTS 16
+
+/* The mean background colour of n renders (geom_metric.py:232-241): mean[3 i + c] = sum over the pixels with blur1 > 0.99f of
+ * (alpha * rgb_c + (1 - alpha)), divided by max(n_bg[i % k], 1) -- an image without background gets zeros.  blur1 [k,r,r] and n_bg [k]
+ * are nb_bg_guidance_f32's.  NB_BG_MEAN_PARTS workgroups share an image and leave partial sums in `partials`; a second small launch
+ * of the same call adds them in a fixed order and divides.  16-byte vectors when r * r and stride_n are multiples of four and renders
+ * and blur1 are 16-byte aligned, otherwise pixel by pixel.  n == 0: NB_OK without a launch.  NB_EINVAL: a null pointer, k < 1, r
+ * outside 1..8192, n outside 0..2^24, stride_n < 4 r r, a pointer not 4-byte aligned. */
+int nb_bg_mean_colors_f32(const float* renders, long long stride_n, const float* blur1, const int32_t* n_bg, int k, int r, int n,
+                          float* partials, float* mean, void* stream);
+
+#define NB_METRIC_PAIRS_TRANSPOSE 1   /* the second patch with rows and columns exchanged (permute(0,1,3,2), geom_metric.py:250) */
+#define NB_METRIC_PAIRS_MASKED 2      /* fill what is not background in BOTH patches with the first image's mean colour (:255-257) */
+
+/* The LPIPS input of n pairs of patches, both sides in ONE buffer: out [2n,3,p,p], out[i] the first and out[n + i] the second patch
+ * of pair i, so that the trunk runs once over 2n images.  The first patch is the p x p window of image i at (row, column) =
+ * off0[2 i], off0[2 i + 1]; the second the window of image j = src1[i] (src1 NULL: j = i) at off1[2 i], off1[2 i + 1], transposed
+ * with NB_METRIC_PAIRS_TRANSPOSE.  Every pixel is composited over white, alpha * rgb + (1 - alpha).  With NB_METRIC_PAIRS_MASKED a
+ * pixel is background where blur1 of BOTH patches exceeds 0.99f (image j on drawing j % k, its patch transposed first); background
+ * pixels keep their colour, every other pixel of both patches takes mean[3 i .. 3 i + 2] -- the FIRST image's, also for a permuted
+ * second patch (geom_metric.py:256-257).  Both patches are then scaled by * 2 - 1 (:258-259).  Without MASKED (blur1 and mean may be
+ * NULL) and without TRANSPOSE, with p = r and zero offsets: the pairs of compute_lpips_across_geo for the permutation src1.
+ * An offset is clamped into 0..r - p and src1[i] into 0..n - 1 on the device (they cannot be checked on the host).  One launch; the
+ * transposed patch is staged through a padded LDS tile, so both patches are read along image rows.  16-byte stores (and loads, for
+ * windows whose column offset is a multiple of four) when p, r and stride_n are multiples of four and renders, blur1 and out are
+ * 16-byte aligned; otherwise element by element, any alignment of the output planes (p odd).  n == 0: NB_OK without a launch.
+ * NB_EINVAL: a null pointer (src1 excepted; blur1 and mean without MASKED), unknown flags, k < 1, r outside 1..8192, p outside 1..r,
+ * n outside 0..2^24, n * ceil(p / 32)^2 above 2^31 - 1, stride_n < 4 r r, a pointer not 4-byte aligned. */
+int nb_metric_pairs_f32(const float* renders, long long stride_n, const float* blur1, const float* mean, const int32_t* off0,
+                        const int32_t* off1, const int32_t* src1, int k, int r, int p, int n, int flags, float* out, void* stream);
+
 /* ---- clarity optimisation of brushes (csrc/nb_clarity.hip): what one step of run_one_clarity_opt (scripts/opt_clarity_main.py:93-167)
  * does around the generator, for k brushes at once.  The state of k brushes is an arena [k, p] of floats (row stride given per call):
  * a row is W+ (nw floats) followed by noise planes.  NbClarityPlanes lists the planes in the order of their offsets: side (a power of
