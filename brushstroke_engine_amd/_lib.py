@@ -172,6 +172,9 @@ PROTOTYPES = {
     "nb_bg_guidance_f32": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
     "nb_bg_mean_colors_f32": (C.c_int, [vp, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "nb_metric_pairs_f32": (C.c_int, [vp, C.c_longlong, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    # inputs of the stitching scores (csrc/nb_stitch_metrics.hip): windows of full-size drawings, the composited and cropped pairs with their L1 sums
+    "nb_stitch_crops_u8": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
+    "nb_stitch_pairs_f32": (C.c_int, [vp, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     # clarity optimisation (csrc/nb_clarity.hip): the fused loss and its gradient, the noise regulariser, the Adam + renormalise step
     "nb_clarity_scratch_floats": (C.c_longlong, [vp, C.c_int, C.c_longlong, C.c_int]),
     "nb_clarity_loss_f32": (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_float,
@@ -293,6 +296,7 @@ NB_SEG_PITCH = 8
 NB_BRUSH_METRICS_PARTS = 16
 NB_BG_MEAN_PARTS = 16
 NB_METRIC_PAIRS_TRANSPOSE, NB_METRIC_PAIRS_MASKED = 1, 2
+NB_STITCH_PARTS = 32
 NB_CLARITY_MAX_PLANES, NB_CLARITY_LOSS_PARTS, NB_CLARITY_CHUNK = 32, 8, 1024
 NB_PROJECTION_PARTS = 8
 NB_LPIPS_SPLIT_MAX_HW, NB_LPIPS_SPLIT_MIN_C = 1024, 64

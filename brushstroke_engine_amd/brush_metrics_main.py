@@ -1,13 +1,16 @@
 """Scores of a brush library -- LAB_E%, LAB_L2, BG_CLARITY_MEAN and FG_OPACITY_MEDIAN per brush, the numbers the reference's
 ``paint_engine_metric_loop`` reports (forger/metrics/metric_main.py:105-236) -- computed in batches on the device
 (``metrics.BrushEvaluator``).  With ``--lpips_weights`` the three perceptual numbers LPIPS_ACROSS_GEO, LPIPS_UNIFORM_BG and
-LPIPS_UNIFORM_BG_multicolor join them, and the files carry seven columns.
+LPIPS_UNIFORM_BG_multicolor join them, and the files carry seven columns; with ``--stitch_drawings`` too, STITCH_L1 and STITCH_LPIPS
+(two positioned renders of overlapping crops of full-size drawings, each composited into the other) make it the reference's nine.
 
     python -m brushstroke_engine_amd.brush_metrics_main --gan_checkpoint engine.npz --library rand100 --drawings drawings.npz \\
         --output_dir out [--uvs_calibration cal.npz] [--rounds 1] [--batch 32] [--seed 0] [--lab_thresh 10] [--prefix ''] [--conv_mode h3] \\
-        [--lpips_weights alex.npz] [--lpips_net alex] [--patch_width P]
+        [--lpips_weights alex.npz] [--lpips_net alex] [--patch_width P] \\
+        [--stitch_drawings full.npz] [--stitch_margin 10] [--stitch_min_overlap 50]
 
 ``--drawings`` is an .npz whose first array (or the one named ``drawings``) holds [K,R,R] uint8 guidance drawings, 0 = stroke.
+``--stitch_drawings`` is such an .npz with [Ks,D,D] full-size drawings, D above R; it needs ``--lpips_weights``.
 ``--library`` is what ``paint_image_main`` takes.  Three files are written to ``--output_dir``: ``<prefix>style_metrics.txt`` and
 ``<prefix>summary_metrics.txt`` in the reference's line format, and ``<prefix>brush_metrics.json``.  Single process.
 """
@@ -46,6 +49,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lpips_net", default=None, choices=["alex", "vgg"], help="the network of --lpips_weights (default: the file's 'arch' entry)")
     ap.add_argument("--patch_width", type=int, default=None,
                     help="side of the windows of the LPIPS_UNIFORM_BG scores (default: R / 4, R / 2 or 0.8 R, the first of at least 64)")
+    ap.add_argument("--stitch_drawings", default=None,
+                    help=".npz with [Ks,D,D] uint8 full-size drawings (0 = stroke), D above the patch width: also report STITCH_L1 and "
+                         "STITCH_LPIPS (needs --lpips_weights)")
+    ap.add_argument("--stitch_margin", type=int, default=10, help="the stitcher's crop margin (RandomStitcher.crop_margin)")
+    ap.add_argument("--stitch_min_overlap", type=int, default=50, help="the stitcher's minimum overlap of the two crops")
     return ap
 
 
@@ -64,7 +72,10 @@ def write_scores(scores: metrics.BrushScores, out_dir: str, prefix: str = ""):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.stitch_drawings and not args.lpips_weights:
+        ap.error("--stitch_drawings needs --lpips_weights")
     _, _, device, _ = launch.init()                  # kernel library first, then the device
     cfg, gen_sd, enc_sd, preproc, _ = formats.load_engine_snapshot(args.gan_checkpoint)
     G = Generator(cfg, gen_sd, conv_mode=args.conv_mode or DEFAULT_CONV_MODE).to(device)
@@ -82,6 +93,8 @@ def main(argv=None):
         if args.lpips_weights:
             from .perceptual import LPIPS
             kw = dict(lpips=LPIPS(args.lpips_weights, net=args.lpips_net, device=device), patch_width=args.patch_width)
+        if args.stitch_drawings:
+            kw["stitch"] = metrics.StitchSetup(load_drawings(args.stitch_drawings), args.stitch_margin, args.stitch_min_overlap)
         scores = evaluator.evaluate(library, rounds=args.rounds, batch=args.batch, lab_thresh=args.lab_thresh, **kw)
     paths = write_scores(scores, args.output_dir, args.prefix)
     logger.info(f"Scored {len(scores.ids)} brushes: {paths}")

@@ -23,8 +23,19 @@ With an LPIPS network (``perceptual.LPIPS``; the reference uses ``alex``) three 
 ``ops.bg_mean_colors`` and ``ops.metric_pairs`` (csrc/nb_metric_patches.hip) write the network's input of both sides of all pairs of
 a pass into one buffer, and ``LPIPS.pair_distance`` runs the trunk once over it.  The random windows and permutations come from a
 seeded plan (``default_crops``): the reference draws them from the process-global stream, so no seed reproduces ITS draws; the
-distribution is the same.  ``STITCH_LPIPS`` / ``STITCH_L1`` (metric_main.py:181-200: two positioned renders of overlapping crops of
-full-size drawings, which the reference itself skips for W+ brushes) and ``BG_LPIPS*`` are not part of this module.
+distribution is the same.
+
+With full-size drawings (``StitchSetup``) the last two columns of the reference's files join them:
+
+    STITCH_LPIPS, STITCH_L1              how well the brush survives being painted tile by tile: two positioned raw renders of
+                                         overlapping crops of a full-size drawing, each with the other's pixels composited into
+                                         the overlap, against themselves (metric_main.py:181-200, ``RandomStitcher.generate_with_stitching``,
+                                         ``compute_stitching_metrics``, geom_metric.py:165-187)
+
+``ops.stitch_crops`` gathers the crops of a pass, ``ops.render_img`` renders both sides in one generator pass, and
+``ops.stitch_pairs`` (csrc/nb_stitch_metrics.hip) writes the four cropped images of every sample into one LPIPS input and sums the
+absolute differences in the same launch; the crops and noise positions come from ``default_stitch_plan``.  ``BG_LPIPS*`` is not
+part of this module.
 """
 from __future__ import annotations
 
@@ -37,12 +48,13 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .tile_ops import EvalMasks, TileOpsBase, lab_deltas_torch
+from .tile_ops import EvalMasks, TileOpsBase, lab_deltas_torch, stitch_rects
 
 KEYS = ("BG_CLARITY_MEAN", "FG_OPACITY_MEDIAN", "LAB_E%", "LAB_L2")          # sorted, the column order of the reference's files
 PERCEPTUAL_KEYS = ("LPIPS_ACROSS_GEO", "LPIPS_UNIFORM_BG", "LPIPS_UNIFORM_BG_multicolor")          # sorted likewise; they sort behind KEYS
+STITCH_KEYS = ("STITCH_L1", "STITCH_LPIPS")                                  # sorted likewise; they sort behind PERCEPTUAL_KEYS
 _HIGHER_IS_BETTER = {"BG_CLARITY_MEAN": True, "FG_OPACITY_MEDIAN": True, "LAB_E%": False, "LAB_L2": False, "LPIPS_ACROSS_GEO": False,
-                     "LPIPS_UNIFORM_BG": False, "LPIPS_UNIFORM_BG_multicolor": False}
+                     "LPIPS_UNIFORM_BG": False, "LPIPS_UNIFORM_BG_multicolor": False, "STITCH_L1": False, "STITCH_LPIPS": False}
 
 
 def _fg_pool(masks: EvalMasks):
@@ -155,6 +167,24 @@ def compute_lpips_across_geo(renders, lpips, perm=None, ops=None):
     return {"LPIPS_ACROSS_GEO": lpips.pair_distance(x).mean().item()}
 
 
+def compute_stitching_metrics(stitching_result, margin, lpips, ops=None):
+    """{'STITCH_LPIPS', 'STITCH_L1'} of a ``RandomStitcher.generate_with_stitching`` dict (geom_metric.py:165-187): each 0.5 * (fake1
+    against fake1_composite + fake2 against fake2_composite), all four images [N,3,R,R] cropped to ``[margin:R - 2 margin]`` on both
+    axes first -- the reference's asymmetric crop, S = R - 3 margin wide --; LPIPS is the mean over the batch of the raw, unscaled
+    images, L1 the mean over the N * 3 * S * S entries.  ``lpips``: a ``perceptual.LPIPS``.  The dict's images are composited already,
+    so only the crop and the differences remain: torch where the tensors are, whatever ``ops`` (accepted like in the other
+    functions); a library goes through ``BrushEvaluator.evaluate(stitch=)``, which composites, crops and sums in one launch."""
+    m = int(margin)
+    imgs = [stitching_result[key] for key in ("fake1", "fake2", "fake1_composite", "fake2_composite")]
+    n, r = imgs[0].shape[0], imgs[0].shape[-1]
+    if m < 0 or r - 3 * m < 1 or any(t.shape != imgs[0].shape for t in imgs):
+        raise ValueError(f"compute_stitching_metrics: margin {margin} and images {[tuple(t.shape) for t in imgs]} do not fit")
+    x = torch.cat([t[:, :, m:r - 2 * m, m:r - 2 * m].to(torch.float32) for t in imgs]).contiguous()
+    d = lpips.pair_distance(x)
+    l1 = (x[:2 * n] - x[2 * n:]).abs()
+    return {"STITCH_LPIPS": (0.5 * (d[:n].mean() + d[n:].mean())).item(), "STITCH_L1": (0.5 * (l1[:n].mean() + l1[n:].mean())).item()}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # a whole library
 # ---------------------------------------------------------------------------------------------------------------------
@@ -175,23 +205,28 @@ def value_cells(values: Dict[str, float], keys: Sequence[str] = KEYS) -> List[st
 @dataclasses.dataclass
 class BrushScores:
     """The scores of a library's brushes (``BrushEvaluator.evaluate``), on the host: four float32 arrays [B] in the order of ``ids``,
-    and, from a run with an LPIPS network, ``perceptual``: {key of ``PERCEPTUAL_KEYS``: float32 [B]}."""
+    and, from a run with an LPIPS network, ``perceptual``: {key of ``PERCEPTUAL_KEYS``: float32 [B]}; from one with full-size
+    drawings too, ``stitching``: {key of ``STITCH_KEYS``: float32 [B]}."""
     ids: List
     lab_e_percent: np.ndarray          # LAB_E%: share (in %) of the stroke's weight whose Lab distance to the picked colour exceeds lab_thresh
     lab_l2: np.ndarray                 # LAB_L2: mean over ALL pixels of weight * Lab distance
     bg_clarity_mean: np.ndarray        # BG_CLARITY_MEAN: 1 - mean alpha on sure background; NaN without background
     fg_opacity_median: np.ndarray      # FG_OPACITY_MEDIAN: lower median of alpha on the strokes; NaN without foreground
     perceptual: Optional[Dict[str, np.ndarray]] = None          # the three LPIPS numbers (lower = more uniform); None: not computed
+    stitching: Optional[Dict[str, np.ndarray]] = None           # STITCH_L1, STITCH_LPIPS (lower = the seam shows less); None: not computed
 
     def keys(self) -> tuple:
-        """The columns, sorted as the reference's files: ``KEYS``, and ``PERCEPTUAL_KEYS`` behind them when they were computed."""
-        return KEYS if self.perceptual is None else KEYS + PERCEPTUAL_KEYS
+        """The columns, sorted as the reference's files: ``KEYS``, and ``PERCEPTUAL_KEYS`` and ``STITCH_KEYS`` behind them when they
+        were computed."""
+        return KEYS + (() if self.perceptual is None else PERCEPTUAL_KEYS) + (() if self.stitching is None else STITCH_KEYS)
 
     def as_dict(self) -> Dict[str, np.ndarray]:
         d = {"BG_CLARITY_MEAN": self.bg_clarity_mean, "FG_OPACITY_MEDIAN": self.fg_opacity_median, "LAB_E%": self.lab_e_percent,
              "LAB_L2": self.lab_l2}
         if self.perceptual is not None:
             d.update({k: self.perceptual[k] for k in PERCEPTUAL_KEYS})
+        if self.stitching is not None:
+            d.update({k: self.stitching[k] for k in STITCH_KEYS})
         return d
 
     def summary(self) -> Dict[str, float]:
@@ -264,6 +299,52 @@ def default_crops(seed: int, n_brushes: int, rounds: int, k: int, r: int, p: int
 
 
 CROP_KEYS = ("multi_off0", "multi_off1", "same_off0", "same_off1", "same_perm", "geo_perm")
+
+
+@dataclasses.dataclass
+class StitchSetup:
+    """What ``BrushEvaluator.evaluate(stitch=)`` scores STITCH_* on: full-size drawings and the stitcher's two numbers
+    (``RandomStitcher(crop_margin, min_overlap)``, stitching.py:194-200)."""
+    drawings: np.ndarray             # [Ks,D,D] uint8, 0 = stroke, D above the engine's patch width
+    margin: int = 10                 # crop_margin: how far a crop is inset before it is composited into the other; also the metric's crop
+    min_overlap: int = 50
+
+
+STITCH_PLAN_KEYS = ("crop1", "crop2", "positions1")
+
+
+def default_stitch_plan(seed: int, n_brushes: int, rounds: int, k: int, r: int, d: int, margin: int = 10, min_overlap: int = 50) -> Dict[str, np.ndarray]:
+    """The random plan of the stitching scores for every (brush, round), from a CPU ``torch.Generator`` seeded ``seed + 3`` (a stream
+    of its own: ``default_colors`` and ``default_crops`` keep theirs).  Per unit, brush-major, in THIS order of draws:
+
+        crop1        [B, rounds, 2] int32      (row, column) of the first r x r crop of the d x d drawings: ``randint(0, d - r + 1, (2,))``,
+                                               the range of ``RandomCrop.get_params`` (metric_main.py:185)
+        crop2        [B, rounds, 2] int32      of the second: per axis (row, then column) one ``randint`` over the INCLUSIVE range of
+                                               ``CropHelper.gen_overlapping_square_crop`` (stitching.py:182-191): max(0, crop1 - radius) ..
+                                               min(crop1 + radius, d - r - 1) with radius = r - margin - min_overlap - 1
+        positions1   [B, rounds, K, 2] int32   the noise positions of the first render: ``randint(0, r - 1, (k, 2))`` (stitching.py:210)
+
+    One crop pair serves the K samples of a unit: the reference's loop draws one per batch (metric_main.py:185-186).  Where the range of
+    crop2 is empty (crop1 at d - r with radius 0; the reference's ``random.randint`` raises there) crop2 = crop1.  Stated departure,
+    as for ``default_crops``: the reference draws from the process-global streams, so no seed reproduces its draws.  ValueError unless
+    ``d > r`` and ``r - margin - min_overlap - 1 >= 0``."""
+    r, d, margin, min_overlap = int(r), int(d), int(margin), int(min_overlap)
+    radius = r - margin - min_overlap - 1
+    if d <= r or radius < 0 or margin < 0 or min_overlap < 0:
+        raise ValueError(f"default_stitch_plan: drawings of side {d} must exceed the patch width {r}, and r - margin - min_overlap - 1 = "
+                         f"{radius} (margin {margin}, min_overlap {min_overlap}) must not be negative")
+    gen = torch.Generator().manual_seed(int(seed) + 3)
+    out = {"crop1": np.zeros([n_brushes, rounds, 2], np.int32), "crop2": np.zeros([n_brushes, rounds, 2], np.int32),
+           "positions1": np.zeros([n_brushes, rounds, k, 2], np.int32)}
+    for b in range(n_brushes):
+        for j in range(rounds):
+            c1 = torch.randint(0, d - r + 1, (2,), generator=gen).tolist()
+            out["crop1"][b, j] = c1
+            for axis in range(2):
+                lo, hi = max(0, c1[axis] - radius), min(c1[axis] + radius, d - r - 1)
+                out["crop2"][b, j, axis] = int(torch.randint(lo, hi + 1, (1,), generator=gen)) if hi >= lo else c1[axis]
+            out["positions1"][b, j] = torch.randint(0, r - 1, (k, 2), generator=gen).numpy()
+    return out
 
 
 def _takes_keyword(fn, name: str) -> bool:
@@ -357,7 +438,8 @@ class BrushEvaluator:
         return pooled_scores(self.ops, sums, alpha, self.masks, self.fg_mask, self.n_fg)
 
     def evaluate(self, library, style_ids: Optional[Sequence] = None, rounds: int = 1, batch: int = 32, lab_thresh: float = 10,
-                 colors=None, on_pass: Optional[Callable] = None, lpips=None, patch_width: Optional[int] = None, crops=None) -> BrushScores:
+                 colors=None, on_pass: Optional[Callable] = None, lpips=None, patch_width: Optional[int] = None, crops=None,
+                 stitch: Optional[StitchSetup] = None, stitch_plan=None) -> BrushScores:
         """The scores of every brush of ``library`` (of ``style_ids``, in that order, if given), each the mean over ``rounds`` renders
         of the K drawings with fresh primary colours.  A unit is one brush in one round, K samples; ``floor(batch / K)`` units share a
         generator pass, brush-major; a brush that carries noise buffers gets passes of its own, with its noise set.  ``colors``
@@ -369,7 +451,18 @@ class BrushEvaluator:
         colours (metric_main.py:172-173) -- and scored on that render for LPIPS_UNIFORM_BG and LPIPS_ACROSS_GEO; the scores carry
         ``perceptual``.  ``patch_width``: the windows' side (``default_patch_width(R)``); ``crops``: the plan of every unit
         (``default_crops(seed, ...)``).  A callback that takes the keyword ``own_renders`` (or ``**kwargs``) also sees the second
-        render."""
+        render.
+
+        ``stitch`` (a ``StitchSetup``; needs ``lpips``): STITCH_L1 and STITCH_LPIPS join them, the scores carry ``stitching``.  A unit
+        is then also scored on the Ks full-size drawings: both crops of the unit's plan (``stitch_plan``, default
+        ``default_stitch_plan(seed, ...)``) of every drawing are gathered (``ops.stitch_crops``) and encoded, rendered as raw images in
+        ONE generator pass with noise positions ``positions2 = positions1 + (crop2 - crop1)`` (``ops.render_img``), composited, cropped
+        and summed in one launch (``ops.stitch_pairs``), and the network runs once over the pass's 4 nu Ks images.  These passes are
+        their own: ``floor(batch / (2 Ks))`` units share one, a brush with noise buffers again alone.  Stated departure: W+ brushes
+        are scored like any other, where the reference skips them (metric_main.py:196-197, a TODO there).  A callback that takes the
+        keyword ``stitch`` is also called once per such pass, as ``on_pass(units, None, None, stitch=info)`` with info = {"units",
+        "crop1" [nu,2], "crop2" [nu,2], "positions1" [nu Ks,2], "positions2" [nu Ks,2], "fake" [2 nu Ks,3,R,R]} (the plan as host
+        arrays, ``fake`` where it was rendered); its ordinary calls are as without ``stitch``.  Without ``stitch`` nothing changes."""
         ops, k = self.ops, self.k
         ids = list(library.get_style_ids() if style_ids is None else style_ids)
         rounds, per = int(rounds), max(1, int(batch) // k)
@@ -390,20 +483,43 @@ class BrushEvaluator:
             want = {name: (len(ids), rounds, k if name.endswith("perm") else 2) for name in CROP_KEYS}
             if any(name not in crops or tuple(np.shape(crops[name])) != shape for name, shape in want.items()):
                 raise ValueError(f"evaluate: the crop plan needs {want}")
+        if stitch is not None:
+            if lpips is None:
+                raise ValueError("evaluate: the stitching scores need an LPIPS network (lpips=)")
+            sdraw = np.asarray(stitch.drawings)
+            if sdraw.dtype != np.uint8 or sdraw.ndim != 3 or sdraw.shape[0] < 1 or sdraw.shape[1] != sdraw.shape[2] or sdraw.shape[1] <= r_img:
+                raise ValueError(f"evaluate: uint8 stitch drawings [Ks,D,D] with D above the patch width {r_img} expected, got {sdraw.dtype} {sdraw.shape}")
+            ks, d_full, margin = sdraw.shape[0], sdraw.shape[1], int(stitch.margin)
+            if margin < 0 or r_img - 3 * margin < 1:
+                raise ValueError(f"evaluate: stitch margin {margin} leaves no crop window of {r_img} - 3 * margin pixels")
+            if stitch_plan is None:
+                stitch_plan = default_stitch_plan(self.seed, len(ids), rounds, ks, r_img, d_full, margin, stitch.min_overlap)
+            want = {"crop1": (len(ids), rounds, 2), "crop2": (len(ids), rounds, 2), "positions1": (len(ids), rounds, ks, 2)}
+            if any(name not in stitch_plan or tuple(np.shape(stitch_plan[name])) != shape for name, shape in want.items()):
+                raise ValueError(f"evaluate: the stitch plan needs {want}")
+            splan = {name: np.asarray(stitch_plan[name]).astype(np.int64) for name in STITCH_PLAN_KEYS}
+            if any(splan[name].size and (splan[name].min() < 0 or splan[name].max() > d_full - r_img) for name in ("crop1", "crop2")):
+                raise ValueError(f"evaluate: the stitch plan's crops must lie in 0..{d_full - r_img}")
         if not ids:
             return BrushScores([], *(np.zeros([0], np.float32) for _ in range(4)),
-                               perceptual=None if lpips is None else {key: np.zeros([0], np.float32) for key in PERCEPTUAL_KEYS})
+                               perceptual=None if lpips is None else {key: np.zeros([0], np.float32) for key in PERCEPTUAL_KEYS},
+                               stitching=None if stitch is None else {key: np.zeros([0], np.float32) for key in STITCH_KEYS})
         sf = self.uvs_mapper.calibrate(opts_list, batch) if self.uvs_mapper is not None else None
         ws = [ops.map_style(z=o.style_z, ws=o.style_ws) for o in opts_list]
         noisy = [bool(o.style_ws is not None and o.custom_args and o.custom_args.get("noise_buffers")) for o in opts_list]
-        passes, cur = [], []                                              # lists of (brush, round); a brush with noise never shares
-        for b in range(len(ids)):
-            for r in range(rounds):
-                if cur and (len(cur) == per or noisy[b] != noisy[cur[-1][0]] or (noisy[b] and cur[-1][0] != b)):
-                    passes.append(cur)
-                    cur = []
-                cur.append((b, r))
-        passes.append(cur)
+
+        def split(per):
+            """Lists of (brush, round), at most ``per`` each; a brush with noise never shares."""
+            passes, cur = [], []
+            for b in range(len(ids)):
+                for r in range(rounds):
+                    if cur and (len(cur) == per or noisy[b] != noisy[cur[-1][0]] or (noisy[b] and cur[-1][0] != b)):
+                        passes.append(cur)
+                        cur = []
+                    cur.append((b, r))
+            passes.append(cur)
+            return passes
+        passes = split(per)
         col_dev = ops.to_device(colors)                                   # [B, rounds, K, 3]
         if lpips is not None:                                             # the plan, unit-major: unit (b, r) is row b * rounds + r
             plan = {name: ops.to_device(np.ascontiguousarray(np.asarray(crops[name], np.int32).reshape(len(ids) * rounds, -1))) for name in CROP_KEYS}
@@ -438,5 +554,42 @@ class BrushEvaluator:
         if lpips is not None:
             q = ops.to_host(torch.cat(perc).view(len(ids), rounds, 3).mean(dim=1).contiguous())
             perceptual = {key: q[:, j].copy() for j, key in enumerate(PERCEPTUAL_KEYS)}
+        stitching = None
+        if stitch is not None:
+            q = ops.to_host(self._stitch_scores(lpips, sdraw, margin, splan, ws, opts_list, noisy, split(max(1, int(batch) // (2 * ks))), rounds,
+                                                on_pass if (on_pass is not None and _takes_keyword(on_pass, "stitch")) else None))
+            stitching = {key: q[:, j].copy() for j, key in enumerate(STITCH_KEYS)}
         return BrushScores(ids, lab_e_percent=s[:, 2].copy(), lab_l2=s[:, 3].copy(), bg_clarity_mean=s[:, 0].copy(),
-                           fg_opacity_median=s[:, 1].copy(), perceptual=perceptual)
+                           fg_opacity_median=s[:, 1].copy(), perceptual=perceptual, stitching=stitching)
+
+    def _stitch_scores(self, lpips, sdraw: np.ndarray, margin: int, plan, ws, opts_list, noisy, passes, rounds: int, hook) -> torch.Tensor:
+        """[B, 2] in the order of ``STITCH_KEYS``, on the device: the mean over the rounds of every brush's units, the passes as
+        ``evaluate`` describes them.  ``plan``: int64 host arrays of ``STITCH_PLAN_KEYS``; ``ws``: every brush's styles."""
+        ops, ks, r = self.ops, sdraw.shape[0], self.masks.geom.shape[-1]
+        s = r - 3 * margin
+        drawings = ops.to_device(np.ascontiguousarray(sdraw))
+        out = []
+        for units in passes:
+            nu = len(units)
+            n = nu * ks
+            c1 = np.stack([plan["crop1"][b, j] for b, j in units])                                   # [nu, 2]
+            c2 = np.stack([plan["crop2"][b, j] for b, j in units])
+            p1 = np.concatenate([plan["positions1"][b, j] for b, j in units])                        # [n, 2], sample u * Ks + d
+            p2 = p1 + np.repeat(c2 - c1, ks, axis=0)                                                 # CropHelper.position_delta
+            rects = [stitch_rects((*c1[u], r, r), (*c2[u], r, r), margin) for u in range(nu)]
+            rects_a = ops.to_device(np.ascontiguousarray(np.repeat(np.stack([a for a, _ in rects]), ks, axis=0)))
+            rects_b = ops.to_device(np.ascontiguousarray(np.repeat(np.stack([b for _, b in rects]), ks, axis=0)))
+            draw = ops.to_device(np.tile(np.arange(ks, dtype=np.int32), 2 * nu))
+            offsets = ops.to_device(np.concatenate([np.repeat(c1, ks, axis=0), np.repeat(c2, ks, axis=0)]).astype(np.int32))
+            feats = ops.encode(ops.stitch_crops(drawings, draw, offsets, r))                         # rows :n the first crops, n: the second
+            w = torch.cat([ws[b] for b, _ in units]).repeat_interleave(ks, 0).repeat(2, 1, 1).contiguous()
+            noise = self._brush_noise(opts_list[units[0][0]]) if noisy[units[0][0]] else None
+            fake = ops.render_img(w, feats, ops.to_device(np.concatenate([p1, p2]).astype(np.int64)), noise)
+            if hook is not None:
+                hook(units, None, None, stitch={"units": list(units), "crop1": c1, "crop2": c2, "positions1": p1, "positions2": p2, "fake": fake})
+            x, l1 = ops.stitch_pairs(fake, rects_a, rects_b, margin)
+            dist = lpips.pair_distance(x)                                                            # [2n]: the first pairs, then the second
+            lp = 0.5 * (dist[:n].view(nu, ks).mean(dim=1) + dist[n:].view(nu, ks).mean(dim=1))
+            ab = 0.5 * (l1[:n].view(nu, ks).sum(dim=1) + l1[n:].view(nu, ks).sum(dim=1)) / float(ks * 3 * s * s)
+            out.append(torch.stack([ab, lp], dim=1))
+        return torch.cat(out).view(len(opts_list), rounds, 2).mean(dim=1).contiguous()

@@ -222,6 +222,57 @@ def _pair_shapes(renders, guidance, mean, off0, off1, src1, p, masked) -> Tuple[
     return n, k, r
 
 
+def _stitch_crop_shapes(drawings, draw, offsets, r) -> Tuple[int, int, int]:
+    """(n, K, D) of a ``stitch_crops`` call, or ValueError."""
+    if drawings.dtype != torch.uint8 or drawings.dim() != 3 or drawings.shape[0] < 1 or drawings.shape[1] != drawings.shape[2]:
+        raise ValueError(f"stitch_crops: uint8 drawings [K,D,D] expected, got {drawings.dtype} {tuple(drawings.shape)}")
+    k, d = drawings.shape[0], drawings.shape[1]
+    if not 1 <= int(r) <= d:
+        raise ValueError(f"stitch_crops: window {r} outside 1..{d}")
+    if draw.dtype != torch.int32 or draw.dim() != 1:
+        raise ValueError(f"stitch_crops: int32 draw [n] expected, got {draw.dtype} {tuple(draw.shape)}")
+    n = draw.shape[0]
+    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (n, 2):
+        raise ValueError(f"stitch_crops: int32 offsets [{n},2] expected, got {offsets.dtype} {tuple(offsets.shape)}")
+    return n, k, d
+
+
+def _stitch_pair_shapes(fake, rects_a, rects_b, margin) -> Tuple[int, int, int]:
+    """(n, R, S) of a ``stitch_pairs`` call, or ValueError."""
+    if fake.dtype != torch.float32 or fake.dim() != 4 or fake.shape[1] != 3 or fake.shape[2] != fake.shape[3] or fake.shape[0] % 2:
+        raise ValueError(f"stitch_pairs: float32 images [2n,3,R,R] expected, got {fake.dtype} {tuple(fake.shape)}")
+    n, r = fake.shape[0] // 2, fake.shape[2]
+    if int(margin) < 0 or r - 3 * int(margin) < 1:
+        raise ValueError(f"stitch_pairs: margin {margin} leaves no crop window of {r} - 3 * margin pixels")
+    for name, q in (("rects_a", rects_a), ("rects_b", rects_b)):
+        if q.dtype != torch.int32 or tuple(q.shape) != (n, 8):
+            raise ValueError(f"stitch_pairs: int32 {name} [{n},8] expected, got {q.dtype} {tuple(q.shape)}")
+    return n, r, r - 3 * int(margin)
+
+
+def stitch_rect(dst, src, r: int):
+    """(r0, c0, r1, c1, sr0, sc0) of a composite of the ``src`` rectangle into the ``dst`` rectangle (each (rstart, cstart, rend, cend),
+    ends exclusive) of r x r images, or None where ``nb_stitch_pairs_f32`` composites nothing: an empty rectangle, one that leaves the
+    image, two of different extents."""
+    r0, c0, r1, c1 = (int(v) for v in dst)
+    sr0, sc0, sr1, sc1 = (int(v) for v in src)
+    ok = 0 <= r0 < r1 <= r and 0 <= c0 < c1 <= r and sr0 >= 0 and sr1 <= r and sc0 >= 0 and sc1 <= r and sr1 - sr0 == r1 - r0 and sc1 - sc0 == c1 - c0
+    return (r0, c0, r1, c1, sr0, sc0) if ok else None
+
+
+def stitch_rects(crop1, crop2, margin: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(rects_a, rects_b), int32 [8] each: (area1, area2) of ``compute_overlaps(crop1, offset_crop(crop2))`` and of
+    ``compute_overlaps(offset_crop(crop1), crop2)`` (stitching.py:248, 252), every area as (rstart, cstart, rend, cend); zeros -- "no
+    composite" -- where the crops do not overlap.  Crops are (row, column, height, width)."""
+    from .forger_losses import CropHelper
+    out = []
+    for a, b in ((crop1, CropHelper.offset_crop(crop2, margin)), (CropHelper.offset_crop(crop1, margin), crop2)):
+        _, a1, a2 = CropHelper.compute_overlaps(tuple(int(v) for v in a), tuple(int(v) for v in b))
+        out.append(np.zeros([8], np.int32) if a1 is None else
+                   np.array([a1.rstart, a1.cstart, a1.rend, a1.cend, a2.rstart, a2.cstart, a2.rend, a2.cend], np.int32))
+    return out[0], out[1]
+
+
 def on_white_f32(renders: torch.Tensor) -> torch.Tensor:
     """[n,3,R,R]: ``alpha * rgb + (1 - alpha) * 1.0`` (geom_metric.py:197-198, 232-233)."""
     alpha = renders[:, 3].unsqueeze(1)
@@ -394,6 +445,50 @@ class TileOpsBase:
             patches0 = bg_mask * patches0[:, :3] + (1 - bg_mask) * mc
             patches1 = bg_mask * patches1[:, :3] + (1 - bg_mask) * mc
         return torch.cat([patches0 * 2 - 1.0, patches1 * 2 - 1.0]).contiguous()
+
+    # -- inputs of the stitching scores: the torch restatements (``TileOps`` runs csrc/nb_stitch_metrics.hip and the HIP generator) --
+    def stitch_crops(self, drawings: torch.Tensor, draw: torch.Tensor, offsets: torch.Tensor, r: Optional[int] = None) -> torch.Tensor:
+        """[n,1,R,R] float32, the generator's geometry input of n windows of full-size drawings: window i is the R x R window of
+        ``drawings[draw[i]]`` ([K,D,D] uint8, 0 = stroke) at ``offsets[i]`` = (row, column), value / 255 (metric_main.py:183-189).
+        ``r``: the window's side (the engine's patch width).  An index is clamped into 0..K - 1 and an offset into 0..D - R."""
+        r = int(self.patch_width if r is None else r)
+        n, k, d = _stitch_crop_shapes(drawings, draw, offsets, r)
+        # value / 255 through a host-computed table: device division is not correctly rounded
+        lut = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(drawings.device)
+        j, o = draw.clamp(0, k - 1).tolist(), offsets.clamp(0, d - r).tolist()
+        if not n:
+            return torch.zeros([0, 1, r, r], dtype=torch.float32, device=drawings.device)
+        return torch.stack([lut[drawings[j[i], o[i][0]:o[i][0] + r, o[i][1]:o[i][1] + r].to(torch.int64)] for i in range(n)]).unsqueeze(1).contiguous()
+
+    def stitch_pairs(self, fake: torch.Tensor, rects_a: torch.Tensor, rects_b: torch.Tensor, margin: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(x [4n,3,S,S], l1 [2n]) of the raw generator images ``fake`` [2n,3,R,R] (rows :n the first crops, rows n: the second) of
+        ``RandomStitcher.generate_with_stitching``: the LPIPS input of the 2n pairs of ``compute_stitching_metrics``
+        (geom_metric.py:165-187) in the row convention of ``metric_pairs`` -- rows :n crop(fake1), n:2n crop(fake2), 2n:3n
+        crop(fake1 with fake2's pixels), 3n: crop(fake2 with fake1's pixels) -- and the sum of |first - second| of every pair.
+        ``rects_a`` / ``rects_b`` [n,8] int32: per sample the two areas (``stitch_rects``) of the first and of the second composite;
+        a pair that ``stitch_rect`` refuses composites nothing.  crop(img) = img[:, :, margin:R - 2 margin, margin:R - 2 margin]: the
+        reference's asymmetric crop, S = R - 3 margin.  Nothing is rescaled: every value of x is a copy of a value of ``fake``."""
+        n, r, s = _stitch_pair_shapes(fake, rects_a, rects_b, margin)
+        m = int(margin)
+        f1, f2 = fake[:n], fake[n:]
+        c1, c2 = f1.clone(), f2.clone()
+        for i, (qa, qb) in enumerate(zip(rects_a.tolist(), rects_b.tolist())):
+            a, b = stitch_rect(qa[:4], qa[4:], r), stitch_rect(qb[4:], qb[:4], r)
+            if a is not None:                                              # CropHelper.composite(fake1, fake2, area1, area2)
+                c1[i, :, a[0]:a[2], a[1]:a[3]] = f2[i, :, a[4]:a[4] + a[2] - a[0], a[5]:a[5] + a[3] - a[1]]
+            if b is not None:                                              # CropHelper.composite(fake2, fake1, area2, area1)
+                c2[i, :, b[0]:b[2], b[1]:b[3]] = f1[i, :, b[4]:b[4] + b[2] - b[0], b[5]:b[5] + b[3] - b[1]]
+        x = torch.cat([t[:, :, m:r - 2 * m, m:r - 2 * m] for t in (f1, f2, c1, c2)]).contiguous()
+        return x, (x[:2 * n] - x[2 * n:]).abs().sum(dim=(1, 2, 3))
+
+    def render_img(self, ws: torch.Tensor, geom_feats, positions: torch.Tensor, noise_set=None) -> torch.Tensor:
+        """[n,3,R,R] float32: the generator's raw image with the noise read at ``positions`` [n,2] and the checkpoint's constant noise
+        -- no compositing, no sfactor, what ``RandomStitcher.generate_with_stitching`` scores (stitching.py:244-245)."""
+        if noise_set is not None:
+            raise ValueError("render_img: this ops has no noise sets")
+        syn = getattr(self.G.synthesis, "forward", self.G.synthesis)
+        takes = any(p.name == "noise_mode" or p.kind is p.VAR_KEYWORD for p in inspect.signature(syn).parameters.values())
+        return self.G.forward_pre_mapped(ws, geom_feats, positions=positions, **({"noise_mode": "const"} if takes else {}))
 
     def render_rgba(self, ws: torch.Tensor, geom_feats, user_colors=None, sfactor=None, noise_set=None) -> torch.Tensor:
         """[n,4,R,R] float32 in 0..1: the un-positioned "clear" render of the paint engine (brush.py:763-792) with the checkpoint's
@@ -789,6 +884,45 @@ class TileOps(TileOpsBase):
                                                       None if src1 is None else _p(src1.contiguous()), k, r, int(p), n, flags, _p(out),
                                                       self._stream()), "metric_pairs")
         return out
+
+    # -- inputs of the stitching scores (csrc/nb_stitch_metrics.hip) --
+    def stitch_crops(self, drawings: torch.Tensor, draw: torch.Tensor, offsets: torch.Tensor, r: Optional[int] = None) -> torch.Tensor:
+        """[n,1,R,R] on the device, one launch (``nb_stitch_crops_u8``): n windows of the full-size drawings as geometry input."""
+        r = int(self.patch_width if r is None else r)
+        n, k, d = _stitch_crop_shapes(drawings, draw, offsets, r)
+        if any(t.device != self.device for t in (drawings, draw, offsets)):
+            raise ValueError("stitch_crops: drawings and windows must be on the engine's device")
+        out = torch.empty([n, 1, r, r], dtype=torch.float32, device=self.device)
+        if n == 0:                                                         # (empty tensors have no address to hand over)
+            return out
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_stitch_crops_u8(_p(drawings.contiguous()), k, d, _p(draw.contiguous()), _p(offsets.contiguous()), n, r, _p(out),
+                                                     self._stream()), "stitch_crops")
+        return out
+
+    def stitch_pairs(self, fake: torch.Tensor, rects_a: torch.Tensor, rects_b: torch.Tensor, margin: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(x [4n,3,S,S], l1 [2n]) on the device (``nb_stitch_pairs_f32``: one pass over the images and a fixed-order finish; the same
+        input gives the same bits).  A view whose images are dense [3,R,R] blocks is read in place."""
+        n, r, s = _stitch_pair_shapes(fake, rects_a, rects_b, margin)
+        if any(t.device != self.device for t in (fake, rects_a, rects_b)):
+            raise ValueError("stitch_pairs: images and rectangles must be on the engine's device")
+        count = r * r
+        if fake.stride(3) != 1 or fake.stride(2) != r or fake.stride(1) != count or (2 * n > 1 and fake.stride(0) < 3 * count):
+            fake = fake.contiguous()
+        x = torch.empty([4 * n, 3, s, s], dtype=torch.float32, device=self.device)
+        l1 = torch.empty([2 * n], dtype=torch.float32, device=self.device)
+        if n == 0:
+            return x, l1
+        partials = torch.empty([n, _lib.NB_STITCH_PARTS, 2], dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().nb_stitch_pairs_f32(_p(fake), max(int(fake.stride(0)), 3 * count), _p(rects_a.contiguous()), _p(rects_b.contiguous()),
+                                                      n, r, int(margin), _p(x), _p(l1), _p(partials), self._stream()), "stitch_pairs")
+        return x, l1
+
+    def render_img(self, ws: torch.Tensor, geom_feats, positions: torch.Tensor, noise_set=None) -> torch.Tensor:
+        """[n,3,R,R] float32: ONE positioned generator pass with the checkpoint's constant noise, the raw image."""
+        kw = {} if noise_set is None else {"noise_set": noise_set}
+        return self.G.forward_pre_mapped(ws, geom_feats, positions=positions, noise_mode="const", **kw)
 
     def render_rgba(self, ws: torch.Tensor, geom_feats, user_colors=None, sfactor=None, noise_set=None) -> torch.Tensor:
         """[n,4,R,R] float32 in 0..1: ONE un-positioned "clear" generator pass, composited in the ToRGB launch."""

@@ -738,6 +738,42 @@ int nb_bg_mean_colors_f32(const float* renders, long long stride_n, const float*
 int nb_metric_pairs_f32(const float* renders, long long stride_n, const float* blur1, const float* mean, const int32_t* off0,
                         const int32_t* off1, const int32_t* src1, int k, int r, int p, int n, int flags, float* out, void* stream);
 
+/* ---- inputs of the stitching scores (csrc/nb_stitch_metrics.hip): what the reference's metric loop (forger/metrics/metric_main.py:
+ * 181-200) and compute_stitching_metrics (forger/metrics/geom_metric.py:165-187) do around the two generator passes of
+ * RandomStitcher.generate_with_stitching (forger/train/stitching.py:212-267).  fp32 throughout, no float atomics: the same input
+ * gives the same bits.  The entries only enqueue on `stream`: no allocation, no host wait.
+ *
+ * The generator's geometry input of n windows of full-size drawings: out [n,1,r,r] fp32, out[i] = the r x r window of drawing
+ * draw[i] of drawings [k,d,d] uint8 (0 = stroke) at (row, column) = off[2 i], off[2 i + 1], value / 255 in correctly rounded fp32.
+ * draw and off live on the device: an index is clamped into 0..k - 1 and an offset into 0..d - r there.  16-byte stores when r is a
+ * multiple of four and out is 16-byte aligned.  n == 0: NB_OK without a launch.  NB_EINVAL: a null pointer, k outside 1..65535, r
+ * outside 1..8192, d outside r..32768, n outside 0..2^24, draw, off or out not 4-byte aligned. */
+int nb_stitch_crops_u8(const uint8_t* drawings, int k, int d, const int32_t* draw, const int32_t* off, int n, int r, float* out,
+                       void* stream);
+
+/* Workgroups that share one sample in nb_stitch_pairs_f32: `partials` holds n * NB_STITCH_PARTS * 2 floats. */
+#define NB_STITCH_PARTS 32
+
+/* The LPIPS input and the L1 sums of the 2n pairs of n stitched samples.  fake: 2n raw generator images of three dense planes of
+ * r * r floats at fake + j * stride_n (stride_n >= 3 r r: a view is read in place); images 0..n-1 are the first crops (fake1),
+ * n..2n-1 the second (fake2).  rects_a / rects_b [n,8] int32 on the device, per sample (area1, area2), each (rstart, cstart, rend,
+ * cend) with exclusive ends: rects_a those of compute_overlaps(crop1, offset_crop(crop2)) (stitching.py:248), rects_b those of
+ * compute_overlaps(offset_crop(crop1), crop2) (:252).  With crop(img) = img[:, margin:r - 2 margin, margin:r - 2 margin] -- the
+ * reference's ASYMMETRIC crop (geom_metric.py:173-177), s = r - 3 margin wide -- out [4n,3,s,s] is, in the row convention of
+ * nb_metric_pairs_f32 (first sides, then second sides):
+ *     out[i]      = crop(fake1[i])                         out[2n + i] = crop(fake1[i] with fake2[i]'s area2 of rects_a in area1)
+ *     out[n + i]  = crop(fake2[i])                         out[3n + i] = crop(fake2[i] with fake1[i]'s area1 of rects_b in area2)
+ * (CropHelper.composite, stitching.py:161-179, 249, 253), every value a copy of an input float (nothing is rescaled), and
+ * l1[j] = sum over the 3 s s entries of |out[j] - out[2n + j]| for j < 2n: only a rectangle's part inside the crop window adds to
+ * it.  A rectangle pair that is empty (zero or negative extent), leaves 0..r or whose two extents differ means "no composite": the
+ * second side equals the first and the sum is 0.  NB_STITCH_PARTS workgroups share a sample and leave partial sums in `partials`; a
+ * second small launch of the same call adds them in a fixed order.  16-byte loads and stores when s, r, margin and stride_n are
+ * multiples of four and fake and out are 16-byte aligned; otherwise element by element.  n == 0: NB_OK without a launch.
+ * NB_EINVAL: a null pointer, r outside 1..8192, n outside 0..2^22, margin < 0 or 3 margin >= r, stride_n < 3 r r, a pointer not
+ * 4-byte aligned. */
+int nb_stitch_pairs_f32(const float* fake, long long stride_n, const int32_t* rects_a, const int32_t* rects_b, int n, int r, int margin,
+                        float* out, float* l1, float* partials, void* stream);
+
 /* ---- clarity optimisation of brushes (csrc/nb_clarity.hip): what one step of run_one_clarity_opt (scripts/opt_clarity_main.py:93-167)
  * does around the generator, for k brushes at once.  The state of k brushes is an arena [k, p] of floats (row stride given per call):
  * a row is W+ (nw floats) followed by noise planes.  NbClarityPlanes lists the planes in the order of their offsets: side (a power of
