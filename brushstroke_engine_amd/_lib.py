@@ -159,6 +159,10 @@ PROTOTYPES = {
     "nb_raster_segments_u8": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "nb_spline_flatten_f32": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp]),
     "nb_spline_segment_count": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    # synthetic drawings (csrc/nb_drawings.hip): seeded spline control points, K drawings rasterised in one launch
+    "nb_synth_spline_counts": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, vp]),
+    "nb_synth_spline_ctrl_f32": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "nb_raster_batch_u8": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     # compositing for a paint session (csrc/nb_compose.hip): tiles over a canvas, a reduced view of a canvas window
     "nb_over_tiles_u8": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, vp]),
@@ -293,6 +297,17 @@ class NbPassPlan(C.Structure):
 
 NB_GEOM_PREP_WS_BYTES = 1040
 NB_SEG_PITCH = 8
+NB_SPLINE_MODES = {"uniform": 0, "cells": 1}
+NB_THICK_MODES = {"fixed": 0, "range": 1, "mixture": 2}
+NB_SYNTH_MAX_POINTS, NB_SYNTH_MAX_MIX, NB_SYNTH_COORD_ROUNDINGS = 64, 4, 3
+
+
+class NbSplineSpec(C.Structure):
+    """``struct NbSplineSpec`` of include/neube_hip.h (drawings.SplineSpec)."""
+    _fields_ = [("pts_min", C.c_int32), ("pts_max", C.c_int32), ("mode", C.c_int32), ("thick_mode", C.c_int32), ("radius", C.c_float),
+                ("rmin", C.c_int32), ("rmax", C.c_int32), ("n_mix", C.c_int32), ("center", C.c_float * 4), ("sigma", C.c_float * 4),
+                ("cdf", C.c_float * 4)]
+
 NB_BRUSH_METRICS_PARTS = 16
 NB_BG_MEAN_PARTS = 16
 NB_METRIC_PAIRS_TRANSPOSE, NB_METRIC_PAIRS_MASKED = 1, 2

@@ -29,7 +29,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Icons, colours and clear-background factors of a brush library on MI355X.")
     ap.add_argument("--gan_checkpoint", required=True, help=".npz engine container (generator + encoder)")
     ap.add_argument("--library", default="rand100")
-    ap.add_argument("--uvs_calibration", required=True, help=".npz with 'medium' and 'thick' [5,R,R] uint8 calibration drawings")
+    ap.add_argument("--uvs_calibration", required=True, help=".npz with 'medium' and 'thick' [5,R,R] uint8 calibration drawings, or synth[:seed]")
     ap.add_argument("--output_file_prefix", required=True)
     ap.add_argument("--icon_k", type=int, default=1, help="reduce the icons by this factor (1..16, a divisor of the patch width)")
     ap.add_argument("--cols", type=int, default=10, help="icons per row of the contact sheet")
@@ -57,8 +57,8 @@ def main(argv=None):
     if not encoder.HipGeometryEncoder.supports(cfg.img_resolution):
         raise RuntimeError(f"the geometry-encoder kernels tile patches of 32, 64 or 128 k pixels; this checkpoint paints {cfg.img_resolution}")
     ops = painting.TileOps(G, encoder.HipGeometryEncoder(enc_sd, preproc_type=preproc, device=device))
-    with np.load(args.uvs_calibration) as z:
-        mapper = painting.StyleUVSMapper(ops, z["medium"], z["thick"])
+    from .drawings import load_calibration
+    mapper = painting.StyleUVSMapper(ops, *load_calibration(args.uvs_calibration, cfg.img_resolution, device))
     library = formats.BrushLibrary.from_arg(args.library, z_dim=G.z_dim)
     with torch.no_grad():
         cat = mapper.catalogue(library, batch=args.batch, icon_k=args.icon_k)

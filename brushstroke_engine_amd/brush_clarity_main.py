@@ -38,7 +38,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Optimise brushes of a library for a clear background on MI355X.")
     ap.add_argument("--gan_checkpoint", required=True, help=".npz engine container (generator + encoder)")
     ap.add_argument("--library", required=True, help="what paint_image_main takes: a file, rand<N>, a seed count or a seed list")
-    ap.add_argument("--drawings", required=True, help=".npz with [K,R,R] uint8 guidance drawings (0 = stroke)")
+    ap.add_argument("--drawings", required=True, help=".npz with [K,R,R] uint8 guidance drawings (0 = stroke), or synth:K[:seed[:key=value,...]]")
     ap.add_argument("--out_library", required=True, help='output W library (pickle), or "default"')
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--brush_id", default=None, help="optimise this brush only (default: the whole library)")
@@ -47,7 +47,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--losses", default=clarity.DEFAULT_LOSSES)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--brushes_per_pass", type=int, default=4, help="brushes that share an encoder pass and a generator batch")
-    ap.add_argument("--uvs_calibration", default=None, help=".npz with 'medium' and 'thick' calibration drawings: score with the brushes' factors")
+    ap.add_argument("--uvs_calibration", default=None, help=".npz with 'medium' and 'thick' calibration drawings, or synth[:seed]: score with the brushes' factors")
     ap.add_argument("--lpips_weights", default=None, help=".npz of tools/convert_lpips_weights.py: allows lpips(<component>) in --losses")
     return ap
 
@@ -102,7 +102,7 @@ def main(argv=None):
     if not encoder.HipGeometryEncoder.supports(cfg.img_resolution):
         raise RuntimeError(f"the geometry-encoder kernels tile patches of 32, 64 or 128 k pixels; this checkpoint paints {cfg.img_resolution}")
     enc = encoder.HipGeometryEncoder(enc_sd, preproc_type=preproc, device=device)
-    drawings = load_drawings(args.drawings)
+    drawings = load_drawings(args.drawings, cfg.img_resolution, device)
     library = formats.BrushLibrary.from_arg(args.library, z_dim=cfg.z_dim)
     ids = [args.brush_id] if args.brush_id is not None else list(library.get_style_ids())
     out_library = default_out_library(args.library, args.output_dir) if args.out_library == "default" else args.out_library
@@ -112,8 +112,8 @@ def main(argv=None):
     ops = painting.TileOps(Generator(cfg, gen_sd).to(device), enc)
     mapper = None
     if args.uvs_calibration:
-        with np.load(args.uvs_calibration) as z:
-            mapper = painting.StyleUVSMapper(ops, z["medium"], z["thick"])
+        from .drawings import load_calibration
+        mapper = painting.StyleUVSMapper(ops, *load_calibration(args.uvs_calibration, cfg.img_resolution, device))
     with torch.no_grad():
         evaluator = metrics.BrushEvaluator(ops, drawings, seed=args.seed or 0, uvs_mapper=mapper)
         before = evaluator.evaluate(library, style_ids=ids)

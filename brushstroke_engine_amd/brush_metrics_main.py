@@ -33,8 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Colour and transparency scores of a brush library on MI355X.")
     ap.add_argument("--gan_checkpoint", required=True, help=".npz engine container (generator + encoder)")
     ap.add_argument("--library", default="rand100")
-    ap.add_argument("--drawings", required=True, help=".npz with [K,R,R] uint8 guidance drawings (0 = stroke)")
-    ap.add_argument("--uvs_calibration", default=None, help=".npz with 'medium' and 'thick' calibration drawings: render with the brushes' factors")
+    ap.add_argument("--drawings", required=True, help=".npz with [K,R,R] uint8 guidance drawings (0 = stroke), or synth:K[:seed[:key=value,...]] (drawings.parse_synth)")
+    ap.add_argument("--uvs_calibration", default=None, help=".npz with 'medium' and 'thick' calibration drawings, or synth[:seed]: render with the brushes' factors")
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--prefix", default="", help="prefix of the three file names")
     ap.add_argument("--rounds", type=int, default=1, help="renders per brush, each with fresh primary colours")
@@ -50,16 +50,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--patch_width", type=int, default=None,
                     help="side of the windows of the LPIPS_UNIFORM_BG scores (default: R / 4, R / 2 or 0.8 R, the first of at least 64)")
     ap.add_argument("--stitch_drawings", default=None,
-                    help=".npz with [Ks,D,D] uint8 full-size drawings (0 = stroke), D above the patch width: also report STITCH_L1 and "
+                    help=".npz with [Ks,D,D] uint8 full-size drawings (0 = stroke), D above the patch width, or synth:Ks:seed:size=D: also report STITCH_L1 and "
                          "STITCH_LPIPS (needs --lpips_weights)")
     ap.add_argument("--stitch_margin", type=int, default=10, help="the stitcher's crop margin (RandomStitcher.crop_margin)")
     ap.add_argument("--stitch_min_overlap", type=int, default=50, help="the stitcher's minimum overlap of the two crops")
     return ap
 
 
-def load_drawings(path: str) -> np.ndarray:
-    with np.load(path) as z:
-        return np.asarray(z["drawings"] if "drawings" in z.files else z[z.files[0]], np.uint8)
+def load_drawings(path: str, r=None, device="cpu") -> np.ndarray:
+    """[K,D,D] uint8 drawings: the .npz at ``path``, or ``synth:K[:seed[:key=value,...]]`` of patch width ``r`` made on ``device``
+    (``drawings.load_drawings``)."""
+    from .drawings import load_drawings as load
+    return load(path, r, device)
 
 
 def write_scores(scores: metrics.BrushScores, out_dir: str, prefix: str = ""):
@@ -84,17 +86,17 @@ def main(argv=None):
     ops = painting.TileOps(G, encoder.HipGeometryEncoder(enc_sd, preproc_type=preproc, device=device))
     mapper = None
     if args.uvs_calibration:
-        with np.load(args.uvs_calibration) as z:
-            mapper = painting.StyleUVSMapper(ops, z["medium"], z["thick"])
+        from .drawings import load_calibration
+        mapper = painting.StyleUVSMapper(ops, *load_calibration(args.uvs_calibration, cfg.img_resolution, device))
     library = formats.BrushLibrary.from_arg(args.library, z_dim=G.z_dim)
     with torch.no_grad():
-        evaluator = metrics.BrushEvaluator(ops, load_drawings(args.drawings), seed=args.seed, uvs_mapper=mapper)
+        evaluator = metrics.BrushEvaluator(ops, load_drawings(args.drawings, cfg.img_resolution, device), seed=args.seed, uvs_mapper=mapper)
         kw = {}
         if args.lpips_weights:
             from .perceptual import LPIPS
             kw = dict(lpips=LPIPS(args.lpips_weights, net=args.lpips_net, device=device), patch_width=args.patch_width)
         if args.stitch_drawings:
-            kw["stitch"] = metrics.StitchSetup(load_drawings(args.stitch_drawings), args.stitch_margin, args.stitch_min_overlap)
+            kw["stitch"] = metrics.StitchSetup(load_drawings(args.stitch_drawings, cfg.img_resolution, device), args.stitch_margin, args.stitch_min_overlap)
         scores = evaluator.evaluate(library, rounds=args.rounds, batch=args.batch, lab_thresh=args.lab_thresh, **kw)
     paths = write_scores(scores, args.output_dir, args.prefix)
     logger.info(f"Scored {len(scores.ids)} brushes: {paths}")

@@ -22,8 +22,8 @@ LIB = os.path.join(CSRC, "libneube_hip.so")
 SOURCES = ["nb_modconv_up1_h3.hip", "nb_modconv_up2_h3.hip", "nb_modconv_up2v.hip", "nb_encoder.hip", "nb_ops.hip", "nb_modconv.hip", "nb_pack_h2.hip",
            "nb_modconv_small.hip", "nb_grad.hip", "nb_canvas.hip", "nb_calib.hip", "nb_generator.hip", "nb_weight_pack.hip", "nb_gen_plan.hip", "nb_gen_encoder.hip", "nb_geomprep.hip", "nb_noise_seeded.hip", "nb_brush_noise.hip",
            "nb_strokes.hip", "nb_compose.hip", "nb_select.hip", "nb_metrics.hip", "nb_clarity.hip", "nb_projection.hip", "nb_lpips.hip", "nb_metric_patches.hip",
-           "nb_stitch_metrics.hip"]
-HEADERS = ["nb_common.h", "nb_h3_common.h", "nb_h3_launch.h", "nb_torgb.h", "nb_gen_internal.h", os.path.join("..", "..", "include", "neube_hip.h")]
+           "nb_stitch_metrics.hip", "nb_drawings.hip"]
+HEADERS = ["nb_common.h", "nb_h3_common.h", "nb_h3_launch.h", "nb_torgb.h", "nb_gen_internal.h", "nb_philox.h", "nb_raster_cell.h", os.path.join("..", "..", "include", "neube_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall",
@@ -48,6 +48,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-fn
 # nb_lpips.hip: scalar fp32 per element (one add, maxima, a quotient) and scalar fp64 channel sums per pixel: the same case.
 # nb_metric_patches.hip: scalar fp32 per pixel (the composite, the fill and the rescale of four pixels per thread, 25-tap sums): the same case.
 # nb_stitch_metrics.hip: copies, and scalar fp32 sums of absolute differences in a stated order, four pixels per thread: the same case.
+# nb_drawings.hip: the flags of nb_strokes.hip, whose per-cell raster code it shares (nb_raster_cell.h: the two must give the same bytes);
+# its sampler is scalar fp32 per control point, x and y through the same two or three operations: the same case.
 # nb_generator.hip, nb_weight_pack.hip: the generator's small set-up kernels and weight packers, scalar fp32 per element, were one file.
 FILE_FLAGS = {"nb_modconv.hip": ["-fno-slp-vectorize"], "nb_ops.hip": ["-fno-slp-vectorize"],
               "nb_modconv_up2v.hip": ["-fno-slp-vectorize"], "nb_generator.hip": ["-fno-slp-vectorize"], "nb_weight_pack.hip": ["-fno-slp-vectorize"],
@@ -56,7 +58,8 @@ FILE_FLAGS = {"nb_modconv.hip": ["-fno-slp-vectorize"], "nb_ops.hip": ["-fno-slp
               "nb_compose.hip": ["-fno-slp-vectorize"], "nb_select.hip": ["-fno-slp-vectorize"],
               "nb_metrics.hip": ["-fno-slp-vectorize"], "nb_clarity.hip": ["-fno-slp-vectorize"],
               "nb_projection.hip": ["-fno-slp-vectorize"], "nb_lpips.hip": ["-fno-slp-vectorize"],
-              "nb_metric_patches.hip": ["-fno-slp-vectorize"], "nb_stitch_metrics.hip": ["-fno-slp-vectorize"]}
+              "nb_metric_patches.hip": ["-fno-slp-vectorize"], "nb_stitch_metrics.hip": ["-fno-slp-vectorize"],
+              "nb_drawings.hip": ["-fno-slp-vectorize"]}
 
 
 STAMP = LIB + ".stamp"

@@ -118,8 +118,8 @@ def main(argv=None) -> str:
     ops = painting.TileOps(G, enc)
     mapper = None
     if not args.no_uvs_mapping and args.uvs_calibration:
-        with np.load(args.uvs_calibration) as z:
-            mapper = painting.StyleUVSMapper(ops, z["medium"], z["thick"])
+        from .drawings import load_calibration
+        mapper = painting.StyleUVSMapper(ops, *load_calibration(args.uvs_calibration, cfg.img_resolution, device))
     library = formats.BrushLibrary.from_arg(args.library, z_dim=G.z_dim)
     opts = painting.GanBrushOptions()
     opts.enable_uvs_mapping = mapper is not None

@@ -152,9 +152,8 @@ def main(argv=None) -> str:
     ops = painting.TileOps(G, encoder.HipGeometryEncoder(enc_sd, preproc_type=preproc, device=device))
     mapper = None
     if args.uvs_calibration:
-        import numpy as np
-        with np.load(args.uvs_calibration) as z:
-            mapper = painting.StyleUVSMapper(ops, z["medium"], z["thick"])
+        from .drawings import load_calibration
+        mapper = painting.StyleUVSMapper(ops, *load_calibration(args.uvs_calibration, cfg.img_resolution, device))
     session = run_script(painting.PaintingHelper(ops, uvs_mapper=mapper), script, G.z_dim)
     from PIL import Image
     output_file = args.output_file_prefix + ".png"

@@ -344,6 +344,13 @@ class TileOpsBase:
             return out
         return torch.from_numpy(raster_strokes_numpy(strokes, (int(out_shape[0]), int(out_shape[1])), offset, subdiv))
 
+    def raster_strokes_batch(self, stroke_lists, out_shape, offset=(0, 0), subdiv: int = 8) -> torch.Tensor:
+        """One drawing per ``StrokeList``: [K, out_h, out_w] uint8 geometry, each as ``raster_strokes`` gives it for that list alone."""
+        shape = (int(out_shape[0]), int(out_shape[1]))
+        if not len(stroke_lists):
+            raise ValueError("raster_strokes_batch: no stroke lists")
+        return torch.from_numpy(np.stack([raster_strokes_numpy(s, shape, offset, subdiv) for s in stroke_lists]))
+
     # -- brush calibration: the torch restatements (``TileOps`` runs csrc/nb_select.hip and the HIP generator) --
     def masked_kth_largest(self, x: torch.Tensor, mask: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """(kth [n] float32, n_masked [n] int32): per image of ``x`` [n,1,h,w] or [n,h,w] (a strided view is fine) the ``k``-th largest
@@ -1094,3 +1101,29 @@ class TileOps(TileOpsBase):
         pixel ``offset`` = (off_y, off_x): splines are flattened on the device, and polyline and spline segments are rasterised in
         one ``nb_raster_segments_u8`` launch.  ``out`` given: the strokes are added to that geometry (every other byte untouched)."""
         return self.raster_segments(self.stroke_segments(strokes, subdiv), out_shape, offset, out)
+
+    def raster_strokes_batch(self, stroke_lists, out_shape, offset=(0, 0), subdiv: int = 8) -> torch.Tensor:
+        """One drawing per ``StrokeList``: [K, out_h, out_w] uint8 on the device, byte for byte what ``raster_strokes`` gives for each
+        list alone, from one ``nb_spline_flatten_f32`` launch over all splines and one ``nb_raster_batch_u8`` launch over all
+        drawings.  Polyline rows are uploaded and joined with their drawing's spline rows on the device; nothing is read back."""
+        from .drawings import raster_batch
+        k = len(stroke_lists)
+        if not k:
+            raise ValueError("raster_strokes_batch: no stroke lists")
+        merged = StrokeList()
+        for s in stroke_lists:
+            merged._ctrl.extend(s._ctrl)
+        spl = self.stroke_segments(merged, subdiv)                  # all splines, drawing after drawing
+        n_spl = np.array([s.spline_segment_count(subdiv) for s in stroke_lists], np.int64)
+        polys = [s.polyline_segments() for s in stroke_lists]
+        if any(p.shape[0] for p in polys):
+            ends = np.cumsum(n_spl)
+            pieces = []
+            for i, p in enumerate(polys):
+                pieces += [self.to_device(p), spl[int(ends[i] - n_spl[i]):int(ends[i])]]
+            segs = torch.cat(pieces)
+        else:
+            segs = spl
+        seg_off = np.zeros(k + 1, np.int32)
+        np.cumsum(n_spl + np.array([p.shape[0] for p in polys], np.int64), out=seg_off[1:])
+        return raster_batch(segs, seg_off, out_shape, offset, device=self.device)

@@ -601,6 +601,76 @@ int nb_spline_flatten_f32(const float* ctrl, const int32_t* stroke_off, int n_po
  * GPU).  NB_EINVAL (negative) for n_strokes < 0, subdiv < 1 or n_points_total < 4 * n_strokes. */
 long long nb_spline_segment_count(int n_points_total, int n_strokes, int subdiv);
 
+/* ---- synthetic drawings: seeded random spline patches, rasterised K at a time (csrc/nb_drawings.hip) -----------------------------
+ * What scripts/create_splines.py of the reference makes on the host, one image per process-pool task: random centripetal
+ * Catmull-Rom control points (create_splines.py:35-39, forger/core/curve.py:98-116 sample_control_pts2), a thickness from a Gaussian
+ * mixture or an integer range (forger/util/spline_dist.py:37-96) or a fixed radius (--use_radii, create_splines.py:49-52), the curve
+ * drawn and dilated (create_splines.py:47-59).  Here: counts -> control points -> nb_spline_flatten_f32 -> one batch raster.
+ * Departures, all stated: (1) the draws are a pure function of (seed, drawing, draw index) instead of the process-global `random`
+ * and `np.random` streams; (2) the drawing is the capsule union of nb_raster_segments_u8, not a sampled curve dilated by a disc;
+ * (3) sample_control_pts2 marks the TRANSPOSED cell as used (curve.py:110, quadrants[idx[1], idx[0]]), so it can repeat a cell while
+ * others stay free; that is not reproduced: cells are used without replacement; (4) the thickness loop `while res < -0.5`
+ * (spline_dist.py:75-76) is bounded to eight tries.
+ *
+ * The draws.  For drawing k of a call, s = offset + k (uint64, wraps), and
+ *     P(j) = Philox4x32-10(counter = (j, 0x53504C4E, lo32(s), hi32(s)), key = (lo32(seed), hi32(seed)))  -> (x0, x1, x2, x3)
+ * with the constants of nb_noise_seeded_f32; u(x) = (x >> 8) * 2^-24 (exact in fp32).  So drawing k at offset o is drawing 0 at
+ * offset o + k, at any batch size.
+ *   P(0):        npts = pts_min + x0 mod (pts_max - pts_min + 1).  Mixture component c = the first with u(x1) < cdf[c].  Integer-range
+ *                thickness: radius = rmin + x2 mod (rmax - rmin + 1).
+ *   P(1 + i), i = 0..7: Gaussian thickness tries.  z = the even normal of pair(x0, x1) as nb_noise_seeded_f32 defines it;
+ *                v = center[c] + sigma[c] * z (one fp32 multiply, one add); the first v >= -0.5 is taken, radius = rintf(v); none
+ *                accepted: radius 0.
+ *   P(16 + i), i < npts: control point i.  NB_SPLINE_CELLS, i < 16: the free cell number x0 mod (16 - i) of the 4 x 4 grid, free
+ *                cells counted in ascending index, cx = cell mod 4, cy = cell div 4, X = (cx + u(x1)) * (r / 4), Y = (cy + u(x2)) *
+ *                (r / 4); i >= 16: X = (u(x1) * 1.1f - 0.05f) * r, Y likewise from x2.  NB_SPLINE_UNIFORM (rand * 2.2 - 1 of
+ *                create_splines.py:39 in pixels): X = (u(x1) * 1.1f) * r, Y from x2.
+ *   The row is (X, Y, r_eff), r_eff = radius for radius >= 2 and 0.5 below (the reference leaves its one-pixel curve undilated
+ *   below 2, create_splines.py:58).  Coordinates carry at most NB_SYNTH_COORD_ROUNDINGS fp32 roundings, each within one ulp(1.1 r).
+ * The curve of a drawing runs from its control point 1 to npts - 2 (draw_spline_custom; nb_spline_flatten_f32 does the same). */
+#define NB_SPLINE_UNIFORM 0
+#define NB_SPLINE_CELLS 1
+#define NB_THICK_FIXED 0
+#define NB_THICK_RANGE 1
+#define NB_THICK_MIXTURE 2
+#define NB_SYNTH_MAX_POINTS 64
+#define NB_SYNTH_MAX_MIX 4
+#define NB_SYNTH_COORD_ROUNDINGS 3
+typedef struct NbSplineSpec {
+    int32_t pts_min, pts_max;     /* 4 <= pts_min <= pts_max <= NB_SYNTH_MAX_POINTS (reference: 4..15) */
+    int32_t mode;                 /* NB_SPLINE_UNIFORM | NB_SPLINE_CELLS (--smart_sampling) */
+    int32_t thick_mode;           /* NB_THICK_FIXED | NB_THICK_RANGE | NB_THICK_MIXTURE */
+    float radius;                 /* NB_THICK_FIXED: the radius in pixels, >= 0 */
+    int32_t rmin, rmax;           /* NB_THICK_RANGE: 0 <= rmin <= rmax (reference: 1..30) */
+    int32_t n_mix;                /* NB_THICK_MIXTURE: 1..NB_SYNTH_MAX_MIX components */
+    float center[4], sigma[4];    /* (reference: centres 6, 10, sigmas 2, 3, for 256-pixel patches) */
+    float cdf[4];                 /* normalised cumulative weights (reference: 6 : 10), non-decreasing, cdf[n_mix - 1] = 1 */
+} NbSplineSpec;
+
+/* npts[k] control points of drawings offset .. offset + k - 1 (HOST ONLY: no HIP call, works without a GPU; pure integer
+ * arithmetic).  From it the caller builds stroke_off [k + 1] and the totals of nb_synth_spline_ctrl_f32 and nb_spline_flatten_f32
+ * with no device read-back.  NB_EINVAL: a null pointer, k < 0, a spec outside the ranges stated at NbSplineSpec. */
+int nb_synth_spline_counts(const NbSplineSpec* spec, uint64_t seed, uint64_t offset, int k, int32_t* npts);
+
+/* ctrl [n_points_total][3] device fp32: rows stroke_off[d] .. stroke_off[d + 1] are the control points (X, Y, r_eff) of drawing d
+ * of side r, d < k.  spec is a host struct, passed by value to the kernel; stroke_off [k + 1] is device int32 and read on the device
+ * only.  One lane per drawing (the cell choice is sequential).  A drawing whose stroke_off entries disagree with its count, or
+ * reach outside 0..n_points_total, is skipped: nothing outside ctrl is ever written.  Enqueue only.  NB_EINVAL: a null pointer, a
+ * bad spec, k < 1, r outside 1..2^20, n_points_total outside pts_min * k .. pts_max * k. */
+int nb_synth_spline_ctrl_f32(const NbSplineSpec* spec, uint64_t seed, uint64_t offset, int k, int r, const int32_t* stroke_off,
+                             float* ctrl, int n_points_total, void* stream);
+
+/* out [k,h,w] uint8 (any alignment, any size): drawing i is rows seg_off[i] .. seg_off[i + 1] of segs (NB_SEG_PITCH floats each, device
+ * fp32, 16-byte aligned; seg_off [k + 1] device int32), rasterised under the contract of nb_raster_segments_u8 with clear = 1: every
+ * byte is written, a drawing with an empty range is all 255, rows with a non-finite value or r < 0 draw nothing, and the bytes are
+ * IDENTICAL to that entry's on the same rows (the per-cell code is one function).  A drawing's rows darken that drawing only:
+ * curves that leave the patch are clipped at its edges.  A range outside 0..n_segs_total, or a decreasing one, draws nothing and
+ * reads nothing.  This replaces the draw and the dilation of create_splines.py:47-59 for K images at once.  One 256-thread workgroup
+ * per 64 x 64 cell of one drawing (grid = k * cells).  Enqueue only.  NB_EINVAL: a null pointer, n_segs_total < 0, k < 1,
+ * non-positive sizes, h * w >= 2^31, k * cells >= 2^31, unaligned segs. */
+int nb_raster_batch_u8(const float* segs, const int32_t* seg_off, int n_segs_total, int k, uint8_t* out, int h, int w, int off_y,
+                       int off_x, void* stream);
+
 /* ---- compositing for a paint session: tiles over a canvas, a reduced view of a window (csrc/nb_compose.hip) ----------------------
  * What the reference leaves to its browser client -- the patches of a stroke written into a foreground layer with putImageData
  * (forger/ui/js/main_controller.js:776) and that layer drawn over the background canvas when the stroke ends
